@@ -2,6 +2,7 @@
 """bench.py — Msamples/s of the RTIOW cover-scene render on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f64|f32] [--config 1|2]
+                  [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU, RCCL backend.  Either launched by
   torch.distributed.run, or — plain `python bench.py --gpus N` — this script
   starts torch.distributed.run itself as a child process before touching the
@@ -20,9 +21,18 @@ traces 1200 x 675/N x 500N ~= 405 M samples, bit-identical to the same rows of
 a 1-GPU render of the N*500-spp frame.  value = samples of all ranks / max
 rank time.
 
-Extra fields: roofline (dominant kernel = trace; HIP events on the render
-stream), cpu_baseline (oracle Tier A = the reference's algorithm, sequential
-RNG, one core, on a bounded sample of the same frame), f32_hybrid_variant,
+A plain run sets up, warms up, times the K steps and prints the headline
+line (metric, value, unit, ms_per_step, dist, config); nothing else runs.
+--dump-outputs DIR writes what the last timed step computed, the frame a
+caller of the timed path receives, as DIR/image.npy (float32; a fixed seeded
+sample of the pixels, with DIR/image_index.npy, where the frame is over the
+64 MB limit).  The scene, camera and RNG are seeded, so the same arguments
+give the same inputs and, build for build, comparable outputs.
+
+Extra fields, with --full only (each takes GPU or CPU runs of its own):
+roofline (dominant kernel = trace; HIP events on the render stream; its
+counts pass and the shader-clock probe), cpu_baseline (oracle Tier A = the
+reference's algorithm, sequential RNG, one core, on a bounded sample of the same frame), f32_hybrid_variant,
 wavefront_variant (BASELINE configs[3]: the same frame on the wavefront
 engine, bit-identical image, with its HBM roofline), globe_10k_variant
 (configs[4]: globe + 10k spheres through the BVH world kernel) and
@@ -73,7 +83,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-f32-variant", action="store_true")
     ap.add_argument("--cpu-spp", type=int, default=64, help="spp of the bounded CPU sample (~15-25 s on one core)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's frame as DIR/image.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the trace roofline (counts pass, shader-clock "
+                         "probe), the f32, wavefront, globe and Cornell variants and the CPU baseline")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def parse():
@@ -518,6 +536,30 @@ def wavefront_variant(args, R, rend, cam, out, W, H, spp, rb, rs, rc, counts, sa
                     "same Tier-B image as the megakernel, bit for bit"}
 
 
+DUMP_LIMIT_BYTES = 64_000_000 - 1024  # 64 MB for every file together, .npy headers included
+DUMP_SAMPLE_PIXELS = 1 << 21  # 24 MB of float32 rgb + 16 MB of float64 indices
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs: the frame of the last timed step (uint8 rgb as the
+    caller of the timed path receives it: H x W x 3, at N > 1 rank 0's
+    assembled frame) as path/image.npy in float32.  A frame over the limit
+    is written as a fixed seeded sample of its pixels: image.npy holds the
+    sampled pixels' rgb (n x 3), image_index.npy their row-major pixel
+    indices (float64, ascending), the same for every run of the same size."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    img = frame.cpu().numpy().astype(np.float32)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(path, "image.npy"), img)
+        return
+    px = img.reshape(-1, 3)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(path, "image.npy"), px[idx])
+    np.save(os.path.join(path, "image_index.npy"), idx.astype(np.float64))
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -624,6 +666,52 @@ def workload(args, world):
     return args.width, R.image_height(args.width, ASPECT), args.spp * world
 
 
+def trace_roofline(args, R, rend, cam, params, counts, W, rc, spp, world, trace_ms_avg, sclk, clk):
+    """--full: the roofline object of the headline engine from the counts pass
+    (`counts`), the timed launches' HIP-event average and the clock probe."""
+    # Roofline of the dominant kernel (trace): algorithmic flops per launch /
+    # average launch time.  HBM: algorithmic bytes per launch = one f64x3
+    # chunk sum (24 B) per (pixel, chunk) unit written + scene tables read.
+    flops = counts["static_tests"] * FLOP_STATIC + counts["moving_tests"] * FLOP_MOVING
+    achieved_tf = flops / (trace_ms_avg * 1e-3) / 1e12
+    peak = PEAK_FP64_VALU_TF if args.precision == "f64" else PEAK_FP32_VALU_TF
+    chunk = min(R.DEFAULT_CHUNK, spp)
+    n_chunks = (spp + chunk - 1) // chunk
+    hbm_bytes = rc * W * n_chunks * 24
+    hbm_gbs = hbm_bytes / (trace_ms_avg * 1e-3) / 1e9
+    if args.engine == "megakernel":
+        roofline = {
+            "bound": "valu-fp64" if args.precision == "f64" else "valu-fp32",
+            "achieved": round(achieved_tf, 3), "peak": peak, "unit": "TFLOP/s",
+            "frac": round(achieved_tf / peak, 4),
+            "traffic": traffic_per_launch(args, W, rc, spp),
+            "traffic_source": os.path.relpath(evidence("traffic.json"), REPO),
+            "kernel": "trace_kernel", "trace_ms_per_launch": round(trace_ms_avg, 3), "sclk_mhz": sclk,
+            "sclk_window_ms": clk.window_ms if clk is not None else None,
+            "flop_per_launch": flops, "segments_per_launch": counts["segments"],
+            "hbm": {"achieved": round(hbm_gbs, 3), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                    "frac": round(hbm_gbs / PEAK_HBM_GBS, 7), "algorithmic_bytes_per_launch": hbm_bytes},
+            "valu_issue": valu_issue(args, W, rc, spp),
+            "evidence_scope": evidence_scope(world, W, rc, spp),
+            "note": "megakernel is VALU-issue bound (valu_issue.busy_frac: the fraction of SIMD cycles in "
+                    "which the VALU issues; f64, f32 and integer-multiply wave64 instructions each take ~4 cycles) plus "
+                    "divergence; `achieved` counts only the algorithm's sphere-test flops; MFMA n/a (no "
+                    "contraction); HBM traffic is ~24 B per chunk of samples by construction (DESIGN.md §Roofline)",
+        }
+    else:  # wavefront headline: HBM-bound path queues
+        byts = wf_frame_bytes(args, rend.counts(cam, params), rc * W * n_chunks)
+        gbs = byts / (trace_ms_avg * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                    "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": wf_traffic(args, W, rc, spp),
+                    "traffic_source": os.path.relpath(evidence("wf_traffic.json"), REPO),
+                    "evidence_scope": evidence_scope(world, W, rc, spp),
+                    "kernel": wf_kernels(args), "wf_sets": wf_sets(args), "wf_drain": args.wf_drain,
+                    "loop_ms_per_frame": round(trace_ms_avg, 3), "algorithmic_bytes_per_frame": byts,
+                    "valu": {"achieved": round(achieved_tf, 3), "peak": peak, "unit": "TFLOP/s",
+                             "frac": round(achieved_tf / peak, 4)}}
+    return roofline
+
+
 def main():
     args = parse()
     rc = maybe_launch(args, sys.argv[1:])
@@ -668,9 +756,9 @@ def main():
     samples_rank = rc * W * spp
     tg = TileGather(out, H, rank, world)  # send tile + rank 0's receive tiles, allocated once
 
-    # Untimed: counts pass (algorithmic flops of one trace launch) + warmup.
+    # Untimed: counts pass (algorithmic flops of one trace launch; --full: the roofline's) + warmup.
     counts = rend.counts(cam, R.make_params(W, H, spp, DEPTH, SEED, row_begin=rb, row_stride=rs, row_count=rc,
-                                            precision=args.precision))
+                                            precision=args.precision)) if args.full else None
     torch.cuda.synchronize()
 
     def step_warm():
@@ -685,7 +773,7 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    clk = ClockWindow(R, torch, args.steps * warm_ms) if args.warmup > 0 else None
+    clk = ClockWindow(R, torch, args.steps * warm_ms) if args.full and args.warmup > 0 else None
     t0 = time.perf_counter()
     for i in range(args.steps):
         rend.render(cam, params, out=out, timer=timers[i])
@@ -726,6 +814,8 @@ def main():
         dist_info = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                      "samples_per_rank": per_rank, "gather_ms": round(float(gt.item()) * 1e3, 3)}
     dist_info.update(per_rank_t)
+    if args.dump_outputs and rank == 0:  # before any variant below renders into `out` again
+        dump_outputs(args.dump_outputs, frame if world > 1 else out)
     if world == 1:
         samples_all = float(samples_rank)
     trace_ms_avg = roofline_launch_ms(world, trace_ms_avg, per_rank_t)
@@ -733,49 +823,11 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = samples_all * args.steps / elapsed / 1e6
 
-    # Roofline of the dominant kernel (trace): algorithmic flops per launch /
-    # average launch time.  HBM: algorithmic bytes per launch = one f64x3
-    # chunk sum (24 B) per (pixel, chunk) unit written + scene tables read.
-    flops = counts["static_tests"] * FLOP_STATIC + counts["moving_tests"] * FLOP_MOVING
-    achieved_tf = flops / (trace_ms_avg * 1e-3) / 1e12
-    peak = PEAK_FP64_VALU_TF if args.precision == "f64" else PEAK_FP32_VALU_TF
-    chunk = min(R.DEFAULT_CHUNK, spp)
-    n_chunks = (spp + chunk - 1) // chunk
-    hbm_bytes = rc * W * n_chunks * 24
-    hbm_gbs = hbm_bytes / (trace_ms_avg * 1e-3) / 1e9
-    if args.engine == "megakernel":
-        roofline = {
-            "bound": "valu-fp64" if args.precision == "f64" else "valu-fp32",
-            "achieved": round(achieved_tf, 3), "peak": peak, "unit": "TFLOP/s",
-            "frac": round(achieved_tf / peak, 4),
-            "traffic": traffic_per_launch(args, W, rc, spp),
-            "traffic_source": os.path.relpath(evidence("traffic.json"), REPO),
-            "kernel": "trace_kernel", "trace_ms_per_launch": round(trace_ms_avg, 3), "sclk_mhz": sclk,
-            "sclk_window_ms": clk.window_ms if clk is not None else None,
-            "flop_per_launch": flops, "segments_per_launch": counts["segments"],
-            "hbm": {"achieved": round(hbm_gbs, 3), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": round(hbm_gbs / PEAK_HBM_GBS, 7), "algorithmic_bytes_per_launch": hbm_bytes},
-            "valu_issue": valu_issue(args, W, rc, spp),
-            "evidence_scope": evidence_scope(world, W, rc, spp),
-            "note": "megakernel is VALU-issue bound (valu_issue.busy_frac: the fraction of SIMD cycles in "
-                    "which the VALU issues; f64, f32 and integer-multiply wave64 instructions each take ~4 cycles) plus "
-                    "divergence; `achieved` counts only the algorithm's sphere-test flops; MFMA n/a (no "
-                    "contraction); HBM traffic is ~24 B per chunk of samples by construction (DESIGN.md §Roofline)",
-        }
-    else:  # wavefront headline: HBM-bound path queues
-        byts = wf_frame_bytes(args, rend.counts(cam, params), rc * W * n_chunks)
-        gbs = byts / (trace_ms_avg * 1e-3) / 1e9
-        roofline = {"bound": "hbm", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": wf_traffic(args, W, rc, spp),
-                    "traffic_source": os.path.relpath(evidence("wf_traffic.json"), REPO),
-                    "evidence_scope": evidence_scope(world, W, rc, spp),
-                    "kernel": wf_kernels(args), "wf_sets": wf_sets(args), "wf_drain": args.wf_drain,
-                    "loop_ms_per_frame": round(trace_ms_avg, 3), "algorithmic_bytes_per_frame": byts,
-                    "valu": {"achieved": round(achieved_tf, 3), "peak": peak, "unit": "TFLOP/s",
-                             "frac": round(achieved_tf / peak, 4)}}
+    roofline = trace_roofline(args, R, rend, cam, params, counts, W, rc, spp, world, trace_ms_avg, sclk, clk) \
+        if args.full else None
 
     extra = {}
-    if not args.no_f32_variant and args.precision == "f64":
+    if args.full and not args.no_f32_variant and args.precision == "f64":
         p32 = R.make_params(W, H, spp, DEPTH, SEED, row_begin=rb, row_stride=rs, row_count=rc, precision="f32",
                             engine=args.engine, **wf_params(args))
         for _ in range(max(1, args.warmup)):
@@ -801,11 +853,11 @@ def main():
                                        "note": "precision=f32 (f32 + f64 wide spheres + convex self-skip); "
                                                "not the headline: the reference computes in f64"}
 
-    if not args.no_wavefront_variant and args.engine == "megakernel":
+    if args.full and not args.no_wavefront_variant and args.engine == "megakernel":
         extra["wavefront_variant"] = wavefront_variant(args, R, rend, cam, out, W, H, spp, rb, rs, rc, counts,
                                                        samples_all, world, rank, dist, tg, torch)
 
-    if world == 1 and not args.no_world_variants:
+    if args.full and world == 1 and not args.no_world_variants:
         # (at least 10 renders each: one world render varies +-7 % on one box, profiles/r05/world_spread.txt)
         extra["globe_10k_variant"] = world_variant(R, torch, 7, max(10, args.steps // 2), 2)
         extra["cornell_variant"] = world_variant(R, torch, 6, max(10, args.steps // 2), 2)
@@ -830,10 +882,12 @@ def main():
                    "width": W, "height": H, "spp_frame": spp, "max_depth": DEPTH, "seed": SEED,
                    "precision": args.precision, "parallelism": f"rows{world}"},
         "dist": dist_info,
-        "roofline": roofline,
+        "full": args.full,
     }
+    if args.full:
+        res["roofline"] = roofline
     res.update(extra)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(W, H, args.cpu_spp)
     if rank == 0:
         print(json.dumps(res), flush=True)

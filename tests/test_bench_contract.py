@@ -1,5 +1,5 @@
-"""The committed bench line (profiles/<ROUND>/bench.json, written by bench.py on
-an MI355X) keeps the driver's contract: the BASELINE metric and unit, whole-job
+"""The committed bench line (profiles/<ROUND>/bench.json, written by
+`bench.py --full` on an MI355X) keeps the driver's contract: the BASELINE metric and unit, whole-job
 throughput consistent with ms_per_step, the roofline object (bound, achieved,
 peak, unit, frac = achieved / peak, traffic from the PMC passes) with the
 VALU-issue evidence of profiles/<ROUND>/valu_issue.json, the world kernels'

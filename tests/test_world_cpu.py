@@ -17,7 +17,7 @@ import pytest
 
 from conftest import REPO
 
-REF_PNG = "/root/reference/assets/sekaichizu.png"
+REF_PNG_DIGEST = os.path.join(REPO, "tests", "golden", "sekaichizu_png.json")
 
 
 @pytest.fixture(scope="module")
@@ -171,9 +171,14 @@ def test_load_png_reference_asset(W):
     assert (a == 0).any() and (a == 255).any()  # ocean (alpha 0) and land
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PNG), reason="reference tree not present (GPU box)")
 def test_committed_asset_is_the_reference_file(W):
-    assert open(W.EARTH_PNG, "rb").read() == open(REF_PNG, "rb").read()
+    """Byte for byte: the length and SHA-256 recorded from the reference's
+    assets/sekaichizu.png (tests/golden/sekaichizu_png.json)."""
+    import hashlib
+    import json
+    want = json.load(open(REF_PNG_DIGEST))
+    data = open(W.EARTH_PNG, "rb").read()
+    assert len(data) == want["bytes"] and hashlib.sha256(data).hexdigest() == want["sha256"]
 
 
 def test_load_png_roundtrip(W, tmp_path):

@@ -38,7 +38,7 @@ for r in $(seq 1 ${ROUNDS:-3}); do
     E="$(envs_of $L) RTW_LIB_PATH=$P/$L/librtw_hip.so"
     case $ENGINE in
       mk)
-        env $E timeout -k 10 200 python bench.py --steps 5 --warmup 2 --no-wavefront-variant --no-world-variants \
+        env $E timeout -k 10 200 python bench.py --full --steps 5 --warmup 2 --no-wavefront-variant --no-world-variants \
           --no-cpu-baseline > gpurun_out/ab_cur.json 2>> gpurun_out/ab.err || exit 1
         python -c "import json;d=json.load(open('gpurun_out/ab_cur.json'));print('$L round $r', d['value'], \
 d['f32_hybrid_variant']['value'], d['roofline']['trace_ms_per_launch'])" >> $OUT ;;

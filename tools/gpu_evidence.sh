@@ -4,7 +4,8 @@
 #          (gpu_pmc_valu.sh) and HBM traffic (FETCH_SIZE, WRITE_SIZE in separate
 #          passes), wavefront traffic (gpu_pmc_wf.sh), world kernel on the globe
 #          and Cornell (gpu_world_pmc.sh)
-#   bench  the default bench line + rocprofv3 --kernel-trace --stats of the same command
+#   bench  the whole bench line (bench.py --full, into RTW_OUT_DIR, default ./out)
+#          + rocprofv3 --kernel-trace --stats of the same command
 # TAG names the rocprofv3 output directories (default r03).  Every GPU step has
 # its own time limit and the chain stops at the first failure.
 # Replaces round 2's gpu_r02_*.sh / gpu_bench_profile.sh / gpu_round.sh
@@ -29,8 +30,9 @@ for stage in ${STAGES:-tests pmc bench}; do
       bash tools/gpu_pmc_wf.sh &&
       SCENE=7 bash tools/gpu_world_pmc.sh && SCENE=6 bash tools/gpu_world_pmc.sh || exit 1 ;;
     bench)
-      timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err &&
+      O=${RTW_OUT_DIR:-$PWD/out} && mkdir -p "$O" &&
+      timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" &&
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${TAG} -o run \
-        -- python bench.py --no-cpu-baseline > gpurun_out/bench_prof.log 2>&1 || exit 1 ;;
+        -- python bench.py --full --no-cpu-baseline > "$O/bench_prof.log" 2>&1 || exit 1 ;;
   esac
 done

@@ -23,13 +23,14 @@ ev gpurun_out/traffic.json &&
 bash tools/gpu_pmc_wf.sh > /dev/null && ev gpurun_out/wf_traffic.json &&
 python tools/wf_kernel_pmc.py gpurun_out/wf_issue_a gpurun_out/wf_issue_b > gpurun_out/ev/wf_issue.txt &&
 bash tools/gpu_world_pmc_both.sh && ev gpurun_out/world_pmc_7.json && ev gpurun_out/world_pmc_6.json &&
-timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err &&
+O=${RTW_OUT_DIR:-$PWD/out} && mkdir -p "$O" &&  # where the bench lines go (RTW_OUT_DIR, default ./out)
+timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" &&
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${TAG} -o run \
-  -- python bench.py --no-cpu-baseline > gpurun_out/bench_prof.log 2>&1 &&
-timeout -k 10 600 python bench.py --config 2 --steps 3 --warmup 1 --no-cpu-baseline --no-wavefront-variant \
-  --no-world-variants --no-f32-variant > gpurun_out/bench_config2.json 2> gpurun_out/bench_config2.err &&
+  -- python bench.py --full --no-cpu-baseline > "$O/bench_prof.log" 2>&1 &&
+timeout -k 10 600 python bench.py --full --config 2 --steps 3 --warmup 1 --no-cpu-baseline --no-wavefront-variant \
+  --no-world-variants --no-f32-variant > "$O/bench_config2.json" 2> "$O/bench_config2.err" &&
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${TAG}_c2 -o run \
-  -- python bench.py --config 2 --steps 3 --warmup 1 --no-cpu-baseline --no-wavefront-variant --no-world-variants \
-  --no-f32-variant > gpurun_out/bench_config2_prof.log 2>&1 &&
+  -- python bench.py --full --config 2 --steps 3 --warmup 1 --no-cpu-baseline --no-wavefront-variant --no-world-variants \
+  --no-f32-variant > "$O/bench_config2_prof.log" 2>&1 &&
 bash tools/gpu_dist_rehearsal.sh &&
-python -c "import json; d=json.load(open('gpurun_out/bench.json')); print(d['value'], d['wavefront_variant']['value'], d['globe_10k_variant']['value'], d['cornell_variant']['value'], d['cpu_baseline']['value'])"
+python -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['wavefront_variant']['value'], d['globe_10k_variant']['value'], d['cornell_variant']['value'], d['cpu_baseline']['value'])"

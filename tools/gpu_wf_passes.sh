@@ -14,6 +14,6 @@ timeout -k 10 400 python tools/wf_bench.py 4 - RTW_WF_PASSES=2 RTW_WF_PASSES=3 R
   > gpurun_out/wf_passes_ab.txt 2>&1 && cat gpurun_out/wf_passes_ab.txt &&
 unset RTW_LIB_PATH &&
 RTW_DIST_BACKEND=gloo RTW_SHARE_GPU=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 \
-  --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 \
+  --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 10 --warmup 2 \
   --no-cpu-baseline --no-wavefront-variant --no-world-variants --no-f32-variant \
   > gpurun_out/dist_rehearsal10.json 2> gpurun_out/dist_rehearsal10.err && tail -c 600 gpurun_out/dist_rehearsal10.json
