@@ -50,3 +50,322 @@ def deep_cluster_world(W, n=12000, seed=1):
     tex = [dict(kind=W.TEX_SOLID, color=(0.6, 0.5, 0.4))]
     mats = [dict(kind=W.WMAT_LAMBERT, tex=0), dict(kind=W.WMAT_METAL, albedo=(0.8, 0.8, 0.9), fuzz=0.2)]
     return prims, mats, tex
+
+
+def _to_desc(W, prims, xf, tex, mats, perl, imgs):
+    """Plain tables (the dict form oracle.TableWorld takes) -> an
+    rtw_world_desc; `keep` holds the ctypes arrays the desc points into."""
+    import ctypes as C
+    keep = []
+
+    def arr(typ, items, fill):
+        a = (typ * max(1, len(items)))()
+        for i, it in enumerate(items):
+            fill(a[i], it)
+        keep.append(a)
+        return C.cast(a, C.POINTER(typ))
+
+    def f_prim(d, p):
+        d.kind, d.mat, d.xform = p["kind"], p["mat"], p["xform"]
+        d.a[:] = list(p["a"]) + [0.0] * (9 - len(p["a"]))
+
+    def f_xf(d, x):
+        d.n = x["n"]
+        for k in range(x["n"]):
+            d.op[k] = x["op"][k]
+            d.v[k][:] = x["v"][k]
+
+    def f_tex(d, t):
+        d.kind, d.perlin, d.image = t["kind"], t.get("perlin", 0), t.get("image", 0)
+        d.color[:], d.odd[:], d.even[:] = t.get("color", (0, 0, 0)), t.get("odd", (0, 0, 0)), t.get("even", (0, 0, 0))
+        d.scale = t.get("scale", 0.0)
+
+    def f_mat(d, m):
+        d.kind, d.tex = m["kind"], m.get("tex", 0)
+        d.albedo[:] = m.get("albedo", (0, 0, 0))
+        d.fuzz, d.ir = m.get("fuzz", 0.0), m.get("ir", 0.0)
+
+    def f_pl(d, p):
+        for k in range(256):
+            d.ranvec[k][:] = p["ranvec"][k]
+        for a in range(3):
+            d.perm[a][:] = p["perm"][a]
+
+    ims = [np.ascontiguousarray(i, np.uint8) for i in imgs]
+    keep.extend(ims)
+    d = W.WorldDesc()
+    d.prims, d.n_prims = arr(W.Prim, prims, f_prim), len(prims)
+    d.xforms, d.n_xforms = arr(W.Xform, xf, f_xf), len(xf)
+    d.textures, d.n_textures = arr(W.Texture, tex, f_tex), len(tex)
+    d.mats, d.n_mats = arr(W.WMaterial, mats, f_mat), len(mats)
+    d.perlins, d.n_perlins = arr(W.Perlin, perl, f_pl), len(perl)
+    d.images, d.n_images = arr(W.Image, ims, lambda q, im: (setattr(q, "width", im.shape[1]),
+                                                            setattr(q, "height", im.shape[0]),
+                                                            setattr(q, "rgba", im.ctypes.data))), len(ims)
+    return d, keep
+
+
+# ------------------------------------------------- mixed BVH worlds ----
+# Worlds of > 32 primitives that are NOT spheres only, so that rtw_world_create
+# gives rects, boxes, transform chains, lights and coincident primitives a BVH
+# (tests/test_gpu_world_general.py; tests/test_world_cpu.py checks on the oracle
+# alone that every class below is visible, so the GPU tests cannot pass vacuously).
+MIXED_SIZES = {"small": (11, 27), "large": (44, 230)}  # (n_boxes, n_spheres): ~120 / >= 512 primitives
+MIXED_CAMERA = dict(look_from=(0.0, 7.0, 19.0), look_at=(0.0, 1.8, 0.0), vfov=38.0, aperture=0.05, focus=19.0)
+# the classes tests remove one at a time (prim["cls"]); "pair_*" are the coincident pairs
+MIXED_CLASSES = ("free_rect", "xf_box", "own_range", "hollow", "pair_rect", "pair_sphere", "pair_face")
+PAIR_COLOURS = {"pair_rect": ((3.0, 0.15, 0.15), (0.15, 0.15, 3.0)),     # red / blue
+                "pair_sphere": ((2.5, 2.5, 0.1), (0.1, 2.5, 2.5)),     # yellow / cyan
+                "pair_face": ((0.15, 3.0, 0.15), (3.0, 0.15, 3.0))}    # green / magenta
+
+
+def _rot(t):
+    return (float(np.sin(t)), float(np.cos(t)), float(t))
+
+
+def chain_to_object(xf, p):
+    """World point -> object space of a chain (op 0 outermost): the inverse of
+    Translate (p - offset) and RotateY (angle -t), outermost first."""
+    p = np.array(p, float)
+    for k in range(xf["n"]):
+        v = xf["v"][k]
+        if xf["op"][k] == 0:
+            p = p - np.array(v)
+        else:
+            sn, cs = v[0], v[1]
+            p = np.array([cs * p[0] - sn * p[2], p[1], sn * p[0] + cs * p[2]])
+    return p
+
+
+def chain_to_world(xf, p):
+    """Object point -> world (hittable.zig Translate.hit / RotateY.hit), innermost op first."""
+    p = np.array(p, float)
+    for k in reversed(range(xf["n"])):
+        v = xf["v"][k]
+        if xf["op"][k] == 0:
+            p = p + np.array(v)
+        else:
+            sn, cs = v[0], v[1]
+            p = np.array([cs * p[0] + sn * p[2], p[1], -sn * p[0] + cs * p[2]])
+    return p
+
+
+def _box_rects(W, lo, hi, mats6, xform, cls):
+    """Six rects of the box [lo, hi] (hittable.zig Box.init order), consecutive."""
+    (x0, y0, z0), (x1, y1, z1) = lo, hi
+    XY, XZ, YZ = W.PRIM_XY_RECT, W.PRIM_XZ_RECT, W.PRIM_YZ_RECT
+    sides = [(XY, [x0, x1, y0, y1, z1]), (XY, [x0, x1, y0, y1, z0]), (XZ, [x0, x1, z0, z1, y1]),
+             (XZ, [x0, x1, z0, z1, y0]), (YZ, [y0, y1, z0, z1, x1]), (YZ, [y0, y1, z0, z1, x0])]
+    return [dict(kind=k, mat=m, xform=xform, a=a, cls=cls) for (k, a), m in zip(sides, mats6)]
+
+
+def _mixed_tables(W, earth, variant):
+    """Textures, materials and the Perlin table (borrowed from scene 3, as
+    test_gpu_world.custom_world does).  Returns (tex, mats, perlins, images,
+    plain material indices to cycle through, {pair class: (mat A, mat B)})."""
+    tex = [dict(kind=W.TEX_CHECKER, odd=(0.2, 0.3, 0.1), even=(0.9, 0.9, 0.9)),   # 0 ground
+           dict(kind=W.TEX_SOLID, color=(7.0, 6.5, 6.0)),                        # 1 ceiling light
+           dict(kind=W.TEX_SOLID, color=(0.7, 0.3, 0.2)),                        # 2
+           dict(kind=W.TEX_SOLID, color=(0.2, 0.4, 0.7)),                        # 3
+           dict(kind=W.TEX_SOLID, color=(0.8, 0.8, 0.8))]                        # 4
+    mats = [dict(kind=W.WMAT_LAMBERT, tex=0), dict(kind=W.WMAT_LIGHT, tex=1), dict(kind=W.WMAT_LAMBERT, tex=2),
+            dict(kind=W.WMAT_LAMBERT, tex=3), dict(kind=W.WMAT_LAMBERT, tex=4),
+            dict(kind=W.WMAT_METAL, albedo=(0.8, 0.8, 0.9), fuzz=0.0),            # 5
+            dict(kind=W.WMAT_METAL, albedo=(0.8, 0.6, 0.3), fuzz=0.3),            # 6
+            dict(kind=W.WMAT_DIELECTRIC, ir=1.5)]                                 # 7
+    cycle = [2, 3, 4, 5, 6, 7]
+    perl, imgs = [], []
+    if variant in (None, "spheres_image"):
+        tex.append(dict(kind=W.TEX_IMAGE, image=0))
+        mats.append(dict(kind=W.WMAT_LAMBERT, tex=len(tex) - 1))
+        cycle.append(len(mats) - 1)
+        imgs = [earth]
+    if variant is None:
+        scene3 = W.BuiltScene(3, 7)  # (kept alive while its table is copied: desc points into it)
+        pl = scene3.desc.perlins[0]
+        perl =[{"ranvec": [list(pl.ranvec[k]) for k in range(256)], "perm": [list(pl.perm[a]) for a in range(3)]}]
+        tex += [dict(kind=W.TEX_NOISE, perlin=0, scale=4.0), dict(kind=W.TEX_CHECKER, odd=(0.7, 0.2, 0.2), even=(0.9, 0.9, 0.5))]
+        mats += [dict(kind=W.WMAT_LAMBERT, tex=len(tex) - 2), dict(kind=W.WMAT_LAMBERT, tex=len(tex) - 1)]
+        cycle += [len(mats) - 2, len(mats) - 1]
+    pair_mats = {}
+    for name, (ca, cb) in PAIR_COLOURS.items():
+        tex += [dict(kind=W.TEX_SOLID, color=ca), dict(kind=W.TEX_SOLID, color=cb)]
+        mats += [dict(kind=W.WMAT_LIGHT, tex=len(tex) - 2), dict(kind=W.WMAT_LIGHT, tex=len(tex) - 1)]
+        pair_mats[name] = (len(mats) - 2, len(mats) - 1)
+    return tex, mats, perl, imgs, cycle, pair_mats
+
+
+# Box chains (op 0 outermost): every length 1..RTW_MAX_XFORM_OPS, both op
+# orders, one with translations of magnitude >= 1e3 that nearly cancel; None: no chain.
+_T, _R, _B = "T", "R", "B"  # B: the big translation, followed by its near-inverse
+BOX_CHAINS = [[_T], [_R], [_T, _R], [_R, _T], None, [_T, _R, _T], [_R, _T, _R], [_B, _T, _R], [_T, _R, _T, _R],
+              [_R, _T, _R, _T], [_R, _B, _T, _R]]
+
+
+def _make_chain(W, pattern, rng):
+    ops, vs = [], []
+    k = 0
+    while k < len(pattern):
+        c = pattern[k]
+        if c == _R:
+            ops.append(W.XF_ROTATE_Y)
+            vs.append(_rot(rng.uniform(-1.2, 1.2)))
+        elif c == _T:
+            ops.append(W.XF_TRANSLATE)
+            vs.append(tuple(float(x) for x in rng.uniform(-2.0, 2.0, 3)))
+        else:  # _B and the _T after it: +big, then -big + a small rest
+            big = rng.choice([-1.0, 1.0], 3) * rng.uniform(1000.0, 2000.0, 3)
+            ops += [W.XF_TRANSLATE, W.XF_TRANSLATE]
+            vs += [tuple(float(x) for x in big), tuple(float(x) for x in -big + rng.uniform(-1.0, 1.0, 3))]
+            k += 1
+        k += 1
+    return dict(n=len(ops), op=ops, v=vs)
+
+
+def mixed_bvh_world(W, earth, n_boxes, n_spheres, seed, swap=False, drop=(), variant=None):
+    """A deterministic world of every primitive kind, wrapper, material and
+    texture with MORE than 32 primitives, so it is rendered through the BVH:
+    a checker ground sphere (r 1000) under an XZ light; a grid of n_boxes boxes
+    (six consecutive rects each), every box with its own Translate / RotateY
+    chain (BOX_CHAINS: lengths 1-4, both orders, near-cancelling 1e3
+    translations; a few without); free rects of all three kinds with and
+    without chains, one image-textured; n_spheres static spheres; hollow glass
+    (a negative radius inside a positive one); moving spheres over [0, 1] and
+    over their own ranges [-0.5, 1.5] and [0.25, 0.75]; a sphere inside
+    RotateY(Translate(.)); a second sphere of radius >= 100; and three
+    COINCIDENT pairs of lights of different colours (PAIR_COLOURS: two XY rects
+    facing the camera; two spheres; a free rect on the front face of a chained
+    box), one member near the start of the list and one at its end — `swap`
+    exchanges the two members of every pair (their materials: the geometry is
+    identical), so whichever colour sits LATER in the list must be seen
+    (hittable.zig HittableList.hit accepts t == closest_so_far).
+
+    Every primitive dict carries "cls" (MIXED_CLASSES, or "base"); `drop` names
+    classes to leave out (the tables are unchanged, so indices stay valid).
+    variant: None (the full world) or a reduced one, so that every compiled
+    feature set meets a BVH: "rects" (rects only, no chains, no textures beyond
+    solid / checker), "spheres_xform" (spheres and chains), "spheres_image"
+    (spheres with image and solid textures only, with three coincident sphere
+    pairs; the only one the per-lane walk accepts).
+
+    Returns (prims, xforms, textures, mats, perlins, images) in the dict form
+    _to_desc and oracle.TableWorld take.  Camera: MIXED_CAMERA."""
+    rng = np.random.default_rng(seed)
+    tex, mats, perl, imgs, cycle, pair_mats = _mixed_tables(W, earth, variant)
+    S, M, XY, XZ, YZ = W.PRIM_SPHERE, W.PRIM_MOVING_SPHERE, W.PRIM_XY_RECT, W.PRIM_XZ_RECT, W.PRIM_YZ_RECT
+    xf, head, body, tail = [], [], [], []
+    img_mat = next((i for i, m in enumerate(mats) if m["kind"] == W.WMAT_LAMBERT and tex[m["tex"]]["kind"] == W.TEX_IMAGE), 2)
+
+    def pair(name):
+        a, b = pair_mats[name]
+        return (b, a) if swap else (a, b)
+
+    def sph(c, r, mat, cls="base", xform=-1):
+        return dict(kind=S, mat=mat, xform=xform, a=[c[0], c[1], c[2], c[0], c[1], c[2], r, 0, 0], cls=cls)
+
+    def mov(c0, c1, r, t0, t1, mat, cls):
+        return dict(kind=M, mat=mat, xform=-1, a=[*c0, *c1, r, t0, t1], cls=cls)
+
+    def add_xf(x):
+        xf.append(x)
+        return len(xf) - 1
+
+    rects = variant in (None, "rects")
+    spheres = variant != "rects"
+    chains = variant in (None, "spheres_xform")
+    # ---- ground and ceiling light
+    if spheres:
+        head.append(sph((0, -1000, 0), 1000.0, 0))
+    else:
+        head.append(dict(kind=XZ, mat=0, xform=-1, a=[-60, 60, -60, 60, 0.0], cls="base"))
+    if rects:
+        head.append(dict(kind=XZ, mat=1, xform=-1, a=[-5, 5, -4, 4, 14.0], cls="base"))
+    else:
+        head.append(sph((0, 40, 0), 20.0, 1))
+    # ---- coincident pairs: first members near the start of the list, second members at its end
+    if rects:
+        ma, mb = pair("pair_rect")
+        for m, dst in ((ma, head), (mb, tail)):
+            dst.append(dict(kind=XY, mat=m, xform=-1, a=[-9.0, -5.5, 2.6, 5.0, 3.0], cls="pair_rect"))
+    if spheres:
+        ma, mb = pair("pair_sphere")
+        # (the spheres-only variant has no other pair: three of them, since which member a tree
+        # meets first is the builder's business, and a walk that kept the first would pass on one
+        # pair whose later member happens to come first)
+        spots = [((7.0, 4.2, 1.5), 1.3)] + ([((-7.0, 3.6, 1.0), 1.2), ((0.0, 5.6, -2.0), 1.2)] if variant == "spheres_image" else [])
+        for c, r in spots:
+            for m, dst in ((ma, head), (mb, tail)):
+                dst.append(sph(c, r, m, "pair_sphere"))
+    # ---- boxes on a grid (each with its own chain), the face-pair box last
+    n_grid = n_boxes + (1 if rects else 0)
+    if rects and n_grid:
+        cols = int(np.ceil(np.sqrt(n_grid * 2.2)))
+        rows = int(np.ceil(n_grid / cols))
+        size = min(1.5, 15.0 / cols)
+        for i in range(n_grid):
+            cx = -9.0 + 18.0 * ((i % cols) + 0.5) / cols
+            cz = -7.0 + 9.0 * ((i // cols) + 0.5) / rows
+            s = size * rng.uniform(0.75, 1.0)
+            h = s * rng.uniform(0.8, 1.8)
+            face_pair = i == n_grid - 1
+            if face_pair:
+                cx, cz, s, h = 0.5, 5.0, 2.4, 2.4
+            centre = np.array([cx, h / 2 + rng.uniform(0.0, 0.3), cz])
+            pattern = BOX_CHAINS[i % len(BOX_CHAINS)] if chains else None
+            if face_pair and chains:
+                pattern = [_T, _R]
+            if pattern is None:
+                xi, oc = -1, centre
+            else:
+                x = _make_chain(W, pattern, rng)
+                if face_pair:
+                    x["v"][1] = _rot(0.25)  # keep the lit face towards the camera
+                xi, oc = add_xf(x), chain_to_object(x, centre)
+            lo, hi = oc - np.array([s, h, s]) / 2, oc + np.array([s, h, s]) / 2
+            m = cycle[i % len(cycle)]
+            if face_pair:
+                ma, mb = pair("pair_face")
+                # the free rect (near the start) on the box's +z face (at the end, with its box)
+                head.append(dict(kind=XY, mat=ma, xform=xi, a=[lo[0], hi[0], lo[1], hi[1], hi[2]], cls="pair_face"))
+                tail = _box_rects(W, lo, hi, [mb, 4, 4, 4, 4, 4], xi, "pair_face") + tail
+            else:
+                body += _box_rects(W, lo, hi, [m] * 6, xi, "xf_box" if xi >= 0 else "base")
+    # ---- free rects: all three kinds, with and without chains, one image-textured
+    if rects:
+        body.append(dict(kind=XY, mat=img_mat, xform=-1, a=[2.5, 6.5, 0.3, 2.8, -6.0], cls="free_rect"))
+        body.append(dict(kind=YZ, mat=5, xform=-1, a=[0.2, 3.5, -6.0, -1.0, -10.5], cls="free_rect"))
+        body.append(dict(kind=XZ, mat=3, xform=-1, a=[-4.0, -1.0, 3.5, 6.0, 0.6], cls="free_rect"))
+        if chains:
+            for kind, a, pattern, m in ((XY, [-1.5, 1.5, -1.0, 1.0], [_R, _T], 6),
+                                        (XZ, [-1.4, 1.4, -1.2, 1.2], [_T, _R, _T], 2),
+                                        (YZ, [-1.0, 1.0, -1.5, 1.5], [_T, _R], img_mat)):
+                x = _make_chain(W, pattern, rng)
+                target = {XY: (-6.5, 1.4, -3.5), XZ: (4.5, 0.9, 4.5), YZ: (9.5, 1.6, -1.0)}[kind]
+                o = chain_to_object(x, target)
+                ax = {XY: (0, 1, 2), XZ: (0, 2, 1), YZ: (1, 2, 0)}[kind]
+                body.append(dict(kind=kind, mat=m, xform=add_xf(x), cls="free_rect",
+                                 a=[o[ax[0]] + a[0], o[ax[0]] + a[1], o[ax[1]] + a[2], o[ax[1]] + a[3], o[ax[2]]]))
+    # ---- spheres
+    if spheres:
+        for i in range(n_spheres):
+            r = float(rng.uniform(0.22, 0.5))
+            c = (float(rng.uniform(-11, 11)), r, float(rng.uniform(-9, 7)))
+            m = cycle[i % len(cycle)]
+            if chains and variant == "spheres_xform" and i % 2:
+                x = _make_chain(W, BOX_CHAINS[i % len(BOX_CHAINS)] or [_R], rng)
+                body.append(sph(chain_to_object(x, c), r, m, "base", add_xf(x)))
+            else:
+                body.append(sph(c, r, m))
+        body.append(sph((-3.0, 2.2, 2.0), 2.2, 7))                       # hollow glass: the shell ...
+        body.append(sph((-3.0, 2.2, 2.0), -1.9, 7, "hollow"))            # ... and its negative inside
+        body.append(sph((-160.0, 60.0, -330.0), 130.0, 6))               # r >= 100 besides the ground
+    if variant in (None, "spheres_xform"):
+        body.append(mov((3.0, 0.6, 1.5), (3.0, 1.2, 1.5), 0.6, 0.0, 1.0, 2, "base"))
+        body.append(mov((-7.0, 0.5, 4.0), (-6.4, 0.5, 4.3), 0.5, 0.0, 1.0, 5, "base"))
+        body.append(mov((3.6, 1.3, 5.5), (4.2, 2.1, 5.5), 1.3, -0.5, 1.5, 3, "own_range"))
+        body.append(mov((-6.5, 1.2, 6.5), (-5.3, 1.2, 7.0), 1.2, 0.25, 0.75, 6, "own_range"))
+        body.append(mov((8.5, 1.1, 5.5), (8.5, 1.9, 5.0), 1.1, -0.5, 1.5, 2, "own_range"))
+        x = dict(n=2, op=[W.XF_ROTATE_Y, W.XF_TRANSLATE], v=[_rot(0.8), (1.0, 0.0, -2.0)])
+        body.append(sph(chain_to_object(x, (-9.5, 0.9, 0.5)), 0.9, 4, "base", add_xf(x)))
+    prims = head + body + tail
+    return [p for p in prims if p["cls"] not in drop], xf, tex, mats, perl, imgs

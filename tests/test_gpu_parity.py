@@ -64,6 +64,31 @@ def test_max_depth_edges(rtw, oracle, cover, depth):
         assert (g == 0).all()  # rayColor(depth 0) is black (main.zig:105-108)
 
 
+SEEDS = [0, 1, 2**32 + 5, 2**64 - 1]  # rtw_params.seed is a uint64: zero, its low and high words, all ones
+_seed_oracle = {}
+
+
+def seed_oracle(oracle, osc, ocam, seed):
+    """Oracle Tier B of the cover scene at 48x27x4 with `seed` (rendered once per seed)."""
+    if seed not in _seed_oracle:
+        _seed_oracle[seed] = oracle.render_tier_b(osc, ocam, 48, 27, 4, seed=seed)[0]
+    return _seed_oracle[seed]
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_cover_scene_seeds(rtw, oracle, cover, seed):
+    """Every other oracle-compared render uses seed 42, which a kernel that
+    dropped the seed's high word would pass: seeds 0, 1, 2^32 + 5 and 2^64 - 1
+    against the oracle's `seed=`, and 2^32 + 5 is not seed 5."""
+    sph, mats, cam, osc, ocam = cover
+    g = gpu_render(rtw, cam, sph, mats, width=48, height=27, spp=4, seed=seed)
+    assert_parity(g, seed_oracle(oracle, osc, ocam, seed), f"megakernel seed {seed}")
+    if seed == 2**32 + 5:
+        low = gpu_render(rtw, cam, sph, mats, width=48, height=27, spp=4, seed=5)
+        assert_parity(low, seed_oracle(oracle, osc, ocam, 5), "megakernel seed 5")
+        assert (g != low).mean() > 0.5  # another stream, not the low word's
+
+
 def test_empty_scene_is_background(rtw, oracle, cover):
     _, _, cam, _, ocam = cover
     g = rtw.render(cam, None, None, rtw.make_params(32, 18, 3))

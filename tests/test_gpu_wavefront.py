@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from helpers import diff_stats, to_oracle_camera, to_oracle_scene
-from test_gpu_parity import ASPECT, assert_parity, clustered_scene, custom_scene, oracle_render
+from test_gpu_parity import ASPECT, SEEDS, assert_parity, clustered_scene, custom_scene, oracle_render, seed_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -118,6 +118,21 @@ def test_wavefront_depth_edges(rtw, oracle, cover, depth):
     assert_parity(wf[0], oracle_render(oracle, osc, ocam, **kw), f"wavefront depth {depth}")
     if depth == 0:
         assert (wf[0] == 0).all()
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_wavefront_seeds(rtw, oracle, cover, seed):
+    """rtw_params.seed is a uint64 (test_gpu_parity.test_cover_scene_seeds):
+    zero, its low and high words and all ones against the oracle's `seed=`."""
+    sph, mats, cam, osc, ocam = cover
+    kw = dict(width=48, height=27, spp=4, seed=seed)
+    mk, wf = both(rtw, cam, sph, mats, wf_paths=256, **kw)
+    assert_identical(mk, wf, f"seed {seed}")
+    assert_parity(wf[0], seed_oracle(oracle, osc, ocam, seed), f"wavefront seed {seed}")
+    if seed == 2**32 + 5:
+        low = rtw.render(cam, sph, mats, rtw.make_params(engine="wavefront", wf_paths=256, **dict(kw, seed=5)))
+        assert_parity(low, seed_oracle(oracle, osc, ocam, 5), "wavefront seed 5")
+        assert (wf[0] != low).mean() > 0.5  # another stream, not the low word's
 
 
 def test_wavefront_empty_scene(rtw, cover):

@@ -1,13 +1,17 @@
 """GPU parity of the general-world kernel (csrc/rtw_world.hip) against the
 oracle's Tier B (oracle/rtw_world.c): every scene of the reference's main.zig
 (1-6), the configs[4] globe + 10k spheres (7), a custom world exercising every
-primitive / wrapper / material / texture, BVH == linear, scene 1 ==
-megakernel, and exactly-once sample counts.  Bar: as test_gpu_parity.py
+primitive / wrapper / material / texture under the LINEAR loop only (its 14
+primitives get no BVH, as scenes 2-6), BVH == linear on the sphere worlds,
+scene 1 == megakernel, and exactly-once sample counts.  The BVH counterpart
+— rects, boxes, transform chains, lights and coincident primitives in worlds
+of > 32 primitives, and the kernel's parameter edges — is
+test_gpu_world_general.py.  Bar: as test_gpu_parity.py
 (every channel within 1 LSB, >= 99.99 % bit-identical; observed: identical)."""
 import numpy as np
 import pytest
 
-from helpers import diff_stats
+from helpers import _to_desc, diff_stats
 from test_gpu_parity import assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -324,57 +328,6 @@ def custom_world(W, earth):
     prims += [dict(kind=k, mat=6, xform=0, a=a) for k, a in box]
     pv = {"ranvec": [list(perlin.ranvec[k]) for k in range(256)], "perm": [list(perlin.perm[a]) for a in range(3)]}
     return prims, xf, tex, mats, [pv], [earth]
-
-
-def _to_desc(W, prims, xf, tex, mats, perl, imgs):
-    import ctypes as C
-    keep = []
-
-    def arr(typ, items, fill):
-        a = (typ * max(1, len(items)))()
-        for i, it in enumerate(items):
-            fill(a[i], it)
-        keep.append(a)
-        return C.cast(a, C.POINTER(typ))
-
-    def f_prim(d, p):
-        d.kind, d.mat, d.xform = p["kind"], p["mat"], p["xform"]
-        d.a[:] = list(p["a"]) + [0.0] * (9 - len(p["a"]))
-
-    def f_xf(d, x):
-        d.n = x["n"]
-        for k in range(x["n"]):
-            d.op[k] = x["op"][k]
-            d.v[k][:] = x["v"][k]
-
-    def f_tex(d, t):
-        d.kind, d.perlin, d.image = t["kind"], t.get("perlin", 0), t.get("image", 0)
-        d.color[:], d.odd[:], d.even[:] = t.get("color", (0, 0, 0)), t.get("odd", (0, 0, 0)), t.get("even", (0, 0, 0))
-        d.scale = t.get("scale", 0.0)
-
-    def f_mat(d, m):
-        d.kind, d.tex = m["kind"], m.get("tex", 0)
-        d.albedo[:] = m.get("albedo", (0, 0, 0))
-        d.fuzz, d.ir = m.get("fuzz", 0.0), m.get("ir", 0.0)
-
-    def f_pl(d, p):
-        for k in range(256):
-            d.ranvec[k][:] = p["ranvec"][k]
-        for a in range(3):
-            d.perm[a][:] = p["perm"][a]
-
-    ims = [np.ascontiguousarray(i, np.uint8) for i in imgs]
-    keep.extend(ims)
-    d = W.WorldDesc()
-    d.prims, d.n_prims = arr(W.Prim, prims, f_prim), len(prims)
-    d.xforms, d.n_xforms = arr(W.Xform, xf, f_xf), len(xf)
-    d.textures, d.n_textures = arr(W.Texture, tex, f_tex), len(tex)
-    d.mats, d.n_mats = arr(W.WMaterial, mats, f_mat), len(mats)
-    d.perlins, d.n_perlins = arr(W.Perlin, perl, f_pl), len(perl)
-    d.images, d.n_images = arr(W.Image, ims, lambda q, im: (setattr(q, "width", im.shape[1]),
-                                                            setattr(q, "height", im.shape[0]),
-                                                            setattr(q, "rgba", im.ctypes.data))), len(ims)
-    return d, keep
 
 
 @pytest.mark.parametrize("bg", [(0.7, 0.8, 1.0), (0.0, 0.0, 0.0)])

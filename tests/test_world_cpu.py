@@ -3,8 +3,12 @@ main.zig:123-290) against the oracle's (rtw_world.c); the Tier-B libm
 (product csrc/rtw_libm.hpp vs oracle ro_libm.h, bit for bit, and vs glibc);
 Lemire intRangeLessThan and Perlin noise against independent Python
 restatements; the PNG decoder; the world C-ABI validation (no GPU needed);
-and Tier C consistency of the oracle's forward emission (Tier B) with the
-reference's recursive rayColor (Tier A) on the emissive scenes."""
+Tier C consistency of the oracle's forward emission (Tier B) with the
+reference's recursive rayColor (Tier A) on the emissive scenes; and the
+inputs of tests/test_gpu_world_general.py on the oracle alone — every class of
+helpers.mixed_bvh_world is visible, the later of two coincident primitives is
+the one seen, the BVHs have the leaf sizes those tests mean to walk — with
+prim_box (csrc/rtw_world_box.hpp) against a long double restatement."""
 import ctypes as C
 import math
 import os
@@ -371,3 +375,214 @@ def test_deep_sphere_world_bvh_capped_for_the_lane_walk():
     assert nodes >= 10000 and free_depth > 16 and depth <= 16 and leaf == 1, line[0]
     packed = [l for l in p.stderr.splitlines() if l.startswith("[rtw bvh] packed refs:")]
     assert len(packed) == 1 and " 0 mismatches" in packed[0], p.stderr
+
+
+# ------------------------------------------------------------------------
+# The mixed BVH worlds of tests/test_gpu_world_general.py, on the oracle alone
+# (helpers.mixed_bvh_world): conditions on the INPUTS of the GPU tests, so that
+# those cannot pass vacuously, and prim_box against an independent restatement.
+def _mixed_oracle_camera(oracle, aspect=16 / 9, time0=0.0, time1=1.0):
+    from helpers import MIXED_CAMERA as m
+    cam = oracle.Camera()
+    arr = C.c_double * 3
+    oracle.lib().ro_camera_init(C.byref(cam), arr(*m["look_from"]), arr(*m["look_at"]), arr(0, 1, 0), m["vfov"],
+                                aspect, m["aperture"], m["focus"], time0, time1)
+    return cam
+
+
+MIXED_BG = (0.7, 0.8, 1.0)
+MIXED_SEED = 5  # the generator's seed in every test
+
+
+@pytest.fixture(scope="module")
+def mixed_renders(W, oracle, earth):
+    """Oracle Tier B at 96x54x4 of the full mixed world, per size and pair order; rendered once."""
+    from helpers import MIXED_SIZES, mixed_bvh_world
+    cache = {}
+
+    def get(size, swap=False, drop=()):
+        key = (size, swap, tuple(drop))
+        if key not in cache:
+            t = mixed_bvh_world(W, earth, *MIXED_SIZES[size], MIXED_SEED, swap=swap, drop=drop)
+            o = oracle.TableWorld(*t, background=MIXED_BG)
+            cache[key] = (o.render_tier_b(_mixed_oracle_camera(oracle), 96, 54, 4, bg=MIXED_BG, threads=8)[0], t, o)
+        return cache[key]
+    return get
+
+
+@pytest.mark.parametrize("size", ["small", "large"])
+def test_mixed_world_every_class_is_visible(mixed_renders, size):
+    """Removing any one class of the mixed world — free rects, transformed
+    boxes, moving spheres with their own time range, the hollow sphere's
+    negative inside, each coincident pair — changes >= 2 % of the pixels of the
+    oracle's 96x54x4 frame (a condition on the generator's layout and camera,
+    not a measurement: observed 4-22 %).  Tier B draws per-sample streams, so
+    a pixel no path of which meets the class is unchanged."""
+    from helpers import MIXED_CLASSES
+    full, t, _ = mixed_renders(size)
+    n = len(t[0])
+    assert n >= 512 if size == "large" else 100 <= n <= 140, n
+    assert full.std() > 5
+    for cls in MIXED_CLASSES:
+        assert any(p["cls"] == cls for p in t[0]), cls
+        img, td, _ = mixed_renders(size, drop=(cls,))
+        assert len(td[0]) < n
+        frac = float((img != full).any(axis=2).mean())
+        print(size, cls, "removed:", n - len(td[0]), "primitives, changed pixels", frac)
+        assert frac >= 0.02, (size, cls, frac)
+
+
+def test_mixed_world_contents(W, earth):
+    """What the generator promises (helpers.mixed_bvh_world): chains of every
+    length 1..4 in both op orders, one with near-cancelling translations of
+    magnitude >= 1e3, boxes of six consecutive rects, every primitive kind,
+    material and texture, and the pair members far apart in the list."""
+    from helpers import MIXED_SIZES, PAIR_COLOURS, mixed_bvh_world
+    for size in ("small", "large"):
+        prims, xf, tex, mats, perl, imgs = mixed_bvh_world(W, earth, *MIXED_SIZES[size], MIXED_SEED)
+        assert prims == mixed_bvh_world(W, earth, *MIXED_SIZES[size], MIXED_SEED)[0]  # deterministic
+        box_chains = {p["xform"] for p in prims if p["cls"] == "xf_box"}
+        assert {xf[i]["n"] for i in box_chains} == {1, 2, 3, 4}
+        firsts = {(xf[i]["op"][0], xf[i]["op"][1]) for i in box_chains if xf[i]["n"] >= 2}
+        assert (W.XF_TRANSLATE, W.XF_ROTATE_Y) in firsts and (W.XF_ROTATE_Y, W.XF_TRANSLATE) in firsts
+        big = [x for x in xf for k in range(x["n"] - 1) if x["op"][k] == x["op"][k + 1] == W.XF_TRANSLATE and
+               min(abs(c) for c in x["v"][k]) >= 1e3 and max(abs(a + b) for a, b in zip(x["v"][k], x["v"][k + 1])) <= 1.0]
+        assert big
+        assert any(p["cls"] == "base" and p["kind"] >= W.PRIM_XY_RECT and p["xform"] < 0 for p in prims[2:])  # chainless boxes
+        assert {p["kind"] for p in prims} == {0, 1, 2, 3, 4}
+        assert {p["kind"] for p in prims if p["cls"] == "free_rect" and p["xform"] < 0} == {2, 3, 4}
+        assert {p["kind"] for p in prims if p["cls"] == "free_rect" and p["xform"] >= 0} == {2, 3, 4}
+        assert any(p["a"][6] < 0 for p in prims if p["kind"] == 0)
+        assert sum(1 for p in prims if p["kind"] == 0 and abs(p["a"][6]) >= 100) == 2
+        assert {(p["a"][7], p["a"][8]) for p in prims if p["kind"] == 1} == {(0.0, 1.0), (-0.5, 1.5), (0.25, 0.75)}
+        assert any(p["kind"] == 0 and p["xform"] >= 0 and xf[p["xform"]]["op"] == [W.XF_ROTATE_Y, W.XF_TRANSLATE] for p in prims)
+        used = {mats[p["mat"]]["kind"] for p in prims}
+        assert used == {W.WMAT_LAMBERT, W.WMAT_METAL, W.WMAT_DIELECTRIC, W.WMAT_LIGHT}
+        assert {tex[mats[p["mat"]]["tex"]]["kind"] for p in prims if mats[p["mat"]]["kind"] == W.WMAT_LAMBERT} == {0, 1, 2, 3}
+        assert {mats[p["mat"]]["fuzz"] > 0 for p in prims if mats[p["mat"]]["kind"] == W.WMAT_METAL} == {False, True}
+        for name in PAIR_COLOURS:
+            idx = [i for i, p in enumerate(prims) if p["cls"] == name and mats[p["mat"]]["kind"] == W.WMAT_LIGHT]
+            assert len(idx) == 2 and idx[0] < 8 and idx[1] >= len(prims) - 8, (name, idx)
+            a, b = prims[idx[0]], prims[idx[1]]
+            assert (a["kind"], a["xform"], a["a"]) == (b["kind"], b["xform"], b["a"])  # identical geometry
+        # boxes: six consecutive rects sharing one chain
+        rects = [i for i, p in enumerate(prims) if p["cls"] == "xf_box"]
+        assert len(rects) % 6 == 0 and all(prims[rects[k]]["xform"] == prims[rects[k - k % 6]]["xform"] and
+                                           rects[k] == rects[k - k % 6] + k % 6 for k in range(len(rects)))
+
+
+def test_mixed_world_bvh_shapes():
+    """The BVHs rtw_world_create builds for the mixed worlds (the builder runs
+    before the device is needed): ~120 primitives get leaves of up to 2; the
+    >= 512 world gets leaves of 1, and its unconstrained SAH tree is deeper
+    than the per-lane stack (17 > 16), so the depth-capped rebuild runs on a
+    world that is not spheres only; every ref packs."""
+    import sys
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "from rtw_amd import world as W\n"
+            "from helpers import MIXED_SIZES, _to_desc, mixed_bvh_world\n"
+            "for size in ('small', 'large'):\n"
+            "    d, keep = _to_desc(W, *mixed_bvh_world(W, W.earth_map(), *MIXED_SIZES[size], %d))\n"
+            "    try:\n        W.DeviceWorld(d, debug_bvh=True).close()\n    except Exception:\n        pass\n") % (
+        os.path.join(REPO, "raytracinginoneweekend.zig_amd"), os.path.dirname(os.path.abspath(__file__)), MIXED_SEED)
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    lines = [l for l in p.stderr.splitlines() if l.startswith("[rtw bvh]") and "depth" in l]
+    assert len(lines) == 2, p.stderr
+    shape = [tuple(int(x) for x in re.match(
+        r"\[rtw bvh\] (\d+) nodes, depth (\d+) \(unconstrained SAH: (\d+)\), max leaf (\d+)", l).groups()) for l in lines]
+    (n_s, d_s, f_s, leaf_s), (n_l, d_l, f_l, leaf_l) = shape
+    assert leaf_s == 2 and d_s == f_s <= 16 and n_s > 50, lines[0]
+    assert leaf_l == 1 and n_l >= 511 and f_l > 16 >= d_l, lines[1]
+    packed = [l for l in p.stderr.splitlines() if l.startswith("[rtw bvh] packed refs:")]
+    assert len(packed) == 2 and all(" 0 mismatches" in l for l in packed), p.stderr
+
+
+def _light_byte(oracle, colour, spp=4):
+    return [int(oracle.lib().ro_quantize(c * spp, 1.0 / spp)) for c in colour]
+
+
+@pytest.mark.parametrize("size", ["small", "large"])
+def test_mixed_world_tie_rule_later_index_wins(oracle, mixed_renders, size):
+    """Coincident primitives (identical geometry, two lights of different
+    colours, list indices far apart): on t == closest_so_far the reference's
+    sequential HittableList.hit takes the LATER primitive.  In the oracle's
+    frame the pixels that cover each pair show the later member's colour and
+    none shows the earlier one's; with the pair order swapped, the reverse.
+    A ray aimed at each pair reports the later list index."""
+    from helpers import MIXED_CAMERA, PAIR_COLOURS, chain_to_world
+    imgs = {sw: mixed_renders(size, swap=sw) for sw in (False, True)}
+    assert (imgs[False][0] != imgs[True][0]).any()
+    for name, (ca, cb) in PAIR_COLOURS.items():
+        ba, bb = _light_byte(oracle, ca), _light_byte(oracle, cb)
+        assert max(abs(x - y) for x, y in zip(ba, bb)) > 100  # clearly different colours
+        for sw in (False, True):
+            img, t, o = imgs[sw]
+            later, earlier = (ba, bb) if sw else (bb, ba)
+            n_later = int((img == np.array(later, np.uint8)).all(axis=2).sum())
+            n_earlier = int((img == np.array(earlier, np.uint8)).all(axis=2).sum())
+            print(size, name, "swap", sw, "pixels of the later / earlier colour:", n_later, n_earlier)
+            assert n_later >= 30 and n_earlier == 0, (name, sw, n_later, n_earlier)
+            other = imgs[not sw][0]
+            mask = (img == np.array(later, np.uint8)).all(axis=2)
+            # the same pixels show the other colour in the other order (edge pixels aside: a sample
+            # beside the pair can hide under one colour's clamp and not under the other's)
+            assert (other[mask] == np.array(earlier, np.uint8)).all(axis=1).mean() >= 0.9
+            prims, xf = t[0], t[1]
+            idx = [i for i, p in enumerate(prims) if p["cls"] == name and o.w.mats[p["mat"]].kind == 3]
+            p = prims[idx[1]]
+            a = p["a"]
+            if p["kind"] == 0:
+                target = np.array(a[:3]) + np.array([0.0, 0.0, abs(a[6])])
+            else:
+                target = np.array([(a[0] + a[1]) / 2, (a[2] + a[3]) / 2, a[4]])
+            if p["xform"] >= 0:
+                target = chain_to_world(xf[p["xform"]], target)
+            org = np.array(MIXED_CAMERA["look_from"])
+            h = o.hit(tuple(org), tuple(target - org))
+            assert h is not None and h["prim"] == idx[1], (name, sw, h, idx)
+            assert abs(h["t"] - 1.0) < 1e-9
+
+
+def test_prim_box_is_conservative(tmp_path):
+    """csrc/rtw_world_box.hpp prim_box (the BVH builder's input): 1e5 random
+    primitives of every kind with chains of 0-4 ops — moving spheres with their
+    own time ranges, one radius in ten negative — and 12 surface points each at
+    shutter times in [0, 1], carried to world space in long double by a
+    restatement of hittable.zig's forward transforms: every point lies inside
+    its box within 1e-12 * (1 + max |coordinate|), and rects are covered by
+    their +-1e-4 padding (tests/native/prim_box_check.cpp)."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "primboxchk")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(REPO, "include"), "-I",
+                    os.path.join(REPO, "raytracinginoneweekend.zig_amd", "csrc"),
+                    os.path.join(REPO, "tests", "native", "prim_box_check.cpp"), "-o", exe], check=True)
+    for seed in (1, 2):
+        p = subprocess.run([exe, "100000", str(seed)], capture_output=True, text=True)
+        print(p.stdout)
+        m = re.search(r"violations (\d+)/(\d+)", p.stdout)
+        assert m and p.returncode == 0, p.stdout + p.stderr
+        assert int(m.group(1)) == 0 and int(m.group(2)) == 1_200_000
+
+
+def test_prim_box_check_has_teeth(tmp_path):
+    """The same program against two broken copies of the header finds
+    violations: prim_box ignoring the RotateY op, and without the rect padding."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    src = open(os.path.join(REPO, "raytracinginoneweekend.zig_amd", "csrc", "rtw_world_box.hpp")).read()
+    rot = "      } else {\n        const double sn = xf->v[i][0]"
+    pad_lo, pad_hi = "p.a[4] - 0.0001", "p.a[4] + 0.0001"
+    assert src.count(rot) == 1 and src.count(pad_lo) == 1 and src.count(pad_hi) == 1
+    broken = {"norot": src.replace(rot, rot.replace("} else {", "} else if (false) {")),
+              "nopad": src.replace(pad_lo, "p.a[4]").replace(pad_hi, "p.a[4]")}
+    for name, text in broken.items():
+        d = tmp_path / name
+        d.mkdir()
+        (d / "rtw_world_box.hpp").write_text(text)
+        exe = str(d / "chk")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(REPO, "include"), "-I", str(d),
+                        os.path.join(REPO, "tests", "native", "prim_box_check.cpp"), "-o", exe], check=True)
+        p = subprocess.run([exe, "20000", "1"], capture_output=True, text=True)
+        m = re.search(r"violations (\d+)/(\d+)", p.stdout)
+        assert m and int(m.group(1)) > 0 and p.returncode == 1, (name, p.stdout)
