@@ -390,6 +390,83 @@ int rtw_world_render_counts(rtw_world world, const rtw_camera *cam, const rtw_pa
 int rtw_world_render_counts_ex(rtw_world world, const rtw_camera *cam, const rtw_params *params,
                                void *workspace, size_t workspace_bytes, uint64_t counts_out[8]);
 
+/* ============================================= progressive rendering ===
+ * A frame accumulated over sample passes: render some samples, look at the
+ * image, render more, stop on a sample or a noise budget, save the state and
+ * resume it.  The accumulator holds the frame's running f64 pixel sum and a
+ * per-pixel luminance statistic (rows * W * 40 bytes of device memory); a
+ * pass needs the workspace of its own samples only, so device memory no
+ * longer grows with the frame's spp.
+ *
+ * Contract: after passes totalling N samples, the resolved rgb8 and mean are
+ * byte-identical to a one-shot render (rtw_render_device /
+ * rtw_world_render_device) of the same params with spp = N, whenever N is a
+ * multiple of the chunk or equals params->spp — for every engine, precision,
+ * row shard and world.  The chunk is the one-shot's:
+ * min(params->chunk ? params->chunk : RTW_DEFAULT_CHUNK, params->spp).
+ *
+ * Pass rules: pass_spp >= 1; done + pass_spp <= params->spp; pass_spp is a
+ * multiple of the chunk unless the pass is the frame's last
+ * (done + pass_spp == params->spp).  A violation returns RTW_EINVAL, sets the
+ * message and leaves the accumulator untouched.
+ *
+ * Calling conventions: the passes, resolves and noise queries of one
+ * accumulator are issued on one stream, on the accumulator's device.  The
+ * count of samples done is HOST state, advanced when a pass is enqueued, and
+ * a pass's sample range is fixed at that moment: a captured graph of a pass
+ * would replay the SAME samples, so passes are not to be replayed from a
+ * graph.  The wavefront engine's passes cannot be captured at all
+ * (rtw_render_device). */
+typedef struct rtw_accum_s *rtw_accum;
+
+/* An empty accumulator (sums zeroed) on the CURRENT device.  params is copied:
+ * every pass renders with its size, rows, seed, depth, background, precision,
+ * engine and engine knobs; params->spp is the frame's total. */
+int rtw_accum_create(const rtw_params *params, rtw_accum *out);
+int rtw_accum_destroy(rtw_accum a);
+/* Samples accumulated so far (enqueued passes included). */
+int rtw_accum_samples(rtw_accum a, uint32_t *done);
+
+/* Device workspace of a pass of pass_spp samples: rtw_workspace_bytes /
+ * rtw_world_workspace_bytes of params with spp = pass_spp.  0 unless pass_spp
+ * is a multiple of the chunk or equals params->spp.  (A shorter last pass fits
+ * the workspace of the next multiple of the chunk.) */
+size_t rtw_accum_workspace_bytes(const rtw_params *params, uint32_t pass_spp);
+size_t rtw_accum_world_workspace_bytes(rtw_world w, const rtw_params *params, uint32_t pass_spp);
+
+/* One pass: samples [done, done + pass_spp) of every pixel, asynchronous on
+ * `stream` — the render of rtw_render_device / rtw_world_render_device with
+ * spp = pass_spp, started `done` samples into each pixel's random stream,
+ * its chunk sums folded into the accumulator where the one-shot render
+ * launches its finalize kernel.  timer (optional) brackets the trace kernel(s).
+ * A world pass in a workspace of only rtw_accum_workspace_bytes runs without
+ * tail dealing (the same sums). */
+int rtw_accum_render_device(rtw_accum a, rtw_scene scene, const rtw_camera *cam, uint32_t pass_spp,
+                            void *workspace, size_t workspace_bytes, void *stream, rtw_timer timer);
+int rtw_accum_world_render_device(rtw_accum a, rtw_world world, const rtw_camera *cam, uint32_t pass_spp,
+                                  void *workspace, size_t workspace_bytes, void *stream, rtw_timer timer);
+
+/* The image of the samples done so far, asynchronous on `stream`: d_rgb
+ * (W*row_count*3 bytes) and optional d_mean (W*row_count*3 floats) =
+ * sum / done, quantised as the one-shot render does.  RTW_EINVAL before the
+ * first pass. */
+int rtw_accum_resolve_device(rtw_accum a, uint8_t *d_rgb, float *d_mean, void *stream);
+
+/* The frame's noise, synchronous: the RMS over the pixels of the standard
+ * error of the pixel's mean luminance, sqrt(sum_pix se2 / npix) with
+ * se2 = max(0, SY2 - SY*SY/m) / (m*(m-1)*n_c*n_c), where SY and SY2 sum Y and
+ * Y*Y over the m full chunks accumulated, Y = (0.2126 r + 0.7152 g) + 0.0722 b
+ * of a chunk's sum and n_c is the chunk.  Deterministic: the same state gives
+ * the same bits.  RTW_EINVAL with fewer than 2 full chunks. */
+int rtw_accum_noise(rtw_accum a, void *stream, double *noise);
+
+/* Save and resume, HOST buffers, synchronous (they wait for the device):
+ * sum (npix*3) is the running pixel sum, stat (npix*2; optional in _read) the
+ * luminance statistic {SY, SY2}, npix = W*row_count.  rtw_accum_load replaces
+ * the state; samples_done must be a multiple of the chunk or params->spp. */
+int rtw_accum_read(rtw_accum a, double *sum_out, double *stat_out);
+int rtw_accum_load(rtw_accum a, const double *sum, const double *stat, uint32_t samples_done);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,23 @@ struct rtw_sclk_probe_s {
   hipStream_t s = nullptr;
 };
 
+// A frame accumulated over sample passes (rtw_hip.h rtw_accum_*).  One device
+// allocation: sum [npix][3] f64 | stat [npix][2] f64 (npix * 40 B) | the noise
+// reduction's kNoiseGrid + 1 words.
+struct rtw_accum_s {
+  int device = 0;
+  rtw_params p{};      // the frame's params, copied at creation (spp = the total)
+  uint32_t chunk = 0;  // the one-shot's effective chunk for p
+  uint32_t done = 0;   // samples folded: a multiple of chunk, or p.spp (host state, advanced at enqueue)
+  uint32_t npix = 0;
+  double *sum = nullptr, *stat = nullptr, *noise = nullptr;
+};
+
+// ---- shared by the one-shot and the pass paths, here and in rtw_world_capi.hip ----
+int rtw_launch_finalize(const rtw_params* p, unsigned char* ws, uint8_t* d_rgb, float* d_mean, hipStream_t s);
+int rtw_accum_pass_begin(rtw_accum a, uint32_t pass_spp, rtw_params* pp, uint64_t* seed_adv);
+int rtw_accum_pass_fold(rtw_accum a, const rtw_params* pp, unsigned char* ws, hipStream_t s);
+
 namespace {
 // One wave: spin (s_sleep between reads) until `ticks` of the constant-rate
 // s_memrealtime counter passed; the SIMD clock = delta(s_memtime) /
@@ -602,7 +619,7 @@ constexpr uint32_t kWorldUnitOrder = 1u;
 
 template <typename R>
 void fill_args(rtwk::TraceArgs<R>& a, const rtwk::SceneView<R>& v, const rtw_camera* cam, const rtw_params* p,
-               unsigned char* ws, const WsLayout& L) {
+               unsigned char* ws, const WsLayout& L, uint64_t seed_adv) {
   std::memset(&a, 0, sizeof(a));
   a.sc = v;
   for (int k = 0; k < 3; ++k) {
@@ -638,7 +655,9 @@ void fill_args(rtwk::TraceArgs<R>& a, const rtwk::SceneView<R>& v, const rtw_cam
   a.total_units = a.tiles_x * tiles_y * 64u * a.n_chunks;
   const rtwm::UDivMagic mu = rtwm::udiv_magic(rtwk::kTileW * rtwk::kTileH * a.n_chunks), mt = rtwm::udiv_magic(a.tiles_x);
   a.upt_m = mu.m, a.upt_sh = mu.sh, a.tx_m = mt.m, a.tx_sh = mt.sh;
-  a.seed_base = splitmix_first(p->seed);
+  // seed_adv: 0 for a frame; an accumulator pass starts at sample s0 of its
+  // pixels' streams, s0 * (gamma << 16) further on (accum_pass_begin).
+  a.seed_base = splitmix_first(p->seed) + seed_adv;
   // Unit dealing order (rtw_device.hpp dealt_unit): image order, top rows
   // first, for the cover-scene engines, last-first for the world kernel
   // (rtw_fill_trace_args), each the faster in the in-process A/Bs
@@ -1026,8 +1045,13 @@ int run_wavefront(const rtwk::TraceArgs<R>& ta, const rtw_params* p, unsigned ch
   return st;
 }
 
+// acc: the render is a pass of this accumulator (p->spp = the pass's samples,
+// seed_adv = its offset into the pixels' sample streams): the fold takes the
+// place of the finalize launch, ordered as that launch is — on `stream`,
+// which the wavefront engine's queue sets have joined by then.
 int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* workspace, size_t ws_bytes,
-               uint8_t* d_rgb, float* d_mean, hipStream_t stream, rtw_timer timer, int mode) {
+               uint8_t* d_rgb, float* d_mean, hipStream_t stream, rtw_timer timer, int mode,
+               uint64_t seed_adv = 0, rtw_accum acc = nullptr) {
   const WsLayout L = ws_layout(p);
   if (!workspace || ws_bytes < L.total)
     return fail(RTW_EINVAL, "workspace %zu bytes < required %zu", ws_bytes, L.total);
@@ -1064,12 +1088,12 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
     int st;
     if (p->precision == RTW_PRECISION_F32) {
       rtwk::TraceArgs<float> a;
-      fill_args(a, sc->v32, cam, p, ws, L);
+      fill_args(a, sc->v32, cam, p, ws, L, seed_adv);
       a.sc.n_clusters = 0u;  // f32: no clustered pretest
       st = run_wavefront<float>(a, p, ws, L, dev, lds, stream, mode == 1);
     } else {
       rtwk::TraceArgs<double> a;
-      fill_args(a, sc->v64, cam, p, ws, L);
+      fill_args(a, sc->v64, cam, p, ws, L, seed_adv);
       a.sc.cluster_on = cl_on;  // (0 unless the bounce kernels were built with the clustered pretest)
       if (!cl_on) a.sc.n_clusters = 0u;
       st = run_wavefront<double>(a, p, ws, L, dev, lds, stream, mode == 1);
@@ -1078,7 +1102,7 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
     e = hipSuccess;
   } else if (p->precision == RTW_PRECISION_F32) {
     rtwk::TraceArgs<float> a;
-    fill_args(a, sc->v32, cam, p, ws, L);
+    fill_args(a, sc->v32, cam, p, ws, L, seed_adv);
     a.sc.n_clusters = 0u;  // f32: no clustered pretest
     total_units = a.total_units;
     const uint32_t want = (total_units + 255) / 256;
@@ -1086,7 +1110,7 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
     e = rtwk::launch_trace_f32(a, grid, lds, stream, mode, var);
   } else {
     rtwk::TraceArgs<double> a;
-    fill_args(a, sc->v64, cam, p, ws, L);
+    fill_args(a, sc->v64, cam, p, ws, L, seed_adv);
     a.sc.cluster_on = cl_on;
     if (!cl_on) a.sc.n_clusters = 0u;  // nothing to stage (lds_bytes above)
     total_units = a.total_units;
@@ -1099,17 +1123,8 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
     HIP_TRY(hipEventRecord(timer->stop, stream));
     timer->recorded = true;
   }
-  if (d_rgb) {
-    rtwk::FinalizeArgs f;
-    f.partial = reinterpret_cast<const double*>(ws + L.partial_off);
-    f.rgb = d_rgb;
-    f.mean = d_mean;
-    f.npix = p->row_count * p->width;
-    f.n_chunks = n_chunks(p);
-    f.scale = 1.0 / (double)p->spp;
-    e = rtwk::launch_finalize(f, stream);
-    if (e != hipSuccess) return fail(RTW_EHIP, "finalize kernel launch: %s", hipGetErrorString(e));
-  }
+  if (acc) return rtw_accum_pass_fold(acc, p, ws, stream);
+  if (d_rgb) return rtw_launch_finalize(p, ws, d_rgb, d_mean, stream);
   return RTW_OK;
 }
 
@@ -1337,8 +1352,9 @@ uint32_t rtw_total_units(const rtw_params* p) {
   const uint32_t tiles_y = (p->row_count + rtwk::kTileH - 1) / rtwk::kTileH;
   return tiles_x * tiles_y * 64u * n_chunks(p);  // = TraceArgs::total_units (fill_args)
 }
-void rtw_fill_trace_args(rtwk::TraceArgs<double>& a, const rtw_camera* cam, const rtw_params* p, unsigned char* ws) {
-  fill_args(a, rtwk::SceneView<double>{}, cam, p, ws, ws_layout(p));
+void rtw_fill_trace_args(rtwk::TraceArgs<double>& a, const rtw_camera* cam, const rtw_params* p, unsigned char* ws,
+                         uint64_t seed_adv) {
+  fill_args(a, rtwk::SceneView<double>{}, cam, p, ws, ws_layout(p), seed_adv);
   a.unit_order = unit_order(kWorldUnitOrder);  // the world kernel's default (fill_args)
 }
 int rtw_launch_finalize(const rtw_params* p, unsigned char* ws, uint8_t* d_rgb, float* d_mean, hipStream_t s) {
@@ -1359,3 +1375,199 @@ int rtw_timer_mark(rtw_timer t, hipStream_t s, bool start) {
   if (!start) t->recorded = true;
   return RTW_OK;
 }
+
+// ------------------------------------------------------------ accumulator ----
+// Progressive rendering (rtw_hip.h rtw_accum_*).  A pass over
+// samples [done, done + n) is the one-shot render of params with spp = n whose
+// seed_base is advanced by done * (gamma << 16): sample s of a pixel starts at
+// seed_base + (pixel << 40) * gamma + s * (gamma << 16) mod 2^64
+// (rtw_device.hpp start_sample_uv), so the pass's sample j is the frame's
+// sample done + j.  validate() keeps spp <= 2^24, where the kernel's
+// `| s` is that addition.
+namespace {
+constexpr uint64_t kSeedGamma = 0x9e3779b97f4a7c15ULL;  // rtw_device.hpp kGamma
+
+// The params of a pass of n samples of the frame `p`, for sizing: n a multiple
+// of the frame's chunk, or the whole frame.
+bool accum_size_params(const rtw_params* p, uint32_t n, rtw_params* pp) {
+  if (validate(p) != RTW_OK) return false;
+  const uint32_t c = eff_chunk(p);
+  if (n == 0 || n > p->spp || (n % c != 0 && n != p->spp)) {
+    fail(RTW_EINVAL, "pass of %u samples: not a multiple of the chunk %u nor the frame's %u", n, c, p->spp);
+    return false;
+  }
+  *pp = *p;
+  pp->spp = n;
+  return true;
+}
+int accum_current(rtw_accum a, const char* who) {
+  if (!a) return fail(RTW_EINVAL, "%s: accumulator is NULL", who);
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != a->device)
+    return fail(RTW_EINVAL, "%s: accumulator lives on device %d but the current device is %d", who, a->device, dev);
+  return RTW_OK;
+}
+}  // namespace
+
+bool rtw_accum_size_params(const rtw_params* p, uint32_t n, rtw_params* pp) { return accum_size_params(p, n, pp); }
+
+// Checks a pass of pass_spp samples against the accumulator's state; *pp = its
+// render params, *seed_adv = its offset into the sample streams.  Changes
+// nothing.
+int rtw_accum_pass_begin(rtw_accum a, uint32_t pass_spp, rtw_params* pp, uint64_t* seed_adv) {
+  const int st = accum_current(a, "accumulator pass");
+  if (st != RTW_OK) return st;
+  if (pass_spp == 0) return fail(RTW_EINVAL, "pass_spp must be >= 1");
+  if (pass_spp > a->p.spp - a->done)
+    return fail(RTW_EINVAL, "pass of %u samples after %u exceeds the frame's %u", pass_spp, a->done, a->p.spp);
+  if (pass_spp % a->chunk != 0 && a->done + pass_spp != a->p.spp)
+    return fail(RTW_EINVAL, "pass of %u samples after %u: not a multiple of the chunk %u and not the frame's last",
+                pass_spp, a->done, a->chunk);
+  *pp = a->p;
+  pp->spp = pass_spp;
+  *seed_adv = (uint64_t)a->done * (kSeedGamma << 16);
+  return RTW_OK;
+}
+
+// The fold of a rendered pass (its chunk sums are in ws), enqueued on s; the
+// accumulator's sample count advances here, at enqueue time.
+int rtw_accum_pass_fold(rtw_accum a, const rtw_params* pp, unsigned char* ws, hipStream_t s) {
+  rtwk::FoldArgs f;
+  f.partial = reinterpret_cast<const double*>(ws + ws_layout(pp).partial_off);
+  f.sum = a->sum;
+  f.stat = a->stat;
+  f.npix = a->npix;
+  f.n_chunks = n_chunks(pp);
+  f.n_full = pp->spp / a->chunk;  // (a last chunk of fewer samples: into the sum only)
+  const hipError_t e = rtwk::launch_accum_fold(f, s);
+  if (e != hipSuccess) return fail(RTW_EHIP, "fold kernel launch: %s", hipGetErrorString(e));
+  a->done += pp->spp;
+  return RTW_OK;
+}
+
+extern "C" {
+
+int rtw_accum_create(const rtw_params* p, rtw_accum* out) {
+  if (!out) return fail(RTW_EINVAL, "rtw_accum_create: out is NULL");
+  *out = nullptr;
+  const int v = validate(p);
+  if (v != RTW_OK) return v;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  auto* a = new rtw_accum_s;
+  a->device = dev;
+  a->p = *p;
+  a->chunk = eff_chunk(p);
+  a->npix = p->row_count * p->width;
+  // sub-buffers 256-B aligned (the kernels read stat as double2)
+  const size_t sum_b = al256((size_t)a->npix * 24), stat_b = al256((size_t)a->npix * 16);
+  const size_t bytes = sum_b + stat_b + (rtwk::kNoiseGrid + 1) * sizeof(double);
+  void* d = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess) {
+    delete a;
+    return fail(RTW_ENOMEM, "rtw_accum_create: hipMalloc(%zu)", bytes);
+  }
+  if (hipMemset(d, 0, bytes) != hipSuccess) {
+    (void)hipFree(d);
+    delete a;
+    return fail(RTW_EHIP, "rtw_accum_create: hipMemset failed");
+  }
+  a->sum = static_cast<double*>(d);
+  a->stat = a->sum + sum_b / sizeof(double);
+  a->noise = a->stat + stat_b / sizeof(double);
+  *out = a;
+  return RTW_OK;
+}
+
+int rtw_accum_destroy(rtw_accum a) {
+  if (!a) return RTW_OK;
+  if (a->sum) (void)hipFree(a->sum);
+  delete a;
+  return RTW_OK;
+}
+
+int rtw_accum_samples(rtw_accum a, uint32_t* done) {
+  if (!a || !done) return fail(RTW_EINVAL, "rtw_accum_samples: accumulator/done is NULL");
+  *done = a->done;
+  return RTW_OK;
+}
+
+size_t rtw_accum_workspace_bytes(const rtw_params* p, uint32_t pass_spp) {
+  rtw_params pp;
+  if (!accum_size_params(p, pass_spp, &pp)) return 0;
+  return ws_layout(&pp).total;
+}
+
+int rtw_accum_render_device(rtw_accum a, rtw_scene sc, const rtw_camera* cam, uint32_t pass_spp, void* workspace,
+                            size_t ws_bytes, void* stream, rtw_timer timer) {
+  if (!a || !sc || !cam) return fail(RTW_EINVAL, "accumulator/scene/camera is NULL");
+  rtw_params pp;
+  uint64_t adv = 0;
+  const int st = rtw_accum_pass_begin(a, pass_spp, &pp, &adv);
+  if (st != RTW_OK) return st;
+  return launch_all(sc, cam, &pp, workspace, ws_bytes, nullptr, nullptr, static_cast<hipStream_t>(stream), timer, 0,
+                    adv, a);
+}
+
+int rtw_accum_resolve_device(rtw_accum a, uint8_t* d_rgb, float* d_mean, void* stream) {
+  const int st = accum_current(a, "rtw_accum_resolve_device");
+  if (st != RTW_OK) return st;
+  if (!d_rgb) return fail(RTW_EINVAL, "d_rgb is NULL");
+  if (a->done == 0) return fail(RTW_EINVAL, "rtw_accum_resolve_device: no sample accumulated yet");
+  rtwk::ResolveArgs r;
+  r.sum = a->sum;
+  r.rgb = d_rgb;
+  r.mean = d_mean;
+  r.npix = a->npix;
+  r.scale = 1.0 / (double)a->done;
+  const hipError_t e = rtwk::launch_accum_resolve(r, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(RTW_EHIP, "resolve kernel launch: %s", hipGetErrorString(e));
+  return RTW_OK;
+}
+
+int rtw_accum_noise(rtw_accum a, void* stream, double* noise) {
+  const int st = accum_current(a, "rtw_accum_noise");
+  if (st != RTW_OK) return st;
+  if (!noise) return fail(RTW_EINVAL, "noise is NULL");
+  const uint32_t m = a->done / a->chunk;
+  if (m < 2) return fail(RTW_EINVAL, "rtw_accum_noise: %u full chunks accumulated, the estimate needs 2", m);
+  rtwk::NoiseArgs n;
+  n.stat = a->stat;
+  n.part = a->noise;
+  n.npix = a->npix;
+  n.m = (double)m;
+  n.denom = (double)m * (double)(m - 1) * (double)a->chunk * (double)a->chunk;
+  auto s = static_cast<hipStream_t>(stream);
+  const hipError_t e = rtwk::launch_accum_noise(n, s);
+  if (e != hipSuccess) return fail(RTW_EHIP, "noise kernel launch: %s", hipGetErrorString(e));
+  HIP_TRY(hipMemcpyAsync(noise, a->noise + rtwk::kNoiseGrid, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return RTW_OK;
+}
+
+int rtw_accum_read(rtw_accum a, double* sum_out, double* stat_out) {
+  const int st = accum_current(a, "rtw_accum_read");
+  if (st != RTW_OK) return st;
+  if (!sum_out) return fail(RTW_EINVAL, "sum_out is NULL");
+  HIP_TRY(hipDeviceSynchronize());  // every enqueued pass, whichever stream it ran on
+  HIP_TRY(hipMemcpy(sum_out, a->sum, (size_t)a->npix * 24, hipMemcpyDeviceToHost));
+  if (stat_out) HIP_TRY(hipMemcpy(stat_out, a->stat, (size_t)a->npix * 16, hipMemcpyDeviceToHost));
+  return RTW_OK;
+}
+
+int rtw_accum_load(rtw_accum a, const double* sum, const double* stat, uint32_t samples_done) {
+  const int st = accum_current(a, "rtw_accum_load");
+  if (st != RTW_OK) return st;
+  if (!sum || !stat) return fail(RTW_EINVAL, "sum/stat is NULL");
+  if (samples_done > a->p.spp || (samples_done % a->chunk != 0 && samples_done != a->p.spp))
+    return fail(RTW_EINVAL, "rtw_accum_load: %u samples is not a multiple of the chunk %u nor the frame's %u",
+                samples_done, a->chunk, a->p.spp);
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(a->sum, sum, (size_t)a->npix * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(a->stat, stat, (size_t)a->npix * 16, hipMemcpyHostToDevice));
+  a->done = samples_done;
+  return RTW_OK;
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@
 // crosses the C ABI except status codes.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -188,6 +189,24 @@ uint32_t imageHeight(uint32_t width, double aspect_ratio);  // main.zig:306
 // Replaces main.zig:378-402: returns rgb24 (top row first, main.zig:396).
 std::vector<uint8_t> render(const Camera& cam, const Hittable& world, const RenderSettings& s,
                             uint32_t height);
+
+// The render loop in passes (rtw_accum_*, rtw_accum.hip): the frame of `p`
+// accumulated pass_spp samples at a time (a multiple of the chunk, or >= p.spp
+// for one pass) on the current device, through the cover-scene engines
+// (`scene`) or the world kernel (`world`; exactly one of the two is given).
+// After every pass on_pass (optional) sees the image so far; the loop ends
+// with the frame, or earlier once the frame's noise (rtw_accum_noise) is
+// <= max_noise (0: never).  Returns the last image; *samples_used the samples
+// it holds.  Without an early stop the image is the one-shot render's.
+struct PassInfo {
+  uint32_t pass;     // 1, 2, ...
+  uint32_t samples;  // accumulated so far
+  double noise;      // rtw_accum_noise, < 0 while fewer than two full chunks are in
+};
+using PassFn = std::function<void(const PassInfo&, const std::vector<uint8_t>& rgb)>;
+std::vector<uint8_t> renderProgressive(const rtw_camera& cam, const rtw_params& p, uint32_t pass_spp,
+                                       const FlatScene* scene, const rtw_world_desc* world, double max_noise,
+                                       const PassFn& on_pass, uint32_t* samples_used);
 
 void writePPM(const std::string& path, const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h);
 

@@ -148,6 +148,38 @@ constexpr size_t kUnitBaseLdsBytesPerWave = 3 * 64 * 8;
 constexpr int kDefaultVarF32 = RTW_DEFAULT_VAR_F32;
 bool trace_variant_built(int precision, int var);
 constexpr int kTraceBlock = 256;
+
+// ---------------------------------------------------------- accumulator --
+// rtw_accum.hip: progressive rendering (rtw_hip.h rtw_accum_*).  A pass
+// renders its chunk sums into `partial` as a one-shot render does; the fold
+// adds them, chunk by chunk in order, to the frame's running f64 sum — the
+// additions finalize_kernel performs, in its order — and keeps the per-pixel
+// luminance statistic of the full-size chunks for the noise estimate.
+struct FoldArgs {
+  const double* partial;  // [n_chunks][npix][3] chunk sums of the pass
+  double* sum;            // [npix][3] running pixel sum
+  double* stat;           // [npix][2] {sum Y, sum Y^2} over the full chunks, Y = luminance of a chunk sum
+  uint32_t npix, n_chunks;
+  uint32_t n_full;        // the first n_full chunks of the pass hold a full chunk's samples (a short last one: sum only)
+};
+struct ResolveArgs {
+  const double* sum;  // [npix][3]
+  uint8_t* rgb;       // [npix][3]
+  float* mean;        // [npix][3], optional
+  uint32_t npix;
+  double scale;       // 1.0 / samples folded
+};
+constexpr uint32_t kNoiseGrid = 256;  // workgroups of accum_noise_kernel: fixed, so the sum's order never changes
+struct NoiseArgs {
+  const double* stat;  // [npix][2]
+  double* part;        // [kNoiseGrid] per-workgroup sums, then [kNoiseGrid] = the frame's noise
+  uint32_t npix;
+  double m;            // full chunks folded (>= 2)
+  double denom;        // m (m - 1) n_c^2
+};
+hipError_t launch_accum_fold(const FoldArgs& a, hipStream_t s);
+hipError_t launch_accum_resolve(const ResolveArgs& a, hipStream_t s);
+hipError_t launch_accum_noise(const NoiseArgs& a, hipStream_t s);
 // Per-wave LDS slots of coop_reject (rtw_trace.hip CoopSlots: 64 x u64 + 64 x u32).
 constexpr size_t kCoopLdsBytes = (kTraceBlock / 64) * 768;
 

@@ -5,9 +5,15 @@
 //   rtw_render [--scene 1..7] [--width W] [--aspect A|W:H] [--spp N] [--depth D]
 //              [--seed S] [--precision f64|f32] [--engine megakernel|wavefront]
 //              [--chunk C] [--image earth.png] [--out out.ppm]
+//              [--pass-spp N [--preview-dir DIR] [--max-noise X]]
+// --pass-spp N renders the frame progressively, N samples per pass (a multiple
+// of the chunk): the same --out bytes as without it.  --preview-dir DIR writes
+// the image after every pass to DIR/pass_NNNN.ppm; --max-noise X stops once the
+// frame's noise estimate (rtw_accum_noise) is <= X and prints the samples used.
 // Defaults are the reference's: scene 6 (main.zig:313) with that scene's own
 // size, spp, camera and background (main.zig:316-362); --width/--aspect/--spp
 // override them.  Scenes 4 and 7 need --image (assets/sekaichizu.png).
+#include <sys/stat.h>
 #include <zlib.h>
 
 #include <cstdio>
@@ -104,9 +110,10 @@ static std::shared_ptr<rtw::Image> loadPNG(const std::string& path) {
 int main(int argc, char** argv) {
   uint32_t scene = 6;  // main.zig:313
   uint32_t width = 0, spp = 0, depth = 50, chunk = 0, precision = RTW_PRECISION_F64, engine = RTW_ENGINE_MEGAKERNEL;
-  double aspect = 0;
+  uint32_t pass_spp = 0;
+  double aspect = 0, max_noise = 0;
   uint64_t seed = 42;
-  std::string out = "out.ppm", image_path;
+  std::string out = "out.ppm", image_path, preview_dir;
   for (int i = 1; i + 1 < argc; i += 2) {
     const std::string k = argv[i];
     const char* v = argv[i + 1];
@@ -121,10 +128,17 @@ int main(int argc, char** argv) {
     else if (k == "--chunk") chunk = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--image") image_path = v;
     else if (k == "--out") out = v;
+    else if (k == "--pass-spp") pass_spp = (uint32_t)std::strtoul(v, nullptr, 10);
+    else if (k == "--preview-dir") preview_dir = v;
+    else if (k == "--max-noise") max_noise = std::atof(v);
     else {
       std::fprintf(stderr, "unknown option %s\n", k.c_str());
       return 2;
     }
+  }
+  if (pass_spp == 0 && (!preview_dir.empty() || max_noise > 0)) {
+    std::fprintf(stderr, "--preview-dir and --max-noise need --pass-spp\n");
+    return 2;
   }
   try {
     const rtw_scene_settings st = rtw::sceneSettings(scene);  // main.zig:303-362
@@ -137,7 +151,30 @@ int main(int argc, char** argv) {
                                               st.aperture, 10.0, 0, 1);  // main.zig:366-376
     rtw::Random rng = rtw::Random::init(seed);                           // main.zig:300-301
     std::vector<uint8_t> rgb((size_t)W * H * 3);
-    if (scene == 1) {  // the cover scene: the sphere megakernel (or the wavefront engine)
+    uint32_t used = S;
+    // --pass-spp: the frame through the accumulator, a preview per pass
+    auto progressive = [&](const rtw_params& p, const rtw::FlatScene* fs, const rtw_world_desc* wd) {
+      if (!preview_dir.empty()) (void)mkdir(preview_dir.c_str(), 0777);  // (an existing directory is fine)
+      const rtw_camera c = cam.to_c();
+      return rtw::renderProgressive(c, p, pass_spp, fs, wd, max_noise,
+                                    [&](const rtw::PassInfo& i, const std::vector<uint8_t>& img) {
+                                      if (preview_dir.empty()) return;
+                                      char name[32];
+                                      std::snprintf(name, sizeof(name), "/pass_%04u.ppm", i.pass);
+                                      rtw::writePPM(preview_dir + name, img, W, H);
+                                    },
+                                    &used);
+    };
+    rtw_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = W, p.height = H, p.spp = S, p.max_depth = depth, p.seed = seed;
+    for (int k = 0; k < 3; ++k) p.background[k] = st.background[k];
+    p.row_begin = 0, p.row_stride = 1, p.row_count = H, p.chunk = chunk, p.device = -1;
+    if (scene == 1 && pass_spp) {
+      p.precision = precision, p.engine = engine;
+      const rtw::FlatScene fs = rtw::flatten(rtw::generateRandomScene(rng));
+      rgb = progressive(p, &fs, nullptr);
+    } else if (scene == 1) {  // the cover scene: the sphere megakernel (or the wavefront engine)
       rtw::RenderSettings rs;
       rs.width = W, rs.aspect_ratio = asp, rs.samples_per_pixel = S, rs.max_depth = depth, rs.seed = seed;
       rs.precision = precision, rs.chunk = chunk, rs.engine = engine;
@@ -162,18 +199,18 @@ int main(int argc, char** argv) {
       }
       const rtw::FlatWorld fw = rtw::flattenWorld(world);
       const rtw_world_desc desc = fw.desc();
-      rtw_params p;
-      std::memset(&p, 0, sizeof(p));
-      p.width = W, p.height = H, p.spp = S, p.max_depth = depth, p.seed = seed;
-      for (int k = 0; k < 3; ++k) p.background[k] = st.background[k];
-      p.row_begin = 0, p.row_stride = 1, p.row_count = H, p.chunk = chunk, p.precision = RTW_PRECISION_F64;
-      p.device = -1, p.engine = RTW_ENGINE_MEGAKERNEL;
-      const rtw_camera c = cam.to_c();
-      const int rc = rtw_world_render(&c, &desc, &p, rgb.data(), nullptr);  // main.zig:378-402
-      if (rc != RTW_OK) throw rtw::Error(rc, rtw_last_error());
+      p.precision = RTW_PRECISION_F64, p.engine = RTW_ENGINE_MEGAKERNEL;
+      if (pass_spp) {
+        rgb = progressive(p, nullptr, &desc);
+      } else {
+        const rtw_camera c = cam.to_c();
+        const int rc = rtw_world_render(&c, &desc, &p, rgb.data(), nullptr);  // main.zig:378-402
+        if (rc != RTW_OK) throw rtw::Error(rc, rtw_last_error());
+      }
     }
     rtw::writePPM(out, rgb, W, H);  // main.zig:405
-    std::fprintf(stderr, "wrote %s (scene %u, %ux%u, %u spp)\n", out.c_str(), scene, W, H, S);
+    if (max_noise > 0) std::fprintf(stderr, "noise budget %g: %u of %u samples used\n", max_noise, used, S);
+    std::fprintf(stderr, "wrote %s (scene %u, %ux%u, %u spp)\n", out.c_str(), scene, W, H, used);
   } catch (const rtw::Error& e) {
     std::fprintf(stderr, "rtw_render: %s (status %d)\n", e.what(), e.status);
     return 1;

@@ -26,7 +26,12 @@ int rtw_validate_params(const rtw_params* p);
 const char* rtw_dev_knob(const char* name);  // environment, -DRTW_MEASURE builds only
 size_t rtw_ws_total(const rtw_params* p);
 int rtw_device_cus(int dev);
-void rtw_fill_trace_args(rtwk::TraceArgs<double>& a, const rtw_camera* cam, const rtw_params* p, unsigned char* ws);
+void rtw_fill_trace_args(rtwk::TraceArgs<double>& a, const rtw_camera* cam, const rtw_params* p, unsigned char* ws,
+                         uint64_t seed_adv);
+// accumulator passes (rtw_capi.hip)
+bool rtw_accum_size_params(const rtw_params* p, uint32_t n, rtw_params* pp);
+int rtw_accum_pass_begin(rtw_accum a, uint32_t pass_spp, rtw_params* pp, uint64_t* seed_adv);
+int rtw_accum_pass_fold(rtw_accum a, const rtw_params* pp, unsigned char* ws, hipStream_t s);
 int rtw_launch_finalize(const rtw_params* p, unsigned char* ws, uint8_t* d_rgb, float* d_mean, hipStream_t s);
 size_t rtw_ws_stats_off(const rtw_params* p);
 size_t rtw_ws_counter_off(const rtw_params* p);
@@ -716,7 +721,7 @@ WorldLaunchCfg world_cfg(const rtw_world_s* w, const rtw_params* p, int dev) {
 
 int world_launch(rtw_world w, const rtw_camera* cam, const rtw_params* p, void* ws, size_t ws_bytes,
                  uint8_t* d_rgb, float* d_mean, hipStream_t stream, rtw_timer timer, int mode,
-                 uint32_t* tail_ran = nullptr) {
+                 uint32_t* tail_ran = nullptr, uint64_t seed_adv = 0, rtw_accum acc = nullptr) {
   if (!w || !cam) return rtw_fail(RTW_EINVAL, "world/camera is NULL");
   const int v = rtw_validate_params(p);
   if (v != RTW_OK) return v;
@@ -735,7 +740,7 @@ int world_launch(rtw_world w, const rtw_camera* cam, const rtw_params* p, void* 
     return rtw_fail(RTW_EHIP, "workspace reset failed");
   rtwk::WorldArgs a;
   std::memset(&a, 0, sizeof(a));
-  rtw_fill_trace_args(a.t, cam, p, wsb);
+  rtw_fill_trace_args(a.t, cam, p, wsb, seed_adv);
   a.w = w->view;
   a.margin = bvh_margin(w, cam);
   a.counts = reinterpret_cast<unsigned long long*>(wsb + rtw_ws_stats_off(p));
@@ -759,6 +764,7 @@ int world_launch(rtw_world w, const rtw_camera* cam, const rtw_params* p, void* 
   hipError_t e = rtwk::launch_world(a, grid, lds, stream, mode, oi, fs);
   if (e != hipSuccess) return rtw_fail(RTW_EHIP, "world kernel launch: %s", hipGetErrorString(e));
   if (timer && rtw_timer_mark(timer, stream, false) != RTW_OK) return RTW_EHIP;
+  if (acc) return rtw_accum_pass_fold(acc, p, wsb, stream);  // a pass: the fold in the finalize launch's place
   if (d_rgb) return rtw_launch_finalize(p, wsb, d_rgb, d_mean, stream);
   return RTW_OK;
 }
@@ -800,6 +806,23 @@ int rtw_world_render_device(rtw_world w, const rtw_camera* cam, const rtw_params
                             uint8_t* d_rgb, float* d_mean, void* stream, rtw_timer timer) {
   if (!d_rgb) return rtw_fail(RTW_EINVAL, "d_rgb is NULL");
   return world_launch(w, cam, p, ws, ws_bytes, d_rgb, d_mean, static_cast<hipStream_t>(stream), timer, 0);
+}
+
+size_t rtw_accum_world_workspace_bytes(rtw_world w, const rtw_params* p, uint32_t pass_spp) {
+  rtw_params pp;
+  if (!w || !rtw_accum_size_params(p, pass_spp, &pp)) return 0;
+  return rtw_world_workspace_bytes(w, &pp);
+}
+
+int rtw_accum_world_render_device(rtw_accum a, rtw_world w, const rtw_camera* cam, uint32_t pass_spp, void* ws,
+                                  size_t ws_bytes, void* stream, rtw_timer timer) {
+  if (!a || !w || !cam) return rtw_fail(RTW_EINVAL, "accumulator/world/camera is NULL");
+  rtw_params pp;
+  uint64_t adv = 0;
+  const int st = rtw_accum_pass_begin(a, pass_spp, &pp, &adv);
+  if (st != RTW_OK) return st;
+  return world_launch(w, cam, &pp, ws, ws_bytes, nullptr, nullptr, static_cast<hipStream_t>(stream), timer, 0,
+                      nullptr, adv, a);
 }
 
 int rtw_world_render_counts_ex(rtw_world w, const rtw_camera* cam, const rtw_params* p, void* ws, size_t ws_bytes,

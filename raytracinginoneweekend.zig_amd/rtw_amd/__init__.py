@@ -124,6 +124,23 @@ def lib() -> C.CDLL:
                                        C.c_uint64 * 6]
     L.rtw_render_stats.argtypes = [C.c_void_p, P(Camera), P(Params), C.c_void_p, C.c_size_t,
                                    C.c_uint64 * STATS_WORDS]
+    if not hasattr(L, "rtw_accum_create"):  # (A/B timing may load an older build without the accumulator)
+        _lib = L
+        return L
+    # progressive rendering (rtw_accum_*)
+    L.rtw_accum_create.argtypes = [P(Params), P(C.c_void_p)]
+    L.rtw_accum_destroy.argtypes = [C.c_void_p]
+    L.rtw_accum_samples.argtypes = [C.c_void_p, P(C.c_uint32)]
+    L.rtw_accum_workspace_bytes.restype = C.c_size_t
+    L.rtw_accum_workspace_bytes.argtypes = [P(Params), C.c_uint32]
+    L.rtw_accum_world_workspace_bytes.restype = C.c_size_t
+    L.rtw_accum_world_workspace_bytes.argtypes = [C.c_void_p, P(Params), C.c_uint32]
+    for f in (L.rtw_accum_render_device, L.rtw_accum_world_render_device):
+        f.argtypes = [C.c_void_p, C.c_void_p, P(Camera), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.rtw_accum_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtw_accum_noise.argtypes = [C.c_void_p, C.c_void_p, P(C.c_double)]
+    L.rtw_accum_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtw_accum_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     _lib = L
     return L
 
@@ -296,6 +313,90 @@ class DeviceScene:
     def close(self):
         if self.h:
             lib().rtw_scene_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def effective_chunk(params: Params) -> int:
+    """The accumulation chunk a render of `params` uses (rtw_hip.h)."""
+    return min(params.chunk or DEFAULT_CHUNK, params.spp)
+
+
+class Accumulator:
+    """A frame accumulated over sample passes (rtw_accum_*): render some
+    samples, resolve the image, render more; read() / load() save and resume.
+    `target` is a DeviceScene (cover-scene engines) or a world.DeviceWorld.
+    After passes totalling N samples (a multiple of the chunk, or params.spp)
+    the resolved image is the one-shot render's with spp = N, byte for byte.
+    Passes, resolves and noise queries go on one stream."""
+
+    def __init__(self, target, params: Params):
+        self.target = target
+        self.params = params
+        self.is_world = not isinstance(target, DeviceScene)
+        self.chunk = effective_chunk(params)
+        self.npix = params.row_count * params.width
+        self.h = C.c_void_p()
+        _check(lib().rtw_accum_create(C.byref(params), C.byref(self.h)))
+
+    def workspace_bytes(self, pass_spp: int) -> int:
+        """Device workspace of a pass of pass_spp samples.  A last pass shorter
+        than the chunk's next multiple is sized as that multiple."""
+        n = min(max(1, -(-pass_spp // self.chunk)) * self.chunk, self.params.spp)
+        if self.is_world:
+            b = lib().rtw_accum_world_workspace_bytes(self.target.h, C.byref(self.params), n)
+        else:
+            b = lib().rtw_accum_workspace_bytes(C.byref(self.params), n)
+        if b == 0:
+            _check(RTW_EINVAL)
+        return int(b)
+
+    def render_pass(self, cam: Camera, pass_spp: int, workspace_ptr: int, workspace_bytes_: int,
+                    stream: int | None = None, timer: Timer | None = None):
+        """One pass of pass_spp samples, asynchronous on `stream` (a hipStream_t as int)."""
+        f = lib().rtw_accum_world_render_device if self.is_world else lib().rtw_accum_render_device
+        _check(f(self.h, self.target.h, C.byref(cam), pass_spp, C.c_void_p(workspace_ptr), workspace_bytes_,
+                 C.c_void_p(stream) if stream else None, timer.h if timer is not None else None))
+
+    def resolve(self, rgb_ptr: int, mean_ptr: int | None = None, stream: int | None = None):
+        """The image of the samples so far into device buffers (rtw_accum_resolve_device)."""
+        _check(lib().rtw_accum_resolve_device(self.h, C.c_void_p(rgb_ptr), C.c_void_p(mean_ptr) if mean_ptr else None,
+                                              C.c_void_p(stream) if stream else None))
+
+    def samples(self) -> int:
+        n = C.c_uint32()
+        _check(lib().rtw_accum_samples(self.h, C.byref(n)))
+        return int(n.value)
+
+    def noise(self, stream: int | None = None) -> float:
+        """RMS standard error of the pixels' mean luminance (synchronous)."""
+        x = C.c_double()
+        _check(lib().rtw_accum_noise(self.h, C.c_void_p(stream) if stream else None, C.byref(x)))
+        return float(x.value)
+
+    def read(self):
+        """(sum (rows, W, 3) f64, stat (rows, W, 2) f64) on the host (synchronous)."""
+        shape = (self.params.row_count, self.params.width)
+        s, t = np.empty(shape + (3,), np.float64), np.empty(shape + (2,), np.float64)
+        _check(lib().rtw_accum_read(self.h, s.ctypes.data, t.ctypes.data))
+        return s, t
+
+    def load(self, sum_, stat, samples_done: int):
+        """Replace the state with a saved one (rtw_accum_load)."""
+        s = np.ascontiguousarray(sum_, np.float64)
+        t = np.ascontiguousarray(stat, np.float64)
+        if s.size != self.npix * 3 or t.size != self.npix * 2:
+            raise ValueError("sum / stat do not have this accumulator's size")
+        _check(lib().rtw_accum_load(self.h, s.ctypes.data, t.ctypes.data, samples_done))
+
+    def close(self):
+        if self.h:
+            lib().rtw_accum_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
