@@ -17,9 +17,10 @@
 #include <vector>
 
 #include "rtw_hip.h"
-#include "rtw_cull.hpp"
+#include "rtw_capi_shared.hpp"
 #include "rtw_internal.hpp"
 #include "rtw_math.hpp"
+#include "rtw_scene_pack.hpp"
 
 namespace {
 
@@ -113,32 +114,11 @@ struct rtw_scene_s {
   rtwk::SceneView<float> v32{};
 };
 
-struct rtw_timer_s {
-  hipEvent_t start = nullptr, stop = nullptr;
-  bool recorded = false;
-};
-
+// (rtw_timer_s, rtw_accum_s: rtw_capi_shared.hpp)
 struct rtw_sclk_probe_s {
   double* d = nullptr;  // [0] = MHz (device)
   hipStream_t s = nullptr;
 };
-
-// A frame accumulated over sample passes (rtw_hip.h rtw_accum_*).  One device
-// allocation: sum [npix][3] f64 | stat [npix][2] f64 (npix * 40 B) | the noise
-// reduction's kNoiseGrid + 1 words.
-struct rtw_accum_s {
-  int device = 0;
-  rtw_params p{};      // the frame's params, copied at creation (spp = the total)
-  uint32_t chunk = 0;  // the one-shot's effective chunk for p
-  uint32_t done = 0;   // samples folded: a multiple of chunk, or p.spp (host state, advanced at enqueue)
-  uint32_t npix = 0;
-  double *sum = nullptr, *stat = nullptr, *noise = nullptr;
-};
-
-// ---- shared by the one-shot and the pass paths, here and in rtw_world_capi.hip ----
-int rtw_launch_finalize(const rtw_params* p, unsigned char* ws, uint8_t* d_rgb, float* d_mean, hipStream_t s);
-int rtw_accum_pass_begin(rtw_accum a, uint32_t pass_spp, rtw_params* pp, uint64_t* seed_adv);
-int rtw_accum_pass_fold(rtw_accum a, const rtw_params* pp, unsigned char* ws, hipStream_t s);
 
 namespace {
 // One wave: spin (s_sleep between reads) until `ticks` of the constant-rate
@@ -155,6 +135,25 @@ __global__ void __launch_bounds__(64) sclk_probe_kernel(unsigned long long ticks
   }
   const unsigned long long t1 = __builtin_amdgcn_s_memtime();
   if (threadIdx.x == 0) out[0] = (double)(t1 - t0) / (double)(r - r0) * rt_mhz;
+}
+
+// The view of precision R over a packed scene uploaded at `b`.  The clustered
+// pretest is f64 only: there the view carries cmax_all (cluster centres
+// included) when the scene's clusters are usable; cluster_on is then narrowed
+// per render (launch_all).
+template <typename R>
+rtwk::SceneView<R> scene_view(const rtwp::ScenePack& k, const unsigned char* b) {
+  using namespace rtwp;
+  constexpr bool f64 = sizeof(R) == 8;
+  auto P = [&](SceneTable t64, SceneTable t32) { return reinterpret_cast<const R*>(b + k.off[f64 ? t64 : t32]); };
+  auto D = [&](SceneTable t) { return reinterpret_cast<const double*>(b + k.off[t]); };
+  auto F = [&](SceneTable t) { return reinterpret_cast<const float*>(b + k.off[t]); };
+  auto U = [&](SceneTable t) { return reinterpret_cast<const uint32_t*>(b + k.off[t]); };
+  const uint32_t cl_ok = f64 ? k.cluster_ok : 0u;
+  return {P(kSph64, kSph32), P(kRad64, kRad32), U(kMeta), P(kMat64, kMat32), U(kKind), P(kTg64, kTg32), D(kSph64),
+          D(kTg64), U(kPerm), F(kCull), U(kCullTg), F(kTg32), k.n, k.nm, k.ng, k.g_end[0], k.g_end[1], k.g_end[2],
+          k.nn, k.nn_pad, k.n_sn, k.cull_on, cl_ok ? k.cmax_all : k.cmax, k.rho, F(kCcull), U(kCcullTg), F(kCclus),
+          U(kCpos), U(kCvalid), k.n_clusters, cl_ok, k.rho_c};
 }
 }  // namespace
 
@@ -174,320 +173,32 @@ int rtw_scene_create(const rtw_sphere* spheres, uint32_t n, const rtw_material* 
                      rtw_scene* out) {
   if (!out) return fail(RTW_EINVAL, "rtw_scene_create: out is NULL");
   *out = nullptr;
-  if (n > 0 && !spheres) return fail(RTW_EINVAL, "rtw_scene_create: spheres is NULL");
-  if (nm > 0 && !mats) return fail(RTW_EINVAL, "rtw_scene_create: materials is NULL");
-  if (n > RTW_MAX_SPHERES || nm > RTW_MAX_SPHERES)
-    return fail(RTW_UNSUPPORTED, "rtw_scene_create: %u spheres / %u materials exceeds %u (BVH path not built)",
-                n, nm, RTW_MAX_SPHERES);
-  for (uint32_t i = 0; i < nm; ++i) {
-    if (mats[i].kind > RTW_DIELECTRIC)
-      return fail(RTW_UNSUPPORTED, "material %u: kind %u not supported on the GPU path", i, mats[i].kind);
-  }
-  // Distinct (t0, t1) pairs of moving spheres -> time groups.
-  std::vector<std::pair<double, double>> groups;
-  std::vector<uint32_t> meta_orig(n, 0u);
-  uint32_t n_moving = 0, n_wide = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    const rtw_sphere& s = spheres[i];
-    if (s.mat >= nm) return fail(RTW_EINVAL, "sphere %u: material index %u >= %u", i, s.mat, nm);
-    if (s.moving > 1) return fail(RTW_EINVAL, "sphere %u: moving flag %u", i, s.moving);
-    uint32_t m = (s.mat << 8) | (i << 20);
-    if (s.moving) {
-      ++n_moving;
-      uint32_t g = 0;
-      while (g < groups.size() && !(groups[g].first == s.t0 && groups[g].second == s.t1)) ++g;
-      if (g == groups.size()) {
-        if (groups.size() >= rtwk::kMaxTimeGroups)
-          return fail(RTW_UNSUPPORTED, "more than %u distinct moving-sphere time ranges", rtwk::kMaxTimeGroups);
-        groups.emplace_back(s.t0, s.t1);
-      }
-      m |= rtwk::kMoving | (g << 2);
-    }
-    if (s.radius >= rtwk::kWideRadius) {
-      m |= rtwk::kWide;
-      ++n_wide;
-    }
-    meta_orig[i] = m;
-  }
-  // Table order [static wide | static | moving wide | moving], list order within
-  // each group (rtw_internal.hpp); pos_of[i] = table position of sphere i.
-  std::vector<uint32_t> order;
-  order.reserve(n);
-  for (int grp = 0; grp < 4; ++grp)
-    for (uint32_t i = 0; i < n; ++i) {
-      const bool mv = (meta_orig[i] & rtwk::kMoving) != 0, wd = (meta_orig[i] & rtwk::kWide) != 0;
-      if ((int)mv * 2 + (int)!wd == grp) order.push_back(i);
-    }
-  uint32_t g_end[4] = {0, 0, 0, 0};
-  for (uint32_t i = 0; i < n; ++i) {
-    const bool mv = (meta_orig[i] & rtwk::kMoving) != 0, wd = (meta_orig[i] & rtwk::kWide) != 0;
-    for (int grp = (int)mv * 2 + (int)!wd; grp < 4; ++grp) ++g_end[grp];
-  }
-  std::vector<uint32_t> meta(n + 1, 0u), perm(n, 0u);
-  for (uint32_t k = 0; k < n; ++k) {
-    meta[k] = meta_orig[order[k]];
-    perm[order[k]] = k;
-  }
-  const uint32_t ng = (uint32_t)groups.size();
-  // Host tables (rtw_internal.hpp has the layout).  Reciprocals are correctly
-  // rounded IEEE divisions: the kernel's div_rn needs y = RN(1/b).
-  // sph / meta carry one zero padding record: the sphere loop prefetches k+1.
-  std::vector<double> sph64((size_t)8 * (n + 1), 0.0), rad64(n), mat64((size_t)8 * nm), tg64((size_t)4 * ng);
-  std::vector<float> sph32((size_t)8 * (n + 1), 0.0f), rad32(n), mat32((size_t)8 * nm), tg32((size_t)4 * ng);
-  std::vector<uint32_t> kind(nm);
-  for (uint32_t i = 0; i < n; ++i) {  // i = table position
-    const rtw_sphere& s = spheres[order[i]];
-    const double rec[8] = {s.c0[0], s.c0[1], s.c0[2], s.c1[0] - s.c0[0], s.c1[1] - s.c0[1], s.c1[2] - s.c0[2],
-                           s.radius * s.radius, 1.0 / s.radius};
-    for (int k = 0; k < 8; ++k) sph64[8 * i + k] = rec[k];
-    for (int k = 0; k < 6; ++k) sph32[8 * i + k] = (float)rec[k];
-    const float rf = (float)s.radius;
-    sph32[8 * i + 6] = rf * rf;  // f32 mode: r*r in f32 (tierb_core.h prep)
-    sph32[8 * i + 7] = 1.0f / rf;
-    rad64[i] = s.radius;
-    rad32[i] = rf;
-  }
-  for (uint32_t i = 0; i < nm; ++i) {
-    const rtw_material& m = mats[i];
-    const bool diel = m.kind == RTW_DIELECTRIC;
-    const double rec[8] = {m.albedo[0], m.albedo[1], m.albedo[2], m.albedo_odd[0], m.albedo_odd[1],
-                           m.albedo_odd[2], diel ? 1.0 / m.ir : m.fuzz, m.ir};
-    for (int k = 0; k < 8; ++k) {
-      mat64[8 * i + k] = rec[k];
-      mat32[8 * i + k] = (float)rec[k];
-    }
-    if (diel) {
-      mat32[8 * i + 6] = 1.0f / (float)m.ir;
-      // Schlick's r0^2 (material.zig:87-91) for ratio = RN(1/ir) (front face)
-      // and ir (back face), with the kernel's operations in each precision.
-      for (int f = 0; f < 2; ++f) {
-        const double rd = f == 0 ? mat64[8 * i + 6] : m.ir;
-        const double r0d = (1.0 - rd) / (1.0 + rd);
-        mat64[8 * i + f] = r0d * r0d;
-        const float rf = f == 0 ? mat32[8 * i + 6] : (float)m.ir;
-        const float r0f = (1.0f - rf) / (1.0f + rf);
-        mat32[8 * i + f] = r0f * r0f;
-      }
-    }
-    kind[i] = m.kind;
-  }
-  for (uint32_t g = 0; g < ng; ++g) {
-    const double t0 = groups[g].first, t1 = groups[g].second;
-    tg64[4 * g] = t0;
-    tg64[4 * g + 1] = t1;
-    tg64[4 * g + 2] = 1.0 / (t1 - t0);
-    const float f0 = (float)t0, f1 = (float)t1;
-    tg32[4 * g] = f0;
-    tg32[4 * g + 1] = f1;
-    tg32[4 * g + 2] = 1.0f / (f1 - f0);
-  }
-  // Pretest records (rtw_cull.hpp) over the narrow spheres in table order.
-  const uint32_t n_sn = g_end[1] - g_end[0], nn = n_sn + (n - g_end[2]);
-  const uint32_t nn_pad = (nn + 31u) & ~31u;
-  std::vector<float> cull((size_t)8 * nn_pad + 16, 0.0f);  // + one padding pair (prefetch)
-  std::vector<uint32_t> cull_tg(nn_pad / 2 + 1, 0u);
-  double cmax_c = 0.0, cmax_d = 0.0, rho_max = 1.0;
-  for (uint32_t j = 0; j < nn; ++j) {
-    const uint32_t pos = j < n_sn ? g_end[0] + j : g_end[2] + (j - n_sn);
-    const double* r = &sph64[8 * pos];
-    float* q = &cull[(size_t)16 * (j / 2) + (j & 1)];
-    for (int k = 0; k < 3; ++k) {
-      q[2 * k] = (float)r[k];
-      q[2 * (3 + k)] = -(float)r[3 + k];
-      cmax_c = std::max(cmax_c, std::fabs(r[k]));
-      cmax_d = std::max(cmax_d, std::fabs(r[3 + k]));
-    }
-    const float rf = (float)rad64[pos];
-    q[12] = -(rf * rf);
-    rho_max = std::max(rho_max, 2.0 * r[6] + 1.0);
-    const uint32_t g = (meta[pos] & rtwk::kMoving) ? (meta[pos] >> 2) & 63u : 0u;
-    cull_tg[j / 2] |= g << (8 * (j & 1));
-  }
-  for (uint32_t j = nn; j < nn_pad; ++j)  // padding: same time group as its partner
-    if (j & 1) cull_tg[j / 2] |= (cull_tg[j / 2] & 0xFFu) << 8;
-  for (uint32_t j = 0; j + 1 < nn; j += 2) {  // static half of a mixed pair: partner's group
-    const bool m0 = j >= n_sn, m1 = j + 1 >= n_sn;
-    if (!m0 && m1) cull_tg[j / 2] = (cull_tg[j / 2] & 0xFF00u) | (cull_tg[j / 2] >> 8);
-  }
-  // bit 16: both spheres of the pair move along y only (ndc.x == ndc.z == 0):
-  // the kernel's pretest then skips the x and z centre updates.
-  for (uint32_t p = 0; p < nn_pad / 2; ++p) {
-    const float* q = &cull[(size_t)16 * p];
-    if (q[6] == 0.0f && q[7] == 0.0f && q[10] == 0.0f && q[11] == 0.0f) cull_tg[p] |= 1u << 16;
-  }
-  const float cmax = std::nextafter((float)(cmax_c + cmax_d), INFINITY);
-  const float rho = std::nextafter((float)rho_max, INFINITY);
-  const uint32_t cull_on = (nn > 0 && cmax <= rtwc::kCmaxLimit) ? 1u : 0u;
-  // Clustered pretest tables (SceneView ccull..., trace VAR kVarCluster).
-  // kd-split of the narrow spheres (by the centre of their swept box over
-  // the shutter) into clusters of <= 8; members static first, so pairs are
-  // static-static where possible.  Bounding sphere of cluster c: centre
-  // C = f32(centre of the members' swept box), radius R = max over members
-  // of max(|c0 - C|, |c1 - C|) + |r|, widened by 1e-4 (1 + R): a line whose
-  // f64 discriminant for (C, R) is negative passes every member at a distance
-  // above its radius + 1e-4, far beyond the f64 rounding of the member's own
-  // exact test, which therefore rejects it.  Valid for
-  // sphere times within each time group's [t0, t1] (checked per render).
-  std::vector<uint32_t> cl_items;  // j (narrow index) per slot, ~0u = dummy
-  std::vector<float> cclus;
-  double cmax_cl = 0.0, rho_cl = 1.0;
-  {
-    auto cen_of = [&](uint32_t j, int k) {
-      const uint32_t pos = j < n_sn ? g_end[0] + j : g_end[2] + (j - n_sn);
-      const double* r = &sph64[8 * pos];
-      return r[k] + 0.5 * r[3 + k];
-    };
-    std::vector<std::vector<uint32_t>> groups;
-    std::vector<uint32_t> all(nn);
-    for (uint32_t j = 0; j < nn; ++j) all[j] = j;
-    if (nn) groups.push_back(all);
-    for (bool again = true; again;) {
-      again = false;
-      for (size_t gi = 0; gi < groups.size(); ++gi) {
-        if (groups[gi].size() <= rtwk::kClusterSlots) continue;
-        std::vector<uint32_t> g = groups[gi];
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t j : g)
-          for (int k = 0; k < 3; ++k) lo[k] = std::min(lo[k], cen_of(j, k)), hi[k] = std::max(hi[k], cen_of(j, k));
-        int ax = 0;
-        for (int k = 1; k < 3; ++k)
-          if (hi[k] - lo[k] > hi[ax] - lo[ax]) ax = k;
-        std::stable_sort(g.begin(), g.end(), [&](uint32_t a, uint32_t b) { return cen_of(a, ax) < cen_of(b, ax); });
-        // Split sizes: whole clusters of 8 on the left, ceil(n/8) clusters in
-        // all (profiles/r02/cluster_ab.txt: fewer, fuller clusters beat
-        // smaller ones whose bounds are tighter: each cluster costs a ballot
-        // and a branch per wave-iteration).
-        constexpr size_t CS = rtwk::kClusterSlots;
-        const size_t h = CS * (((g.size() + CS - 1) / CS) / 2);
-        groups[gi].assign(g.begin(), g.begin() + h);
-        groups.emplace_back(g.begin() + h, g.end());
-        again = true;
-      }
-    }
-    for (auto& g : groups) {
-      std::stable_sort(g.begin(), g.end(), [&](uint32_t a, uint32_t b) { return (a >= n_sn) < (b >= n_sn); });
-      double mc0[rtwk::kClusterSlots][3], mdc[rtwk::kClusterSlots][3], mr[rtwk::kClusterSlots];
-      for (size_t i = 0; i < g.size(); ++i) {
-        const uint32_t pos = g[i] < n_sn ? g_end[0] + g[i] : g_end[2] + (g[i] - n_sn);
-        for (int k = 0; k < 3; ++k) mc0[i][k] = sph64[8 * pos + k], mdc[i][k] = sph64[8 * pos + 3 + k];
-        mr[i] = rad64[pos];
-      }
-      float cf[3], rf;
-      rtwc::cluster_sphere(mc0, mdc, mr, (int)g.size(), cf, rf);
-      const size_t c = cl_items.size() / rtwk::kClusterSlots;
-      if (cclus.size() < 16 * (c / 2 + 1)) cclus.resize(16 * (c / 2 + 1), 0.0f);
-      float* q = &cclus[16 * (c / 2) + (c & 1)];
-      for (int k = 0; k < 3; ++k) q[2 * k] = cf[k], cmax_cl = std::max(cmax_cl, (double)std::fabs(cf[k]));
-      q[12] = -(rf * rf);
-      rho_cl = std::max(rho_cl, 2.0 * (double)rf * (double)rf + 1.0);
-      for (uint32_t i = 0; i < rtwk::kClusterSlots; ++i) cl_items.push_back(i < g.size() ? g[i] : ~0u);
-    }
-  }
-  const uint32_t n_clusters = (uint32_t)(cl_items.size() / rtwk::kClusterSlots);
-  const uint32_t n_cslots = rtwk::kClusterSlots * n_clusters;
-  // slot tables; a dummy slot's record (c = 0, nr2 = +3e38) is a proven miss for every lane
-  std::vector<float> ccull((size_t)8 * n_cslots + 16, 0.0f);
-  std::vector<uint32_t> ccull_tg(n_cslots / 2 + 1, 0u), cpos(std::max(n_cslots, 1u), 0u);
-  std::vector<uint32_t> cvalid(2 * ((n_cslots + 63) / 64) + 2, 0u);
-  for (uint32_t sl = 0; sl < n_cslots; ++sl) {
-    float* q = &ccull[(size_t)16 * (sl / 2) + (sl & 1)];
-    const uint32_t j = cl_items[sl];
-    if (j == ~0u) {
-      q[12] = 3e38f;
-      continue;
-    }
-    const uint32_t pos = j < n_sn ? g_end[0] + j : g_end[2] + (j - n_sn);
-    const float* src = &cull[(size_t)16 * (j / 2) + (j & 1)];  // the member's own pretest record
-    for (int k = 0; k < 7; ++k) q[2 * k] = src[2 * k];
-    cpos[sl] = pos;
-    cvalid[2 * (sl / 64) + ((sl % 64) >> 5)] |= 0x80000000u >> (sl & 31u);
-    const uint32_t g = (meta[pos] & rtwk::kMoving) ? (meta[pos] >> 2) & 63u : 0u;
-    ccull_tg[sl / 2] |= g << (8 * (sl & 1));
-  }
-  for (uint32_t p = 0; p < n_cslots / 2; ++p) {
-    const uint32_t j0 = cl_items[2 * p], j1 = cl_items[2 * p + 1];
-    const bool m0 = j0 != ~0u && j0 >= n_sn, m1 = j1 != ~0u && j1 >= n_sn;
-    if (!m0 && !m1) ccull_tg[p] |= 1u << 17;  // static pair (dummies count as static)
-    if (!m0 && m1) ccull_tg[p] = (ccull_tg[p] & 0xFF00u) | ((ccull_tg[p] >> 8) & 0xFFu) | (ccull_tg[p] & ~0xFFFFu);
-    if (m0 && !m1) ccull_tg[p] = (ccull_tg[p] & 0xFFu) | ((ccull_tg[p] & 0xFFu) << 8) | (ccull_tg[p] & ~0xFFFFu);
-    const float* q = &ccull[(size_t)16 * p];
-    if (q[6] == 0.0f && q[7] == 0.0f && q[10] == 0.0f && q[11] == 0.0f) ccull_tg[p] |= 1u << 16;
-  }
-  if (cclus.empty()) cclus.assign(16, 0.0f);
-  const float cmax_all = std::max(cmax, std::nextafter((float)cmax_cl, INFINITY));
-  const float rho_c = std::nextafter((float)rho_cl, INFINITY);
-  // One device allocation, 256-B aligned sub-buffers.
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  size_t off = 0;
-  auto place = [&](size_t bytes) {
-    const size_t o = off;
-    off += al(bytes + 8);
-    return o;
-  };
-  const size_t o_sph64 = place(sph64.size() * 8), o_rad64 = place(rad64.size() * 8);
-  const size_t o_mat64 = place(mat64.size() * 8), o_tg64 = place(tg64.size() * 8);
-  const size_t o_sph32 = place(sph32.size() * 4), o_rad32 = place(rad32.size() * 4);
-  const size_t o_mat32 = place(mat32.size() * 4), o_tg32 = place(tg32.size() * 4);
-  const size_t o_meta = place(meta.size() * 4), o_kind = place(kind.size() * 4), o_perm = place(perm.size() * 4);
-  const size_t o_cull = place(cull.size() * 4), o_cull_tg = place(cull_tg.size() * 4);
-  const size_t o_ccull = place(ccull.size() * 4), o_ccull_tg = place(ccull_tg.size() * 4);
-  const size_t o_cclus = place(cclus.size() * 4), o_cpos = place(cpos.size() * 4), o_cvalid = place(cvalid.size() * 4);
-  const size_t total = off;
-  std::vector<unsigned char> host(total, 0);
-  auto cp = [&](size_t o, const void* p, size_t bytes) {
-    if (bytes) std::memcpy(host.data() + o, p, bytes);
-  };
-  cp(o_sph64, sph64.data(), sph64.size() * 8);
-  cp(o_rad64, rad64.data(), rad64.size() * 8);
-  cp(o_mat64, mat64.data(), mat64.size() * 8);
-  cp(o_tg64, tg64.data(), tg64.size() * 8);
-  cp(o_sph32, sph32.data(), sph32.size() * 4);
-  cp(o_rad32, rad32.data(), rad32.size() * 4);
-  cp(o_mat32, mat32.data(), mat32.size() * 4);
-  cp(o_tg32, tg32.data(), tg32.size() * 4);
-  cp(o_meta, meta.data(), meta.size() * 4);
-  cp(o_kind, kind.data(), kind.size() * 4);
-  cp(o_perm, perm.data(), perm.size() * 4);
-  cp(o_cull, cull.data(), cull.size() * 4);
-  cp(o_cull_tg, cull_tg.data(), cull_tg.size() * 4);
-  cp(o_ccull, ccull.data(), ccull.size() * 4);
-  cp(o_ccull_tg, ccull_tg.data(), ccull_tg.size() * 4);
-  cp(o_cclus, cclus.data(), cclus.size() * 4);
-  cp(o_cpos, cpos.data(), cpos.size() * 4);
-  cp(o_cvalid, cvalid.data(), cvalid.size() * 4);
-
+  rtwp::ScenePack k;
+  std::string msg;
+  const int st = rtwp::pack_scene(spheres, n, mats, nm, k, msg);
+  if (st != RTW_OK) return fail(st, "%s", msg.c_str());
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
+  const size_t total = k.blob.size();
   void* d = nullptr;
   if (hipMalloc(&d, total) != hipSuccess) return fail(RTW_ENOMEM, "rtw_scene_create: hipMalloc(%zu)", total);
-  if (hipMemcpy(d, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipMemcpy(d, k.blob.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipFree(d);
     return fail(RTW_EHIP, "rtw_scene_create: hipMemcpy failed");
   }
   auto* sc = new rtw_scene_s;
   sc->device = dev;
-  sc->n = n;
-  sc->nm = nm;
-  sc->ng = ng;
-  sc->n_moving = n_moving;
-  sc->n_static = n - n_moving;
-  sc->n_wide = n_wide;
+  sc->n = k.n;
+  sc->nm = k.nm;
+  sc->ng = k.ng;
+  sc->n_moving = k.n_moving;
+  sc->n_static = k.n_static;
+  sc->n_wide = k.n_wide;
   sc->buf = d;
-  auto* b = static_cast<unsigned char*>(d);
-  auto D = [&](size_t o) { return reinterpret_cast<const double*>(b + o); };
-  auto F = [&](size_t o) { return reinterpret_cast<const float*>(b + o); };
-  auto U = [&](size_t o) { return reinterpret_cast<const uint32_t*>(b + o); };
-  // cluster_on (per render, fill_args): usable when the scene's bound allows (cmax_all within the limit)
-  const uint32_t cl_ok = (n_clusters > 0 && cull_on && cmax_all <= rtwc::kCmaxLimit) ? 1u : 0u;
-  sc->v64 = {D(o_sph64), D(o_rad64), U(o_meta), D(o_mat64), U(o_kind), D(o_tg64), D(o_sph64), D(o_tg64), U(o_perm),
-             F(o_cull), U(o_cull_tg), F(o_tg32), n, nm, ng, g_end[0], g_end[1], g_end[2], nn, nn_pad, n_sn, cull_on,
-             cl_ok ? cmax_all : cmax, rho, F(o_ccull), U(o_ccull_tg), F(o_cclus), U(o_cpos), U(o_cvalid), n_clusters,
-             cl_ok, rho_c};
-  sc->v32 = {F(o_sph32), F(o_rad32), U(o_meta), F(o_mat32), U(o_kind), F(o_tg32), D(o_sph64), D(o_tg64), U(o_perm),
-             F(o_cull), U(o_cull_tg), F(o_tg32), n, nm, ng, g_end[0], g_end[1], g_end[2], nn, nn_pad, n_sn, cull_on,
-             cmax, rho, F(o_ccull), U(o_ccull_tg), F(o_cclus), U(o_cpos), U(o_cvalid), n_clusters, 0u, rho_c};
-  sc->cull_cmax_cl = cmax_all;
-  sc->groups = groups;
+  sc->v64 = scene_view<double>(k, static_cast<unsigned char*>(d));
+  sc->v32 = scene_view<float>(k, static_cast<unsigned char*>(d));
+  sc->cull_cmax_cl = k.cmax_all;
+  sc->groups = std::move(k.groups);
   *out = sc;
   return RTW_OK;
 }
@@ -689,57 +400,6 @@ uint32_t clusters_usable(const rtw_scene_s* sc, const rtw_camera* cam) {
 
 // ---------------------------------------------------------- wavefront ----
 template <typename R>
-struct WfLaunch;
-template <>
-struct WfLaunch<double> {
-  static hipError_t gen(const rtwk::WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s) {
-    return rtwk::launch_wf_generate_f64(a, g, l, s);
-  }
-  static hipError_t ext(const rtwk::WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s) {
-    return rtwk::launch_wf_extend_f64(a, g, l, s);
-  }
-  static hipError_t shd(const rtwk::WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
-    return rtwk::launch_wf_shade_f64(a, g, l, s, stats);
-  }
-  static hipError_t fin(const rtwk::WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
-    return rtwk::launch_wf_finish_f64(a, g, l, s, stats);
-  }
-  static hipError_t drain(const rtwk::WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
-    return rtwk::launch_wf_drain_f64(a, g, l, s, stats);
-  }
-  static hipError_t gen_hit(const rtwk::WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s) {
-    return rtwk::launch_wf_generate_hit_f64(a, g, l, s);
-  }
-  static hipError_t step(const rtwk::WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
-    return rtwk::launch_wf_step_f64(a, g, l, s, stats);
-  }
-};
-template <>
-struct WfLaunch<float> {
-  static hipError_t gen(const rtwk::WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s) {
-    return rtwk::launch_wf_generate_f32(a, g, l, s);
-  }
-  static hipError_t ext(const rtwk::WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s) {
-    return rtwk::launch_wf_extend_f32(a, g, l, s);
-  }
-  static hipError_t shd(const rtwk::WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
-    return rtwk::launch_wf_shade_f32(a, g, l, s, stats);
-  }
-  static hipError_t fin(const rtwk::WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
-    return rtwk::launch_wf_finish_f32(a, g, l, s, stats);
-  }
-  static hipError_t drain(const rtwk::WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
-    return rtwk::launch_wf_drain_f32(a, g, l, s, stats);
-  }
-  static hipError_t gen_hit(const rtwk::WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s) {
-    return rtwk::launch_wf_generate_hit_f32(a, g, l, s);
-  }
-  static hipError_t step(const rtwk::WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
-    return rtwk::launch_wf_step_f32(a, g, l, s, stats);
-  }
-};
-
-template <typename R>
 rtwk::PathBuf<R> carve_queue(unsigned char*& b, size_t n) {
   rtwk::PathBuf<R> q;
   R** arr[10] = {&q.ox, &q.oy, &q.oz, &q.dx, &q.dy, &q.dz, &q.tx, &q.ty, &q.tz, &q.tm};
@@ -931,7 +591,8 @@ int run_wavefront(const rtwk::TraceArgs<R>& ta, const rtw_params* p, unsigned ch
     // generate -> queue A
     a.out = S.qa;
     a.seg_out = S.seg_a;
-    const hipError_t e = fused ? WfLaunch<R>::gen_hit(a, grid_step, lds, S.s) : WfLaunch<R>::gen(a, grid, 0, S.s);
+    const hipError_t e =
+        fused ? rtwk::launch_wf_generate_hit(a, grid_step, lds, S.s) : rtwk::launch_wf_generate(a, grid, 0, S.s);
     if (e != hipSuccess) st = fail(RTW_EHIP, "wavefront generate launch: %s", hipGetErrorString(e));
     S.started = true;
   }
@@ -968,9 +629,9 @@ int run_wavefront(const rtwk::TraceArgs<R>& ta, const rtw_params* p, unsigned ch
         a.seg_in = even ? S.seg_a : S.seg_b;
         a.seg_out = even ? S.seg_b : S.seg_a;
         if (fused)
-          e = WfLaunch<R>::step(a, grid_step, lds, S.s, stats);
-        else if ((e = WfLaunch<R>::ext(a, grid_ext, lds, S.s)) == hipSuccess)
-          e = WfLaunch<R>::shd(a, grid, lds, S.s, stats);
+          e = rtwk::launch_wf_step(a, grid_step, lds, S.s, stats);
+        else if ((e = rtwk::launch_wf_extend(a, grid_ext, lds, S.s)) == hipSuccess)
+          e = rtwk::launch_wf_shade(a, grid, lds, S.s, stats);
       }
       if (e != hipSuccess) {
         st = fail(RTW_EHIP, "wavefront bounce launch: %s", hipGetErrorString(e));
@@ -1000,8 +661,8 @@ int run_wavefront(const rtwk::TraceArgs<R>& ta, const rtw_params* p, unsigned ch
         rtwk::WfArgs<R>& a = S.a;
         a.in = S.qa;
         a.seg_in = S.seg_a;
-        const hipError_t e = per_sample ? WfLaunch<R>::drain(a, max_grid, lds, S.s, stats)
-                                        : WfLaunch<R>::fin(a, max_grid, lds, S.s, stats);
+        const hipError_t e = per_sample ? rtwk::launch_wf_drain(a, max_grid, lds, S.s, stats)
+                                        : rtwk::launch_wf_finish(a, max_grid, lds, S.s, stats);
         if (e != hipSuccess) st = fail(RTW_EHIP, "wavefront finish launch: %s", hipGetErrorString(e));
       }
       if (live == 0u || (double)live < fin_frac * (double)n) {

@@ -69,9 +69,9 @@ __device__ __forceinline__ V3<R> ld3(const __attribute__((address_space(4))) R* 
 // for f64 when VAR has kVarFastSqrt.
 constexpr int kVarFastSqrt = 32768;
 // Dielectric: Schlick's r0^2 for both ratios precomputed in the material
-// record (rtw_capi.hip: doubles 0, 1 of a dielectric; its albedo is unused).
+// record (rtw_scene_pack.cpp: doubles 0, 1 of a dielectric; its albedo is unused).
 constexpr int kVarR0Table = 131072;
-// Pretest: pairs flagged y-only (rtw_capi.hip cull_tg bit 16) skip the x/z
+// Pretest: pairs flagged y-only (rtw_scene_pack.cpp cull_tg bit 16) skip the x/z
 // centre updates.
 constexpr int kVarYOnly = 65536;
 // Trace loop rotated so that the lens-disk points of new samples and the

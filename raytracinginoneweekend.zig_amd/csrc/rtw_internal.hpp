@@ -22,14 +22,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rtw_layout.hpp"  // kMoving, kClusterSlots, kNodeWords, kLeafBit, ...: the layout's constants (no HIP)
+
 namespace rtwk {
 
-constexpr uint32_t kMoving = 1u;
-constexpr uint32_t kWide = 2u;
-constexpr uint32_t kMaxTimeGroups = 64;
 constexpr uint32_t kTileW = 8, kTileH = 8;  // 64 pixels = one wave's batch
 constexpr uint32_t kBatch = 64;             // work units fetched per atomic
-constexpr double kWideRadius = 100.0;       // f32 mode: radius >= this -> f64 quadratic
 
 template <typename R>
 struct SceneView {
@@ -64,12 +62,6 @@ struct SceneView {
   uint32_t cluster_on;        // clusters usable (set per render: camera times within every time group)
   float cull_rho_cl;          // max 2 R^2 + 1 over the cluster bounding spheres (rounded up)
 };
-
-#ifndef RTW_CLUSTER_SLOTS  // (A/B builds override it: 4 or 8)
-#define RTW_CLUSTER_SLOTS 8
-#endif
-constexpr uint32_t kClusterSlots = RTW_CLUSTER_SLOTS;  // slots per cluster (even, divides 64)
-static_assert(kClusterSlots % 2 == 0 && 64 % kClusterSlots == 0, "cluster slots");
 
 template <typename R>
 struct TraceArgs {
@@ -245,16 +237,17 @@ struct WfArgs {
                        // then shade the stored hit first instead of tracing the segment again
 };
 
-hipError_t launch_wf_generate_f64(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s);
-hipError_t launch_wf_extend_f64(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s);
-hipError_t launch_wf_shade_f64(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
-hipError_t launch_wf_generate_f32(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s);
-hipError_t launch_wf_extend_f32(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s);
-hipError_t launch_wf_shade_f32(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
-hipError_t launch_wf_finish_f64(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
-hipError_t launch_wf_finish_f32(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
-hipError_t launch_wf_drain_f64(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
-hipError_t launch_wf_drain_f32(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
+// The launchers are overloaded on the precision of their WfArgs.
+hipError_t launch_wf_generate(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s);
+hipError_t launch_wf_generate(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s);
+hipError_t launch_wf_extend(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s);
+hipError_t launch_wf_extend(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s);
+hipError_t launch_wf_shade(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
+hipError_t launch_wf_shade(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
+hipError_t launch_wf_finish(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
+hipError_t launch_wf_finish(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
+hipError_t launch_wf_drain(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
+hipError_t launch_wf_drain(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
 // Resident workgroups per CU of a bounce kernel (1 = extend, 2 = shade): the
 // persistent grid of that kernel is CUs x this.
 int wf_blocks_per_cu(int precision, int kernel, size_t lds);
@@ -262,10 +255,10 @@ int wf_blocks_per_cu(int precision, int kernel, size_t lds);
 hipError_t launch_wf_count(const uint32_t* seg_in, uint32_t n_segs, uint32_t* live, hipStream_t s);
 // Fused engine (default): generate + the first closest hit, then one kernel
 // per bounce (shade + the next closest hit; the hit travels with the path).
-hipError_t launch_wf_generate_hit_f64(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s);
-hipError_t launch_wf_generate_hit_f32(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s);
-hipError_t launch_wf_step_f64(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
-hipError_t launch_wf_step_f32(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
+hipError_t launch_wf_generate_hit(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s);
+hipError_t launch_wf_generate_hit(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s);
+hipError_t launch_wf_step(const WfArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
+hipError_t launch_wf_step(const WfArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, bool stats);
 // *bad = violations of the drained state (non-empty segment, unit left in a
 // reservoir, queue head below total_units); 0 after a complete frame.
 hipError_t launch_wf_check_drained(const uint32_t* seg_in, const uint32_t* resv, uint32_t n_segs, const uint32_t* head,
@@ -292,19 +285,9 @@ hipError_t launch_wf_check_drained(const uint32_t* seg_in, const uint32_t* resv,
 //   order  : list index -> stored position (the NaN fallback's sequential loop)
 // Prims are stored in BVH leaf order; `orig` keeps the list index for the
 // reference's tie rule (later object wins).
-constexpr uint32_t kWorldRec = 16;   // doubles per prim / xform / texture record
-constexpr uint32_t kMaxXfOps = 4;    // ops per transform chain (== RTW_MAX_XFORM_OPS)
-constexpr uint32_t kNodeWords = 16;  // 32-bit words per BVH node
-constexpr uint32_t kLeafBit = 0x80000000u;
-constexpr uint32_t kCullBit = 0x40000000u;  // leaf ref: pretest record present
-constexpr uint32_t kLeafCountMask = 0x7Fu;  // leaf ref: count = (ref >> 23) & mask
-constexpr uint32_t kBvhStack = 32;  // per-wave LDS stack entries (the builder caps the depth)
-// per-LANE stack entries of the per-lane traversal (rtw_world.hip closest_lane):
-// a BVH of depth <= kLaneStack never overflows it (a push per level at most);
-// deeper BVHs take the union walk
-constexpr uint32_t kLaneStack = 16;
-// ... of which kLaneStack - 1 in LDS rows: the walk keeps the stack's top entry
-// in a register, and a tree of depth D holds at most D pending nodes (one
+// (record sizes, ref bits, kBvhStack, kLaneStack, kNodeCache, kMaxLeafPrims: rtw_layout.hpp)
+// Of the per-lane walk's kLaneStack entries, kLaneStack - 1 are LDS rows: the
+// walk keeps the stack's top entry in a register, and a tree of depth D holds at most D pending nodes (one
 // sibling per level of the current path: pops take the deepest), so D - 1 rows
 // (RTW_LANE_STACK_LDS: the rows built; the default keeps kLaneStack, one to spare)
 #ifndef RTW_LANE_STACK_LDS
@@ -312,25 +295,9 @@ constexpr uint32_t kLaneStack = 16;
 #endif
 constexpr uint32_t kLaneStackLds = RTW_LANE_STACK_LDS;
 static_assert(kLaneStackLds + 1 >= kLaneStack, "a depth-kLaneStack tree must fit the LDS rows + the top register");
-// The per-lane walk's node cache: the first kNodeCache node records (the top
-// of the tree in breadth-first order, rtw_world_capi.hip top_first) staged in
-// LDS once per workgroup; a lane visiting one reads it with ds_read instead of
-// three vector loads through the TA/TD pipe that bounds the walk.  0: none —
-// the default: 21 records (with RTW_LANE_STACK_LDS 15 to fit four workgroups
-// per CU) measured equal on the globe, 31.67 vs 31.29 ms (the walk pays per
-// wave iteration, ~41 per segment for ~18 visits per lane, not per lane-load);
-// profiles/r06/world_ncache_ab.txt.
-#ifndef RTW_NODE_CACHE
-#define RTW_NODE_CACHE 0
-#endif
-constexpr uint32_t kNodeCache = RTW_NODE_CACHE;
 // per-lane walk: a paused walk keeps its closest hit's stored position + 1 in
 // the low kTravPosBits of one LDS word (rtw_world.hip LaneTravRows)
 constexpr uint32_t kTravPosBits = 26;
-#ifndef RTW_MAX_LEAF_PRIMS
-#define RTW_MAX_LEAF_PRIMS 2  // BVH leaf size (profiles/r01/world_leaf_ab.txt; experiment builds override it)
-#endif
-constexpr uint32_t kMaxLeafPrims = RTW_MAX_LEAF_PRIMS;
 
 struct WorldView {
   const double* prim;
@@ -346,7 +313,6 @@ struct WorldView {
   uint32_t n_prims, n_nodes, n_perlins, flags;
   float cull_cmax, cull_rho;     // rtw_cull.hpp Cmax and rho_max over the pretested spheres
 };
-constexpr uint32_t kWorldHasSpheres = 1;  // WorldView.flags
 
 struct WorldArgs {
   TraceArgs<double> t;  // MUST stay at offset 0 (kargs<double>()); t.sc unused

@@ -1011,46 +1011,46 @@ static hipError_t launch3(int k, const WfArgs<R>& a, uint32_t grid, size_t lds, 
     hipLaunchKernelGGL((wf_finish<R, F32, true>), dim3(grid), dim3(kTraceBlock), lds, s, a);
   return hipGetLastError();
 }
-hipError_t launch_wf_generate_f64(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s) {
+hipError_t launch_wf_generate(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s) {
   return launch3<double, false>(0, a, g, l, s);
 }
-hipError_t launch_wf_extend_f64(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s) {
+hipError_t launch_wf_extend(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s) {
   return launch3<double, false>(1, a, g, l, s);
 }
-hipError_t launch_wf_shade_f64(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
+hipError_t launch_wf_shade(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
   return launch3<double, false>(stats ? 3 : 2, a, g, l, s);
 }
-hipError_t launch_wf_finish_f64(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
+hipError_t launch_wf_finish(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
   return launch3<double, false>(stats ? 5 : 4, a, g, l, s);
 }
-hipError_t launch_wf_finish_f32(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
+hipError_t launch_wf_finish(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
   return launch3<float, true>(stats ? 5 : 4, a, g, l, s);
 }
-hipError_t launch_wf_drain_f64(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
+hipError_t launch_wf_drain(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
   return launch3<double, false>(stats ? 10 : 9, a, g, l, s);
 }
-hipError_t launch_wf_drain_f32(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
+hipError_t launch_wf_drain(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
   return launch3<float, true>(stats ? 10 : 9, a, g, l, s);
 }
-hipError_t launch_wf_generate_hit_f64(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s) {
+hipError_t launch_wf_generate_hit(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s) {
   return launch3<double, false>(6, a, g, l, s);
 }
-hipError_t launch_wf_generate_hit_f32(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s) {
+hipError_t launch_wf_generate_hit(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s) {
   return launch3<float, true>(6, a, g, l, s);
 }
-hipError_t launch_wf_step_f64(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
+hipError_t launch_wf_step(const WfArgs<double>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
   return launch3<double, false>(stats ? 8 : 7, a, g, l, s);
 }
-hipError_t launch_wf_step_f32(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
+hipError_t launch_wf_step(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
   return launch3<float, true>(stats ? 8 : 7, a, g, l, s);
 }
-hipError_t launch_wf_generate_f32(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s) {
+hipError_t launch_wf_generate(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s) {
   return launch3<float, true>(0, a, g, l, s);
 }
-hipError_t launch_wf_extend_f32(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s) {
+hipError_t launch_wf_extend(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s) {
   return launch3<float, true>(1, a, g, l, s);
 }
-hipError_t launch_wf_shade_f32(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
+hipError_t launch_wf_shade(const WfArgs<float>& a, uint32_t g, size_t l, hipStream_t s, bool stats) {
   return launch3<float, true>(stats ? 3 : 2, a, g, l, s);
 }
 

@@ -61,7 +61,7 @@ constexpr int kFeatAll = kFeatNoise | kFeatImage | kFeatXform | kFeatRect;
 // Not a world feature: the sphere-world instantiation that traverses the BVH
 // per lane (closest_lane) instead of as the wave's union (closest).
 constexpr int kFeatLane = 16;
-// ... reading each child's ref from its lower bounds' low bits (rtw_world_capi.hip pack_refs).
+// ... reading each child's ref from its lower bounds' low bits (rtw_world_pack.cpp pack_refs).
 constexpr int kFeatPacked = 32;
 
 __device__ __forceinline__ const uint32_t* meta_of(const D* r) { return reinterpret_cast<const uint32_t*>(r + 14); }
@@ -127,7 +127,7 @@ __device__ __forceinline__ PrimRec load_rec(P r) {
 }
 
 // The per-lane walk's record load: doubles 0-10 and the {kind, list index}
-// copy in double 11 (rtw_world_capi.hip), one 96-B span = six 16-B loads.
+// copy in double 11 (rtw_world_pack.cpp), one 96-B span = six 16-B loads.
 template <typename P>
 __device__ __forceinline__ PrimRec load_rec_lane(P r) {
   PrimRec q;
@@ -412,7 +412,7 @@ __device__ __forceinline__ void closest(const WV& W, D m, uint32_t* stack, const
         reinterpret_cast<const RTW_CONST float*>(reinterpret_cast<const RTW_CONST char*>(cn) + (node << 6));
     static_assert(kNodeWords * 4 == 64, "node record size");
     // The first word of record node + 1 — the left child whenever that child
-    // is interior (depth-first layout, rtw_world_capi.hip Builder) — loaded
+    // is interior (depth-first layout, rtw_world_pack.cpp Builder) — loaded
     // with this node's record (one wait covers both): the child's visit then
     // finds its line in the scalar cache.  (A padding record follows the last;
     // record node + 2 as well: 3 % slower, profiles/r04/world_touch_next_ab.txt.)
@@ -574,7 +574,7 @@ __device__ __forceinline__ bool trav_phase(const WV& W, D m, uint32_t* lstack, L
   // waited for the stack pop's LDS read, which `top` is there to hide)
   using GF = const __attribute__((address_space(1))) float;  // global: vector memory loads, not flat
   GF* nodes = (GF*)W.node;
-  // PACKED: refs in the lower bounds' low bytes, as 24 bits (rtw_world_capi.hip pack_refs): a leaf
+  // PACKED: refs in the lower bounds' low bytes, as 24 bits (rtw_world_pack.cpp pack_refs): a leaf
   // is LB | (count - 1) << 22 | first; the walk keeps refs in that form (kNoRef stays kNoRef).
   constexpr bool PACKED = (FEAT & kFeatPacked) != 0;
   constexpr uint32_t LB = PACKED ? 0x800000u : kLeafBit;

@@ -1,5 +1,5 @@
 // rtw_world_box.hpp — world-space bounding boxes of the general world's
-// primitives (the BVH builder's input, rtw_world_capi.hip).  Host only, no
+// primitives (the BVH builder's input, rtw_world_pack.cpp).  Host only, no
 // HIP: tests/native/prim_box_check.cpp compiles it with a plain C++ compiler
 // and checks that every box holds its primitive.
 #pragma once

@@ -84,7 +84,7 @@ int main(int argc, char** argv) {
     const float hbf = ocf[0] * df[0] + ocf[1] * df[1] + ocf[2] * df[2];
     const float ccf = (ocf[0] * ocf[0] + ocf[1] * ocf[1] + ocf[2] * ocf[2]) - rf * rf;
     const float disc32 = hbf * hbf - af32 * ccf;
-    // pretest, table values as rtw_capi.hip builds them
+    // pretest, table values as rtw_scene_pack.cpp builds them
     const double cm = std::fmax(std::fabs(c0.x), std::fmax(std::fabs(c0.y), std::fabs(c0.z))) +
                       std::fmax(std::fabs(dc.x), std::fmax(std::fabs(dc.y), std::fabs(dc.z)));
     const float cmax = std::nextafter((float)cm, INFINITY);

@@ -1,6 +1,6 @@
 // prim_box (csrc/rtw_world_box.hpp) is conservative: the box the BVH builder
-// gets for a primitive holds every point of the primitive, at every shutter
-// time in [0, 1], after its Translate / RotateY chain.
+// (csrc/rtw_world_pack.cpp) gets for a primitive holds every point of the
+// primitive, at every shutter time in [0, 1], after its Translate / RotateY chain.
 //
 // Random primitives of every kind (spheres, one radius in ten negative; moving
 // spheres with their own time ranges, so the box is an extrapolation to times

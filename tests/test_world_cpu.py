@@ -337,7 +337,7 @@ def test_globe_bvh_isolates_the_ground_at_the_root():
     assert len(lines) == 2, p.stderr
     assert "leaf of 1, box x [-1000, 1000] y [-2000, 0] z [-1000, 1000]" in lines[0]
     assert "node" in lines[1] and "y [0, 4]" in lines[1]
-    # the per-lane walk's refs packed into the lower bounds (rtw_world_capi.hip pack_refs): the
+    # the per-lane walk's refs packed into the lower bounds (rtw_world_pack.cpp pack_refs): the
     # device's byte gather restated on the host recovers every ref, and no bound moved up
     # the globe's SAH tree fits the per-lane walk's stack as built (no depth-capped rebuild)
     dl = [l for l in p.stderr.splitlines() if l.startswith("[rtw bvh]") and "depth" in l]
@@ -352,7 +352,7 @@ def test_deep_sphere_world_bvh_capped_for_the_lane_walk():
     """the per-lane walk keeps its stack in 16 LDS entries per
     lane.  A >= 10k-sphere world whose binned-SAH tree is deeper than that
     (helpers.deep_cluster_world: depth 24) is rebuilt by rtw_world_create with
-    SAH splits only while a median subtree still fits (rtw_world_capi.hip
+    SAH splits only while a median subtree still fits (rtw_world_pack.cpp
     Builder depth_cap): depth <= 16, leaves of one, refs packed — the lane walk
     stays available (the GPU test renders it against the linear loop).  The
     globe's own SAH tree (depth 16) is kept as built (the globe test above)."""
