@@ -467,6 +467,68 @@ int rtw_accum_noise(rtw_accum a, void *stream, double *noise);
 int rtw_accum_read(rtw_accum a, double *sum_out, double *stat_out);
 int rtw_accum_load(rtw_accum a, const double *sum, const double *stat, uint32_t samples_done);
 
+/* ---- adaptive sampling: masked passes and a per-pixel noise budget ----
+ *   The first rtw_accum_set_mask, rtw_accum_set_adaptive
+ * (tol > 0) or rtw_accum_load_counts puts the accumulator in the MASKED state,
+ * for good: it then keeps a per-pixel sample count and an active set.
+ *
+ * A pixel is active while it has received every sample so far (count ==
+ * samples done), the mask keeps it and the budget has not found it converged.
+ * Once inactive it stays inactive: a later pass covers samples
+ * [done, done + pass_spp) for all pixels alike, so a pixel that skipped a pass
+ * could no longer hold a prefix of its sample stream.  A pass renders the
+ * active pixels only (the launch covers only the 8x8 tiles that hold one) and
+ * the fold touches nothing of an inactive pixel.
+ *
+ * Contract, per pixel: a pixel whose count is n holds the bytes of the
+ * one-shot render with spp = n at that pixel — rgb8, mean, and the running
+ * sum — for every engine, precision, row shard and world, whenever n is a
+ * multiple of the chunk or params->spp.  rtw_accum_resolve_device divides
+ * each pixel by its own count (a pixel with no sample resolves to 0).
+ *
+ * Synchronisation: in the masked state rtw_accum_render_device /
+ * rtw_accum_world_render_device first WAIT, on the host, for the active-set
+ * update of the previous pass and read back its active-tile count (one 8-byte
+ * copy per pass) to size the launch; the pass itself is asynchronous as
+ * before.  With no active pixel they launch nothing, change nothing and
+ * return RTW_OK; rtw_accum_samples advances only when something was launched,
+ * and a timer passed to such a pass holds no interval (rtw_timer_elapsed_ms
+ * returns RTW_EINVAL until it brackets a launch again).
+ * A masked pass saves time, not memory: chunk sums go to the pixel's own
+ * position, so it needs the same workspace as an unmasked pass of its
+ * pass_spp.  Masked passes, like all passes, are not for graph replay.  A
+ * never-masked accumulator pays for none of this and keeps its bytes.
+ *
+ * Budget: after every fold (and when the budget is set or a state loaded)
+ * each active pixel with cnt samples, m = cnt / chunk full chunks and
+ * statistic {SY, SY2} is tested, in f64 with one IEEE operation per operator:
+ *   se2 = fmax(0, SY2 - SY*SY/m) / (m * (m-1) * n_c * n_c)
+ *   converged = m >= 2 && cnt >= min_spp && se2 <= tol*tol
+ * — rtw_accum_noise's per-pixel term against an absolute target on the
+ * standard error of the pixel's mean luminance.  The test runs once per fold,
+ * whatever the pass size. */
+
+/* active &= (mask != 0).  mask: HOST, W*row_count bytes.  Synchronous. */
+int rtw_accum_set_mask(rtw_accum a, const uint8_t *mask);
+/* tol > 0 sets the budget, 0 removes it (pixels already inactive stay so);
+ * applied at once if samples are accumulated.  RTW_EINVAL for a negative or
+ * non-finite tol.  Synchronous. */
+int rtw_accum_set_adaptive(rtw_accum a, double tol, uint32_t min_spp);
+/* Active pixels and the tiles that hold them.  Synchronous. */
+int rtw_accum_active(rtw_accum a, uint32_t *pixels, uint32_t *tiles);
+/* Per-pixel sample counts, HOST, W*row_count words.  Synchronous. */
+int rtw_accum_read_counts(rtw_accum a, uint32_t *cnt_out);
+/* rtw_accum_load with per-pixel counts: every cnt <= samples_done, and a
+ * multiple of the chunk or params->spp, else RTW_EINVAL and the state is
+ * untouched.  Afterwards active = (cnt == samples_done), then the budget if
+ * one is set.  A mask is not part of the saved state.  (rtw_accum_load itself:
+ * all counts = samples_done, all pixels active, then the budget.)
+ * rtw_accum_noise on a masked accumulator uses each pixel's own m, leaves
+ * pixels with m < 2 out of the sum and the divisor, and returns RTW_EINVAL if
+ * none remains. */
+int rtw_accum_load_counts(rtw_accum a, const double *sum, const double *stat, const uint32_t *cnt,
+                          uint32_t samples_done);
+
 #ifdef __cplusplus
 }
 #endif

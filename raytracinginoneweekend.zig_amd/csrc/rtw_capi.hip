@@ -722,8 +722,29 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
   if (dev != sc->device)
     return fail(RTW_EINVAL, "scene lives on device %d but the current device is %d", sc->device, dev);
   auto* ws = static_cast<unsigned char*>(workspace);
+  // A pass of a masked accumulator deals its active tiles only (TraceArgs::tile_list); with none it
+  // launches nothing and changes nothing.
+  const uint32_t* m_list = nullptr;
+  const uint64_t* m_mask = nullptr;
+  uint32_t m_tiles = 0;
+  if (acc) {
+    const int st = rtw_accum_pass_map(acc, &m_list, &m_mask, &m_tiles);
+    if (st != RTW_OK) return st;
+    if (m_list && m_tiles == 0) {  // nothing launched: the timer holds no interval (not the previous pass's)
+      if (timer) timer->recorded = false;
+      return RTW_OK;
+    }
+  }
+  auto mask_args = [&](auto& a) {
+    if (!m_list) return;
+    a.tile_list = m_list;
+    a.tile_mask = m_mask;
+    a.total_units = m_tiles * 64u * a.n_chunks;
+  };
   HIP_TRY(hipMemsetAsync(ws + L.counter_off, 0, 512, stream));  // queue head + stats
-  const int var = kernel_variant(p->precision);
+  const int var = (m_list && p->engine == RTW_ENGINE_MEGAKERNEL)
+                      ? (p->precision == RTW_PRECISION_F32 ? rtwk::kMaskedVarF32 : rtwk::kMaskedVarF64)
+                      : kernel_variant(p->precision);
   if (p->engine != RTW_ENGINE_WAVEFRONT && !rtwk::trace_variant_built((int)p->precision, var))
     return fail(RTW_EINVAL, "RTW_VARIANT=%d: trace kernel variant not built into this library", var);
   // The clustered pretest runs only in the f64 megakernel variants with
@@ -750,11 +771,13 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
     if (p->precision == RTW_PRECISION_F32) {
       rtwk::TraceArgs<float> a;
       fill_args(a, sc->v32, cam, p, ws, L, seed_adv);
+      mask_args(a);
       a.sc.n_clusters = 0u;  // f32: no clustered pretest
       st = run_wavefront<float>(a, p, ws, L, dev, lds, stream, mode == 1);
     } else {
       rtwk::TraceArgs<double> a;
       fill_args(a, sc->v64, cam, p, ws, L, seed_adv);
+      mask_args(a);
       a.sc.cluster_on = cl_on;  // (0 unless the bounce kernels were built with the clustered pretest)
       if (!cl_on) a.sc.n_clusters = 0u;
       st = run_wavefront<double>(a, p, ws, L, dev, lds, stream, mode == 1);
@@ -764,6 +787,7 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
   } else if (p->precision == RTW_PRECISION_F32) {
     rtwk::TraceArgs<float> a;
     fill_args(a, sc->v32, cam, p, ws, L, seed_adv);
+    mask_args(a);
     a.sc.n_clusters = 0u;  // f32: no clustered pretest
     total_units = a.total_units;
     const uint32_t want = (total_units + 255) / 256;
@@ -772,6 +796,7 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
   } else {
     rtwk::TraceArgs<double> a;
     fill_args(a, sc->v64, cam, p, ws, L, seed_adv);
+    mask_args(a);
     a.sc.cluster_on = cl_on;
     if (!cl_on) a.sc.n_clusters = 0u;  // nothing to stage (lds_bytes above)
     total_units = a.total_units;
@@ -1069,6 +1094,95 @@ int accum_current(rtw_accum a, const char* who) {
     return fail(RTW_EINVAL, "%s: accumulator lives on device %d but the current device is %d", who, a->device, dev);
   return RTW_OK;
 }
+
+// ---- masked state ----
+// The active-set update on stream s: act &= user mask (with_user), or act = (cnt == done) (from_cnt), then the
+// criterion when a budget is set and anything was folded; tile masks, tile list and counts follow.
+int accum_update_active(rtw_accum a, bool with_user, bool from_cnt, hipStream_t s) {
+  rtwk::ActiveArgs u;
+  u.act = a->act;
+  u.user = with_user ? a->user : nullptr;
+  u.stat = a->stat;
+  u.cnt = a->cnt;
+  u.tile_mask = a->tile_mask;
+  u.tile_list = a->tile_list;
+  u.n_active = a->n_active;
+  u.W = a->p.width;
+  u.rows = a->p.row_count;
+  u.tiles_x = a->tiles_x;
+  u.n_tiles = a->n_tiles;
+  u.chunk = a->chunk;
+  u.min_spp = a->min_spp;
+  u.thr = a->done > 0 ? a->thr : 0.0;
+  u.done = a->done;
+  u.from_cnt = from_cnt ? 1u : 0u;
+  // On a failed launch the host's counts stay those of the last completed update, which match the list the
+  // device still holds (a tile list that is a superset of the non-empty tiles deals only units the masks refuse).
+  const hipError_t e = rtwk::launch_accum_active(u, s);
+  a->counts_known = false;  // (whatever ran of it: the counts are read again before they are used)
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);
+    return fail(RTW_EHIP, "active-set kernel launch: %s", hipGetErrorString(e));
+  }
+  if (hipEventRecord(a->updated, s) != hipSuccess) {  // no event to wait for: wait here instead
+    (void)hipStreamSynchronize(s);
+    return fail(RTW_EHIP, "active-set update: event record failed");
+  }
+  return RTW_OK;
+}
+// Waits for the last update and reads its two counts (the per-pass readback).
+int accum_wait_active(rtw_accum a) {
+  if (a->counts_known) return RTW_OK;
+  HIP_TRY(hipEventSynchronize(a->updated));
+  HIP_TRY(hipMemcpy(a->host_active, a->n_active, sizeof(a->host_active), hipMemcpyDeviceToHost));
+  a->counts_known = true;
+  return RTW_OK;
+}
+// Enters the masked state: every pixel holds `done` samples and is active.
+int accum_enter_masked(rtw_accum a) {
+  if (a->masked) return RTW_OK;
+  HIP_TRY(hipDeviceSynchronize());  // every enqueued pass, whichever stream it ran on
+  a->tiles_x = (a->p.width + rtwk::kTileW - 1) / rtwk::kTileW;
+  a->n_tiles = a->tiles_x * ((a->p.row_count + rtwk::kTileH - 1) / rtwk::kTileH);
+  const size_t cnt_b = al256((size_t)a->npix * 4), act_b = al256(a->npix), mask_b = al256((size_t)a->n_tiles * 8),
+               list_b = al256((size_t)a->n_tiles * 4);
+  const size_t bytes = cnt_b + 2 * act_b + mask_b + list_b + 256;
+  void* d = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess) return fail(RTW_ENOMEM, "masked accumulator state: hipMalloc(%zu)", bytes);
+  hipEvent_t ev = nullptr;
+  if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+    (void)hipFree(d);
+    return fail(RTW_EHIP, "masked accumulator state: event creation failed");
+  }
+  auto* b = static_cast<unsigned char*>(d);
+  a->mbuf = d;
+  a->cnt = reinterpret_cast<uint32_t*>(b);
+  a->act = b + cnt_b;
+  a->user = a->act + act_b;
+  a->tile_mask = reinterpret_cast<uint64_t*>(a->user + act_b);
+  a->tile_list = reinterpret_cast<uint32_t*>(b + cnt_b + 2 * act_b + mask_b);
+  a->n_active = reinterpret_cast<uint32_t*>(b + cnt_b + 2 * act_b + mask_b + list_b);
+  a->updated = ev;
+  int st = RTW_OK;
+  if (hipMemset(d, 0, bytes) != hipSuccess || hipMemset(a->act, 1, a->npix) != hipSuccess ||
+      rtwk::launch_accum_fill_u32(a->cnt, a->npix, a->done, nullptr) != hipSuccess)
+    st = fail(RTW_EHIP, "masked accumulator state: initialisation failed");
+  if (st == RTW_OK) {
+    const double thr = a->thr;  // (entering applies no criterion: the caller does, after setting its budget)
+    a->thr = 0.0;
+    st = accum_update_active(a, false, false, nullptr);
+    a->thr = thr;
+  }
+  if (st == RTW_OK && hipDeviceSynchronize() != hipSuccess) st = fail(RTW_EHIP, "masked accumulator state: sync failed");
+  if (st != RTW_OK) {
+    (void)hipEventDestroy(ev);
+    (void)hipFree(d);
+    a->mbuf = nullptr, a->updated = nullptr;
+    return st;
+  }
+  a->masked = true;
+  return RTW_OK;
+}
 }  // namespace
 
 bool rtw_accum_size_params(const rtw_params* p, uint32_t n, rtw_params* pp) { return accum_size_params(p, n, pp); }
@@ -1101,9 +1215,34 @@ int rtw_accum_pass_fold(rtw_accum a, const rtw_params* pp, unsigned char* ws, hi
   f.npix = a->npix;
   f.n_chunks = n_chunks(pp);
   f.n_full = pp->spp / a->chunk;  // (a last chunk of fewer samples: into the sum only)
+  if (a->masked) {  // active pixels only, then the criterion and the next pass's tile list
+    rtwk::MaskedFoldArgs m;
+    m.f = f;
+    m.act = a->act;
+    m.cnt = a->cnt;
+    m.pass_spp = pp->spp;
+    const hipError_t e = rtwk::launch_accum_fold_masked(m, s);
+    if (e != hipSuccess) return fail(RTW_EHIP, "masked fold kernel launch: %s", hipGetErrorString(e));
+    // The fold is enqueued: the sums and counts hold the pass, so `done` does from here on, whatever becomes
+    // of the update below.  Should the update fail to launch, the device keeps the previous masks, list and
+    // counts, which name a superset of the active pixels: a later pass stays correct (accum_update_active).
+    a->done += pp->spp;
+    return accum_update_active(a, false, false, s);
+  }
   const hipError_t e = rtwk::launch_accum_fold(f, s);
   if (e != hipSuccess) return fail(RTW_EHIP, "fold kernel launch: %s", hipGetErrorString(e));
   a->done += pp->spp;
+  return RTW_OK;
+}
+
+int rtw_accum_pass_map(rtw_accum a, const uint32_t** tile_list, const uint64_t** tile_mask, uint32_t* active_tiles) {
+  *tile_list = nullptr, *tile_mask = nullptr, *active_tiles = 0;
+  if (!a->masked) return RTW_OK;
+  const int st = accum_wait_active(a);
+  if (st != RTW_OK) return st;
+  *tile_list = a->tile_list;
+  *tile_mask = a->tile_mask;
+  *active_tiles = a->host_active[0];
   return RTW_OK;
 }
 
@@ -1123,7 +1262,7 @@ int rtw_accum_create(const rtw_params* p, rtw_accum* out) {
   a->npix = p->row_count * p->width;
   // sub-buffers 256-B aligned (the kernels read stat as double2)
   const size_t sum_b = al256((size_t)a->npix * 24), stat_b = al256((size_t)a->npix * 16);
-  const size_t bytes = sum_b + stat_b + (rtwk::kNoiseGrid + 1) * sizeof(double);
+  const size_t bytes = sum_b + stat_b + 2 * (rtwk::kNoiseGrid + 1) * sizeof(double);  // (x2: the masked noise's pixel counts)
   void* d = nullptr;
   if (hipMalloc(&d, bytes) != hipSuccess) {
     delete a;
@@ -1144,6 +1283,8 @@ int rtw_accum_create(const rtw_params* p, rtw_accum* out) {
 int rtw_accum_destroy(rtw_accum a) {
   if (!a) return RTW_OK;
   if (a->sum) (void)hipFree(a->sum);
+  if (a->mbuf) (void)hipFree(a->mbuf);
+  if (a->updated) (void)hipEventDestroy(a->updated);
   delete a;
   return RTW_OK;
 }
@@ -1176,6 +1317,17 @@ int rtw_accum_resolve_device(rtw_accum a, uint8_t* d_rgb, float* d_mean, void* s
   if (st != RTW_OK) return st;
   if (!d_rgb) return fail(RTW_EINVAL, "d_rgb is NULL");
   if (a->done == 0) return fail(RTW_EINVAL, "rtw_accum_resolve_device: no sample accumulated yet");
+  if (a->masked) {  // each pixel by its own count
+    rtwk::ResolveCntArgs r;
+    r.sum = a->sum;
+    r.cnt = a->cnt;
+    r.rgb = d_rgb;
+    r.mean = d_mean;
+    r.npix = a->npix;
+    const hipError_t e = rtwk::launch_accum_resolve_cnt(r, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(RTW_EHIP, "resolve kernel launch: %s", hipGetErrorString(e));
+    return RTW_OK;
+  }
   rtwk::ResolveArgs r;
   r.sum = a->sum;
   r.rgb = d_rgb;
@@ -1191,6 +1343,24 @@ int rtw_accum_noise(rtw_accum a, void* stream, double* noise) {
   const int st = accum_current(a, "rtw_accum_noise");
   if (st != RTW_OK) return st;
   if (!noise) return fail(RTW_EINVAL, "noise is NULL");
+  if (a->masked) {  // each pixel's own m; pixels with m < 2 left out
+    rtwk::NoiseCntArgs n;
+    n.stat = a->stat;
+    n.cnt = a->cnt;
+    n.part = a->noise;
+    n.npix = a->npix;
+    n.chunk = a->chunk;
+    auto s = static_cast<hipStream_t>(stream);
+    const hipError_t e = rtwk::launch_accum_noise_cnt(n, s);
+    if (e != hipSuccess) return fail(RTW_EHIP, "noise kernel launch: %s", hipGetErrorString(e));
+    double out[2] = {0.0, 0.0};
+    HIP_TRY(hipMemcpyAsync(&out[0], a->noise + rtwk::kNoiseGrid, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&out[1], a->noise + 2 * rtwk::kNoiseGrid + 1, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out[1] < 1.0) return fail(RTW_EINVAL, "rtw_accum_noise: no pixel holds two full chunks, the estimate needs 2");
+    *noise = out[0];
+    return RTW_OK;
+  }
   const uint32_t m = a->done / a->chunk;
   if (m < 2) return fail(RTW_EINVAL, "rtw_accum_noise: %u full chunks accumulated, the estimate needs 2", m);
   rtwk::NoiseArgs n;
@@ -1228,7 +1398,102 @@ int rtw_accum_load(rtw_accum a, const double* sum, const double* stat, uint32_t 
   HIP_TRY(hipMemcpy(a->sum, sum, (size_t)a->npix * 24, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(a->stat, stat, (size_t)a->npix * 16, hipMemcpyHostToDevice));
   a->done = samples_done;
+  if (a->masked) {  // all counts = samples_done, all pixels active; then the budget's criterion, as after a fold
+    if (rtwk::launch_accum_fill_u32(a->cnt, a->npix, samples_done, nullptr) != hipSuccess)
+      return fail(RTW_EHIP, "rtw_accum_load: count fill failed");
+    const int us = accum_update_active(a, false, true, nullptr);
+    if (us != RTW_OK) return us;
+    HIP_TRY(hipDeviceSynchronize());
+  }
   return RTW_OK;
+}
+
+int rtw_accum_set_mask(rtw_accum a, const uint8_t* mask) {
+  if (!a || !mask) return fail(RTW_EINVAL, "rtw_accum_set_mask: accumulator/mask is NULL");
+  int st = accum_current(a, "rtw_accum_set_mask");
+  if (st != RTW_OK) return st;
+  st = accum_enter_masked(a);
+  if (st != RTW_OK) return st;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(a->user, mask, a->npix, hipMemcpyHostToDevice));
+  st = accum_update_active(a, true, false, nullptr);
+  if (st != RTW_OK) return st;
+  return accum_wait_active(a);
+}
+
+int rtw_accum_set_adaptive(rtw_accum a, double tol, uint32_t min_spp) {
+  if (!a) return fail(RTW_EINVAL, "rtw_accum_set_adaptive: accumulator is NULL");
+  if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(RTW_EINVAL, "rtw_accum_set_adaptive: tol must be finite and >= 0");
+  int st = accum_current(a, "rtw_accum_set_adaptive");
+  if (st != RTW_OK) return st;
+  if (tol == 0.0) {  // no budget from here on; what has gone inactive stays so
+    a->tol = a->thr = 0.0;
+    a->min_spp = 0;
+    return RTW_OK;
+  }
+  st = accum_enter_masked(a);
+  if (st != RTW_OK) return st;
+  a->tol = tol;
+  a->thr = tol * tol;
+  a->min_spp = min_spp;
+  if (a->done == 0) return RTW_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  st = accum_update_active(a, false, false, nullptr);
+  if (st != RTW_OK) return st;
+  return accum_wait_active(a);
+}
+
+int rtw_accum_active(rtw_accum a, uint32_t* pixels, uint32_t* tiles) {
+  if (!a || !pixels || !tiles) return fail(RTW_EINVAL, "rtw_accum_active: accumulator/pixels/tiles is NULL");
+  int st = accum_current(a, "rtw_accum_active");
+  if (st != RTW_OK) return st;
+  if (!a->masked) {
+    *pixels = a->npix;
+    *tiles = ((a->p.width + rtwk::kTileW - 1) / rtwk::kTileW) * ((a->p.row_count + rtwk::kTileH - 1) / rtwk::kTileH);
+    return RTW_OK;
+  }
+  st = accum_wait_active(a);
+  if (st != RTW_OK) return st;
+  *tiles = a->host_active[0];
+  *pixels = a->host_active[1];
+  return RTW_OK;
+}
+
+int rtw_accum_read_counts(rtw_accum a, uint32_t* cnt_out) {
+  if (!a || !cnt_out) return fail(RTW_EINVAL, "rtw_accum_read_counts: accumulator/cnt_out is NULL");
+  const int st = accum_current(a, "rtw_accum_read_counts");
+  if (st != RTW_OK) return st;
+  if (!a->masked) {
+    std::fill(cnt_out, cnt_out + a->npix, a->done);
+    return RTW_OK;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(cnt_out, a->cnt, (size_t)a->npix * 4, hipMemcpyDeviceToHost));
+  return RTW_OK;
+}
+
+int rtw_accum_load_counts(rtw_accum a, const double* sum, const double* stat, const uint32_t* cnt,
+                          uint32_t samples_done) {
+  if (!a || !sum || !stat || !cnt) return fail(RTW_EINVAL, "rtw_accum_load_counts: accumulator/sum/stat/cnt is NULL");
+  int st = accum_current(a, "rtw_accum_load_counts");
+  if (st != RTW_OK) return st;
+  if (samples_done > a->p.spp || (samples_done % a->chunk != 0 && samples_done != a->p.spp))
+    return fail(RTW_EINVAL, "rtw_accum_load_counts: %u samples is not a multiple of the chunk %u nor the frame's %u",
+                samples_done, a->chunk, a->p.spp);
+  for (uint32_t i = 0; i < a->npix; ++i)
+    if (cnt[i] > samples_done || (cnt[i] % a->chunk != 0 && cnt[i] != a->p.spp))
+      return fail(RTW_EINVAL, "rtw_accum_load_counts: pixel %u holds %u samples: above the %u done, or off the chunk %u",
+                  i, cnt[i], samples_done, a->chunk);
+  st = accum_enter_masked(a);
+  if (st != RTW_OK) return st;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(a->sum, sum, (size_t)a->npix * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(a->stat, stat, (size_t)a->npix * 16, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(a->cnt, cnt, (size_t)a->npix * 4, hipMemcpyHostToDevice));
+  a->done = samples_done;
+  st = accum_update_active(a, false, true, nullptr);
+  if (st != RTW_OK) return st;
+  return accum_wait_active(a);
 }
 
 }  // extern "C"

@@ -23,6 +23,21 @@ struct rtw_accum_s {
   uint32_t done = 0;   // samples folded: a multiple of chunk, or p.spp (host state, advanced at enqueue)
   uint32_t npix = 0;
   double *sum = nullptr, *stat = nullptr, *noise = nullptr;
+  // Masked state, entered by the first rtw_accum_set_mask / set_adaptive / load_counts and
+  // never left: a second allocation `mbuf` with cnt [npix] u32 | act [npix] u8 | user [npix] u8 (the staged
+  // mask of set_mask) | tile_mask [n_tiles] u64 | tile_list [n_tiles] u32 | n_active {tiles, pixels}.
+  bool masked = false;
+  void* mbuf = nullptr;
+  uint32_t* cnt = nullptr;
+  uint8_t *act = nullptr, *user = nullptr;
+  uint64_t* tile_mask = nullptr;
+  uint32_t *tile_list = nullptr, *n_active = nullptr;
+  uint32_t tiles_x = 0, n_tiles = 0;
+  double tol = 0.0, thr = 0.0;   // the budget: thr = tol * tol, 0 = none
+  uint32_t min_spp = 0;
+  hipEvent_t updated = nullptr;  // recorded after the last active-set update
+  bool counts_known = false;     // host_active holds that update's counts
+  uint32_t host_active[2] = {0, 0};  // {active tiles, active pixels}
 };
 
 int rtw_fail(int status, const char* fmt, ...);  // sets rtw_last_error, returns status
@@ -43,3 +58,6 @@ int rtw_timer_mark(rtw_timer t, hipStream_t s, bool start);
 bool rtw_accum_size_params(const rtw_params* p, uint32_t n, rtw_params* pp);
 int rtw_accum_pass_begin(rtw_accum a, uint32_t pass_spp, rtw_params* pp, uint64_t* seed_adv);
 int rtw_accum_pass_fold(rtw_accum a, const rtw_params* pp, unsigned char* ws, hipStream_t s);
+// The take's map for a pass of `a`: both null for a never-masked accumulator; else the device tile list and
+// masks and the active tile count, after waiting for the previous active-set update (one 8-byte readback).
+int rtw_accum_pass_map(rtw_accum a, const uint32_t** tile_list, const uint64_t** tile_mask, uint32_t* active_tiles);

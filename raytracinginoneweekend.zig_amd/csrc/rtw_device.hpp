@@ -100,6 +100,9 @@ constexpr int kVarUnitBase = 67108864;
 // lane's own rejection loop after the cooperative pass, not inside it
 // (measurement: 4.8 % slower, profiles/r06/mk_var_ab.txt).
 constexpr int kVarLaneDisk = 134217728;
+// kVarMasked: a masked accumulator pass — the take maps the dealt tile through
+// TraceArgs::tile_list and skips the units of inactive pixels (tile_mask).
+constexpr int kVarMasked = 268435456;
 // f64 pretest over spatial clusters of narrow spheres (SceneView ccull...):
 // a wave skips a cluster's member pretests when every lane's line provably
 // misses the cluster's bounding sphere.

@@ -198,6 +198,15 @@ std::vector<uint8_t> render(const Camera& cam, const Hittable& world, const Rend
 // with the frame, or earlier once the frame's noise (rtw_accum_noise) is
 // <= max_noise (0: never).  Returns the last image; *samples_used the samples
 // it holds.  Without an early stop the image is the one-shot render's.
+// adaptive (optional): a per-pixel noise budget (rtw_accum_set_adaptive,
+// DESIGN.md §13) — pixels stop one by one as the standard error of their mean
+// luminance reaches pixel_noise, the loop also ends when no pixel is active,
+// and each pixel of the image is the one-shot render's with its own count.
+struct AdaptiveOpts {
+  double pixel_noise = 0.0;            // > 0: the budget (absolute)
+  uint32_t min_spp = 0;                // no pixel stops below this many samples
+  std::vector<uint32_t>* counts = nullptr;  // out (optional): the per-pixel sample counts of the returned image
+};
 struct PassInfo {
   uint32_t pass;     // 1, 2, ...
   uint32_t samples;  // accumulated so far
@@ -206,7 +215,10 @@ struct PassInfo {
 using PassFn = std::function<void(const PassInfo&, const std::vector<uint8_t>& rgb)>;
 std::vector<uint8_t> renderProgressive(const rtw_camera& cam, const rtw_params& p, uint32_t pass_spp,
                                        const FlatScene* scene, const rtw_world_desc* world, double max_noise,
-                                       const PassFn& on_pass, uint32_t* samples_used);
+                                       const PassFn& on_pass, uint32_t* samples_used,
+                                       const AdaptiveOpts* adaptive = nullptr);
+// The sample-count map as a binary PGM: 8-bit when the largest count fits, else 16-bit (big-endian).
+void writeCountsPGM(const std::string& path, const std::vector<uint32_t>& counts, uint32_t w, uint32_t h);
 
 void writePPM(const std::string& path, const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h);
 

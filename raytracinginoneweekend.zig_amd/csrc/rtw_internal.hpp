@@ -81,6 +81,12 @@ struct TraceArgs {
   double* partial;                // [n_chunks][row_count*W][3] chunk sums
   uint32_t* counter;              // work-queue head (zeroed before launch)
   unsigned long long* stats;      // counts {samples, segments, skipped} [0..2]; phase cycles [8..13]
+  // A masked accumulator pass (rtw_accum.hip): the launch deals only the tiles that hold an
+  // active pixel, total_units = active tiles * 64 * n_chunks, and the take maps a dealt tile through
+  // tile_list to the frame's tile and skips a unit whose pixel's bit of tile_mask is clear, as it skips
+  // the padding units of edge tiles.  Both null in every other render.
+  const uint32_t* tile_list;      // [active tiles] frame tile index, ascending
+  const uint64_t* tile_mask;      // [frame tiles] bit l: pixel l of the tile (l = 8 * row + column) is active
 };
 
 struct FinalizeArgs {
@@ -138,6 +144,14 @@ constexpr size_t kUnitBaseLdsBytesPerWave = 3 * 64 * 8;
 #define RTW_DEFAULT_VAR_F32 (8 + 512 + 131072 + 262144 + 524288 + 16777216)  // 17695240
 #endif
 constexpr int kDefaultVarF32 = RTW_DEFAULT_VAR_F32;
+// rtw_device.hpp kVarMasked: the take reads TraceArgs::tile_list / tile_mask (a masked accumulator pass).
+// Built for the default variant of each precision, product mode only; launched only with both pointers set.
+constexpr int kVarMaskedBit = 268435456;
+// The masked instantiation of each precision.  f32 is built for 4 waves per SIMD (VAR bit 2, 128 VGPRs) where
+// the unmasked kernel has 5 (bit 3, 96): at 96 the map's two loads spilled (32 B of scratch against the unmasked
+// kernel's 16; decoding per batch, kVarBatchDecode, spilled 64).
+constexpr int kMaskedVarF64 = kDefaultVarF64 | kVarMaskedBit;
+constexpr int kMaskedVarF32 = ((kDefaultVarF32 & ~8) | 4) | kVarMaskedBit;
 bool trace_variant_built(int precision, int var);
 constexpr int kTraceBlock = 256;
 
@@ -169,7 +183,48 @@ struct NoiseArgs {
   double m;            // full chunks folded (>= 2)
   double denom;        // m (m - 1) n_c^2
 };
+// Masked accumulator: per-pixel sample counts and an active set.  act[pix] != 0 while the
+// pixel has received every sample so far and has not converged; the tile masks and the ascending list of
+// non-empty tiles are derived from it after every change (launch_accum_active).
+struct MaskedFoldArgs {
+  FoldArgs f;
+  const uint8_t* act;  // [npix]
+  uint32_t* cnt;       // [npix] samples folded into the pixel
+  uint32_t pass_spp;
+};
+struct ActiveArgs {
+  uint8_t* act;            // [npix]
+  const uint8_t* user;     // [npix] optional: act &= (user != 0) (rtw_accum_set_mask)
+  const double* stat;      // [npix][2]
+  const uint32_t* cnt;     // [npix]
+  uint64_t* tile_mask;     // [n_tiles]
+  uint32_t* tile_list;     // [n_tiles]
+  uint32_t* n_active;      // {active tiles, active pixels}
+  uint32_t W, rows, tiles_x, n_tiles;
+  uint32_t chunk, min_spp;
+  double thr;              // tol * tol; <= 0: no criterion
+  uint32_t done;           // with from_cnt: act = (cnt == done) first (rtw_accum_load_counts)
+  uint32_t from_cnt;
+};
+struct ResolveCntArgs {
+  const double* sum;
+  const uint32_t* cnt;
+  uint8_t* rgb;
+  float* mean;
+  uint32_t npix;
+};
+struct NoiseCntArgs {
+  const double* stat;
+  const uint32_t* cnt;
+  double* part;   // [kNoiseGrid] sums, [kNoiseGrid] = the noise; then [kNoiseGrid] pixel counts, [2 kNoiseGrid + 1] = pixels used
+  uint32_t npix, chunk;
+};
 hipError_t launch_accum_fold(const FoldArgs& a, hipStream_t s);
+hipError_t launch_accum_fold_masked(const MaskedFoldArgs& a, hipStream_t s);
+hipError_t launch_accum_active(const ActiveArgs& a, hipStream_t s);
+hipError_t launch_accum_resolve_cnt(const ResolveCntArgs& a, hipStream_t s);
+hipError_t launch_accum_noise_cnt(const NoiseCntArgs& a, hipStream_t s);
+hipError_t launch_accum_fill_u32(uint32_t* p, uint32_t n, uint32_t v, hipStream_t s);
 hipError_t launch_accum_resolve(const ResolveArgs& a, hipStream_t s);
 hipError_t launch_accum_noise(const NoiseArgs& a, hipStream_t s);
 // Per-wave LDS slots of coop_reject (rtw_trace.hip CoopSlots: 64 x u64 + 64 x u32).

@@ -5,11 +5,17 @@
 //   rtw_render [--scene 1..7] [--width W] [--aspect A|W:H] [--spp N] [--depth D]
 //              [--seed S] [--precision f64|f32] [--engine megakernel|wavefront]
 //              [--chunk C] [--image earth.png] [--out out.ppm]
-//              [--pass-spp N [--preview-dir DIR] [--max-noise X]]
+//              [--pass-spp N [--preview-dir DIR] [--max-noise X]
+//                            [--pixel-noise X [--min-spp N] [--spp-map FILE]]]
 // --pass-spp N renders the frame progressively, N samples per pass (a multiple
 // of the chunk): the same --out bytes as without it.  --preview-dir DIR writes
 // the image after every pass to DIR/pass_NNNN.ppm; --max-noise X stops once the
 // frame's noise estimate (rtw_accum_noise) is <= X and prints the samples used.
+// --pixel-noise X samples adaptively: a pixel stops once the standard error of
+// its mean luminance is <= X (and it holds --min-spp samples), the run ends
+// when every pixel has stopped or at --spp, and each pixel of --out is the
+// one-shot render's with that pixel's own sample count; --spp-map FILE writes
+// the counts as a binary PGM (8-bit, or 16-bit when a count exceeds 255).
 // Defaults are the reference's: scene 6 (main.zig:313) with that scene's own
 // size, spp, camera and background (main.zig:316-362); --width/--aspect/--spp
 // override them.  Scenes 4 and 7 need --image (assets/sekaichizu.png).
@@ -110,10 +116,10 @@ static std::shared_ptr<rtw::Image> loadPNG(const std::string& path) {
 int main(int argc, char** argv) {
   uint32_t scene = 6;  // main.zig:313
   uint32_t width = 0, spp = 0, depth = 50, chunk = 0, precision = RTW_PRECISION_F64, engine = RTW_ENGINE_MEGAKERNEL;
-  uint32_t pass_spp = 0;
-  double aspect = 0, max_noise = 0;
+  uint32_t pass_spp = 0, min_spp = 0;
+  double aspect = 0, max_noise = 0, pixel_noise = 0;
   uint64_t seed = 42;
-  std::string out = "out.ppm", image_path, preview_dir;
+  std::string out = "out.ppm", image_path, preview_dir, spp_map;
   for (int i = 1; i + 1 < argc; i += 2) {
     const std::string k = argv[i];
     const char* v = argv[i + 1];
@@ -131,13 +137,20 @@ int main(int argc, char** argv) {
     else if (k == "--pass-spp") pass_spp = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--preview-dir") preview_dir = v;
     else if (k == "--max-noise") max_noise = std::atof(v);
+    else if (k == "--pixel-noise") pixel_noise = std::atof(v);
+    else if (k == "--min-spp") min_spp = (uint32_t)std::strtoul(v, nullptr, 10);
+    else if (k == "--spp-map") spp_map = v;
     else {
       std::fprintf(stderr, "unknown option %s\n", k.c_str());
       return 2;
     }
   }
-  if (pass_spp == 0 && (!preview_dir.empty() || max_noise > 0)) {
-    std::fprintf(stderr, "--preview-dir and --max-noise need --pass-spp\n");
+  if (pass_spp == 0 && (!preview_dir.empty() || max_noise > 0 || pixel_noise > 0)) {
+    std::fprintf(stderr, "--preview-dir, --max-noise and --pixel-noise need --pass-spp\n");
+    return 2;
+  }
+  if (!(pixel_noise > 0) && (min_spp || !spp_map.empty())) {
+    std::fprintf(stderr, "--min-spp and --spp-map need --pixel-noise\n");
     return 2;
   }
   try {
@@ -152,6 +165,9 @@ int main(int argc, char** argv) {
     rtw::Random rng = rtw::Random::init(seed);                           // main.zig:300-301
     std::vector<uint8_t> rgb((size_t)W * H * 3);
     uint32_t used = S;
+    std::vector<uint32_t> counts;
+    rtw::AdaptiveOpts adaptive;
+    adaptive.pixel_noise = pixel_noise, adaptive.min_spp = min_spp, adaptive.counts = &counts;
     // --pass-spp: the frame through the accumulator, a preview per pass
     auto progressive = [&](const rtw_params& p, const rtw::FlatScene* fs, const rtw_world_desc* wd) {
       if (!preview_dir.empty()) (void)mkdir(preview_dir.c_str(), 0777);  // (an existing directory is fine)
@@ -163,7 +179,7 @@ int main(int argc, char** argv) {
                                       std::snprintf(name, sizeof(name), "/pass_%04u.ppm", i.pass);
                                       rtw::writePPM(preview_dir + name, img, W, H);
                                     },
-                                    &used);
+                                    &used, pixel_noise > 0 ? &adaptive : nullptr);
     };
     rtw_params p;
     std::memset(&p, 0, sizeof(p));
@@ -210,6 +226,13 @@ int main(int argc, char** argv) {
     }
     rtw::writePPM(out, rgb, W, H);  // main.zig:405
     if (max_noise > 0) std::fprintf(stderr, "noise budget %g: %u of %u samples used\n", max_noise, used, S);
+    if (pixel_noise > 0) {
+      uint64_t total = 0;
+      for (uint32_t c : counts) total += c;
+      std::fprintf(stderr, "pixel noise budget %g: %.2f samples per pixel on average, %u at most\n", pixel_noise,
+                   (double)total / (double)counts.size(), used);
+      if (!spp_map.empty()) rtw::writeCountsPGM(spp_map, counts, W, H);
+    }
     std::fprintf(stderr, "wrote %s (scene %u, %ux%u, %u spp)\n", out.c_str(), scene, W, H, used);
   } catch (const rtw::Error& e) {
     std::fprintf(stderr, "rtw_render: %s (status %d)\n", e.what(), e.status);

@@ -120,11 +120,27 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
   // (tile x, tile y, chunk) of the wave's current unit batch and of a newly
   // fetched one (VAR kVarBatchDecode; wave-uniform).
   uint32_t cur_tx = 0, cur_ty = 0, cur_c = 0, nb_tx = 0, nb_ty = 0, nb_c = 0;
-  auto decode_batch = [&](uint32_t base, uint32_t& tx, uint32_t& ty, uint32_t& c) {
+  // VAR kVarMasked: a masked accumulator pass.  The dealt tile index counts the
+  // active tiles only, tile_list gives the frame's tile, and a unit whose
+  // pixel's bit of the tile's mask is clear is skipped as a padding unit is.
+  // The two instantiations that are built (kMaskedVarF64 / kMaskedVarF32) take
+  // the per-lane decode below.  The kVarBatchDecode form of the map
+  // (decode_batch, cur_mask / nb_mask) is written out for an A/B build that
+  // combines the two bits; no library builds it and no test runs it (an f32
+  // build of it spilled 64 B of scratch: rtw_internal.hpp).
+  constexpr bool MASKED = (VAR & kVarMasked) != 0;
+  uint64_t cur_mask = 0, nb_mask = 0;  // (kVarBatchDecode: the batch's tile mask, wave-uniform)
+  auto decode_batch = [&](uint32_t base, uint32_t& tx, uint32_t& ty, uint32_t& c, uint64_t& tmask) {
     const uint32_t b64 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 6));
     const uint32_t nc = RTW_KA(n_chunks), txs = RTW_KA(tiles_x);
-    const uint32_t tile = b64 / nc;
+    uint32_t tile = b64 / nc;
     c = b64 - tile * nc;
+    if constexpr (MASKED) {  // (a batch past the queue's end names no tile: its units are refused below)
+      const bool in_q = (b64 << 6) < RTW_KA(total_units);
+      const auto* ka = opaque(kargs<R>());
+      tile = in_q ? ka->tile_list[tile] : 0u;
+      tmask = in_q ? ka->tile_mask[tile] : 0ull;
+    }
     ty = tile / txs;
     tx = tile - ty * txs;
   };
@@ -146,7 +162,7 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
         // A batch is 64 aligned units = one (tile, chunk): decoded once per
         // batch (wave-uniform) instead of two integer divisions per refill.
         if (n > rem)  // (a dealt batch is a 64-aligned batch in every order)
-          decode_batch(dealt_unit(base2, *opaque(kargs<R>())) & ~63u, nb_tx, nb_ty, nb_c);
+          decode_batch(dealt_unit(base2, *opaque(kargs<R>())) & ~63u, nb_tx, nb_ty, nb_c, nb_mask);
       }
       if (need) {
         const uint32_t unit = rank < rem ? qnext + rank : base2 + (rank - rem);
@@ -156,22 +172,34 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
           uint32_t tx, ty, c;
           const uint32_t du = dealt_unit(unit, *opaque(kargs<R>()));
           const uint32_t l = du & 63u;
+          bool active = true;  // (kVarMasked)
           if constexpr ((VAR & kVarBatchDecode) != 0) {
             const bool in_cur = rank < rem;
             tx = in_cur ? cur_tx : nb_tx;
             ty = in_cur ? cur_ty : nb_ty;
             c = in_cur ? cur_c : nb_c;
+            if constexpr (MASKED) active = (((in_cur ? cur_mask : nb_mask) >> l) & 1ull) != 0;
           } else {
             const uint32_t units_per_tile = kTileW * kTileH * RTW_KA(n_chunks);
-            const uint32_t tile = rtwm::udiv(du, RTW_KA(upt_m), RTW_KA(upt_sh));  // du / units_per_tile
+            uint32_t tile = rtwm::udiv(du, RTW_KA(upt_m), RTW_KA(upt_sh));  // du / units_per_tile
             const uint32_t r = du - tile * units_per_tile;
             c = r >> 6;
+            if constexpr (MASKED) {  // (unit < total_units: tile < the list's length)
+              // Both pointers are read from the kernel argument here, whatever VAR bit 1024 says: held in
+              // SGPRs for the whole kernel they cost the f32 variant spills.  The frame has < 2^24 tiles
+              // (validate: <= 2^24 pixels), so the masked indices let the loads take a 32-bit offset.
+              const auto* ka = opaque(kargs<R>());
+              tile = ka->tile_list[tile & 0xFFFFFFu] & 0xFFFFFFu;
+              // (the 32-bit half of the mask that holds bit l: one register less than the u64)
+              const uint32_t half = reinterpret_cast<const uint32_t*>(ka->tile_mask)[2u * tile + (l >> 5)];
+              active = ((half >> (l & 31u)) & 1u) != 0;
+            }
             ty = rtwm::udiv(tile, RTW_KA(tx_m), RTW_KA(tx_sh));  // tile / tiles_x
             tx = tile - ty * RTW_KA(tiles_x);
           }
           const uint32_t px = tx * kTileW + (l & 7u);
           const uint32_t ly = ty * kTileH + (l >> 3);
-          if (px < RTW_KA(W) && ly < RTW_KA(row_count)) {  // else: padding unit, take another
+          if (px < RTW_KA(W) && ly < RTW_KA(row_count) && active) {  // else: padding or inactive unit, take another
             have_unit = true;
             L.s = c * RTW_KA(chunk);
             if constexpr (HOME) {
@@ -203,7 +231,7 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
       if (n > rem) {
         qnext = base2 + (n - rem);
         qend = base2 + kBatch;
-        if constexpr ((VAR & kVarBatchDecode) != 0) cur_tx = nb_tx, cur_ty = nb_ty, cur_c = nb_c;
+        if constexpr ((VAR & kVarBatchDecode) != 0) cur_tx = nb_tx, cur_ty = nb_ty, cur_c = nb_c, cur_mask = nb_mask;
       } else {
         qnext += n;
       }
@@ -509,6 +537,7 @@ constexpr int default_var() {
 
 bool trace_variant_built(int precision, int var) {
   if (var == (precision == 1 ? kDefaultVarF32 : kDefaultVarF64)) return true;
+  if (var == (precision == 1 ? kMaskedVarF32 : kMaskedVarF64)) return true;
 #ifdef RTW_MEASURE
   switch (var) {
 #define RTW_CASE(v) case v:
@@ -525,6 +554,12 @@ static hipError_t launch_trace(const TraceArgs<R>& a, uint32_t grid, size_t lds,
                                int var) {
   if (var == default_var<F32>()) {
     launch_var<R, F32, default_var<F32>()>(a, grid, lds, s, mode);
+    return hipGetLastError();
+  }
+  constexpr int kMaskedVar = F32 ? kMaskedVarF32 : kMaskedVarF64;
+  if (var == kMaskedVar) {  // a masked accumulator pass (product mode only)
+    if (mode != 0 || !a.tile_list || !a.tile_mask) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((trace_kernel<R, F32, 0, kMaskedVar>), dim3(grid), dim3(kTraceBlock), lds, s, a);
     return hipGetLastError();
   }
 #ifdef RTW_MEASURE
@@ -565,6 +600,8 @@ int trace_blocks_per_cu(int precision, size_t lds, int var) {
   int nb = 0;
   if (precision == 1 && var == kDefaultVarF32) nb = occ<float, true, kDefaultVarF32>(lds);
   else if (precision != 1 && var == kDefaultVarF64) nb = occ<double, false, kDefaultVarF64>(lds);
+  else if (precision == 1 && var == kMaskedVarF32) nb = occ<float, true, kMaskedVarF32>(lds);
+  else if (precision != 1 && var == kMaskedVarF64) nb = occ<double, false, kMaskedVarF64>(lds);
 #ifdef RTW_MEASURE
   else switch (var) {
 #define RTW_CASE(v) \

@@ -102,8 +102,20 @@ __device__ __forceinline__ bool take_unit(const TraceArgs<R>& A, uint32_t batch,
       if (raw >= A.total_units) {
         need = false;  // queue exhausted: the slot retires
       } else {
-        const uint32_t u = dealt_unit(raw, A);
-        if (decode_unit(A, u, px, ly, c)) {
+        uint32_t u = dealt_unit(raw, A);
+        // A masked accumulator pass (TraceArgs::tile_list, wave-uniform null check): the dealt unit's tile
+        // counts the active tiles.  The slot keeps the unit of the FRAME's numbering (the mapped tile), so
+        // every later decode_unit is the unmasked one; the unit of an inactive pixel is refused here, as a
+        // padding unit is.  (raw < total_units: the tile index is inside the list.)
+        bool active = true;
+        if (A.tile_list != nullptr) {
+          const uint32_t upt = kTileW * kTileH * A.n_chunks;
+          const uint32_t tile = rtwm::udiv(u, A.upt_m, A.upt_sh), r = u - tile * upt;
+          const uint32_t ft = A.tile_list[tile];
+          active = ((A.tile_mask[ft] >> (r & 63u)) & 1ull) != 0;
+          u = ft * upt + r;
+        }
+        if (active && decode_unit(A, u, px, ly, c)) {
           need = false;
           got = true;
           unit = u;

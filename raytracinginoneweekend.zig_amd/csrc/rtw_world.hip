@@ -892,12 +892,26 @@ __global__ void __launch_bounds__(kWorldBlock, OCC) world_kernel(WorldArgs A) {
         } else {
           const uint32_t unit = dealt_unit(raw, WKA(t));
           const uint32_t units_per_tile = kTileW * kTileH * WKA(t.n_chunks);
-          const uint32_t tile = rtwm::udiv(unit, WKA(t.upt_m), WKA(t.upt_sh));  // unit / units_per_tile
+          uint32_t tile = rtwm::udiv(unit, WKA(t.upt_m), WKA(t.upt_sh));  // unit / units_per_tile
           const uint32_t r = unit - tile * units_per_tile;
+          // A masked accumulator pass (TraceArgs::tile_list; wave-uniform null check): the dealt tile
+          // counts the active tiles, and the unit of an inactive pixel is skipped as a padding unit is.
+          // Product mode only (accumulator passes run in no other): the counts and phase builds keep
+          // their code.
+          bool active = true;
+          if constexpr (MODE == 0) {
+            const uint32_t* tile_list = WKA(t.tile_list);
+            if (tile_list != nullptr) {  // (raw < total_units: tile < the list's length)
+              tile = tile_list[tile];
+              const uint32_t l = r & 63u;
+              const uint32_t half = reinterpret_cast<const uint32_t*>(WKA(t.tile_mask))[2u * tile + (l >> 5)];
+              active = ((half >> (l & 31u)) & 1u) != 0;
+            }
+          }
           const uint32_t tiles_x = WKA(t.tiles_x);
           const uint32_t ty = rtwm::udiv(tile, WKA(t.tx_m), WKA(t.tx_sh)), tx = tile - ty * tiles_x;
           const uint32_t px = tx * kTileW + ((r & 63u) & 7u), ly = ty * kTileH + ((r & 63u) >> 3);
-          if (px < WKA(t.W) && ly < WKA(t.row_count)) {
+          if (px < WKA(t.W) && ly < WKA(t.row_count) && active) {
             have_unit = true;
             L.s = (r >> 6) * WKA(t.chunk);
             TL_C[lid] = r >> 6;

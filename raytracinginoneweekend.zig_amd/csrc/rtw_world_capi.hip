@@ -201,6 +201,19 @@ int world_launch(rtw_world w, const rtw_camera* cam, const rtw_params* p, void* 
   if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
   if (dev != w->device) return rtw_fail(RTW_EINVAL, "world lives on device %d, current is %d", w->device, dev);
   auto* wsb = static_cast<unsigned char*>(ws);
+  // A pass of a masked accumulator deals its active tiles only; with none it launches nothing.
+  const uint32_t* m_list = nullptr;
+  const uint64_t* m_mask = nullptr;
+  uint32_t m_tiles = 0;
+  if (acc) {
+    const int st = rtw_accum_pass_map(acc, &m_list, &m_mask, &m_tiles);
+    if (st != RTW_OK) return st;
+    if (m_list && m_tiles == 0) {  // nothing launched: the timer holds no interval (not the previous pass's)
+      if (timer) timer->recorded = false;
+      if (tail_ran) *tail_ran = 0u;
+      return RTW_OK;
+    }
+  }
   if (hipMemsetAsync(wsb + rtw_ws_counter_off(p), 0, 512, stream) != hipSuccess)
     return rtw_fail(RTW_EHIP, "workspace reset failed");
   rtwk::WorldArgs a;
@@ -223,7 +236,13 @@ int world_launch(rtw_world w, const rtw_camera* cam, const rtw_params* p, void* 
   a.lane_yield = (ye && *ye) ? (uint32_t)atoi(ye) : kLaneYield;
   if (tail_ran) *tail_ran = a.tail_deal;
   const size_t lds = c.lds;
-  const uint32_t grid = c.grid;
+  uint32_t grid = c.grid;
+  if (m_list) {  // (the rings are sized for c.grid: a smaller grid uses their head)
+    a.t.tile_list = m_list;
+    a.t.tile_mask = m_mask;
+    a.t.total_units = m_tiles * 64u * a.t.n_chunks;
+    grid = std::max(1u, std::min(grid, (a.t.total_units + 255u) / 256u));
+  }
   const int oi = c.oi, fs = c.fs;
   if (timer && rtw_timer_mark(timer, stream, true) != RTW_OK) return RTW_EHIP;
   hipError_t e = rtwk::launch_world(a, grid, lds, stream, mode, oi, fs);

@@ -141,6 +141,12 @@ def lib() -> C.CDLL:
     L.rtw_accum_noise.argtypes = [C.c_void_p, C.c_void_p, P(C.c_double)]
     L.rtw_accum_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.rtw_accum_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    if hasattr(L, "rtw_accum_set_mask"):  # adaptive sampling (an older A/B build has none)
+        L.rtw_accum_set_mask.argtypes = [C.c_void_p, C.c_void_p]
+        L.rtw_accum_set_adaptive.argtypes = [C.c_void_p, C.c_double, C.c_uint32]
+        L.rtw_accum_active.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_uint32)]
+        L.rtw_accum_read_counts.argtypes = [C.c_void_p, C.c_void_p]
+        L.rtw_accum_load_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     _lib = L
     return L
 
@@ -333,7 +339,16 @@ class Accumulator:
     `target` is a DeviceScene (cover-scene engines) or a world.DeviceWorld.
     After passes totalling N samples (a multiple of the chunk, or params.spp)
     the resolved image is the one-shot render's with spp = N, byte for byte.
-    Passes, resolves and noise queries go on one stream."""
+    Passes, resolves and noise queries go on one stream.
+
+    Adaptive sampling (rtw_hip.h): set_mask() / set_adaptive()
+    put the accumulator in the masked state, where it keeps per-pixel sample
+    counts (counts()) and an active set (active()).  A pass then renders the
+    active pixels only, a pixel that went inactive stays so, and a pixel with
+    count n holds the one-shot render's bytes with spp = n at that pixel.  In
+    that state render_pass() first waits on the host for the previous pass's
+    active-tile count (one small readback per pass); with no active pixel it
+    does nothing.  Masked passes save time, not workspace."""
 
     def __init__(self, target, params: Params):
         self.target = target
@@ -342,6 +357,7 @@ class Accumulator:
         self.chunk = effective_chunk(params)
         self.npix = params.row_count * params.width
         self.h = C.c_void_p()
+        self.masked = False  # set_mask / set_adaptive(tol > 0) / load(counts=) called: per-pixel counts, active set
         _check(lib().rtw_accum_create(C.byref(params), C.byref(self.h)))
 
     def workspace_bytes(self, pass_spp: int) -> int:
@@ -386,13 +402,48 @@ class Accumulator:
         _check(lib().rtw_accum_read(self.h, s.ctypes.data, t.ctypes.data))
         return s, t
 
-    def load(self, sum_, stat, samples_done: int):
-        """Replace the state with a saved one (rtw_accum_load)."""
+    def load(self, sum_, stat, samples_done: int, counts=None):
+        """Replace the state with a saved one (rtw_accum_load; with `counts`,
+        the per-pixel sample counts of counts(): rtw_accum_load_counts)."""
         s = np.ascontiguousarray(sum_, np.float64)
         t = np.ascontiguousarray(stat, np.float64)
         if s.size != self.npix * 3 or t.size != self.npix * 2:
             raise ValueError("sum / stat do not have this accumulator's size")
-        _check(lib().rtw_accum_load(self.h, s.ctypes.data, t.ctypes.data, samples_done))
+        if counts is None:
+            _check(lib().rtw_accum_load(self.h, s.ctypes.data, t.ctypes.data, samples_done))
+            return
+        c = np.ascontiguousarray(counts, np.uint32)
+        if c.size != self.npix:
+            raise ValueError("counts do not have this accumulator's size")
+        _check(lib().rtw_accum_load_counts(self.h, s.ctypes.data, t.ctypes.data, c.ctypes.data, samples_done))
+        self.masked = True
+
+    def set_mask(self, mask):
+        """active &= (mask != 0); mask: (rows, W), any integer or bool type (synchronous)."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        if m.size != self.npix:
+            raise ValueError("mask does not have this accumulator's size")
+        _check(lib().rtw_accum_set_mask(self.h, m.ctypes.data))
+        self.masked = True
+
+    def set_adaptive(self, tol: float, min_spp: int = 0):
+        """Per-pixel noise budget: a pixel stops once the standard error of its
+        mean luminance is <= tol (absolute) and it holds >= min_spp samples;
+        tol = 0 removes the budget (rtw_accum_set_adaptive)."""
+        _check(lib().rtw_accum_set_adaptive(self.h, float(tol), int(min_spp)))
+        self.masked = self.masked or tol > 0
+
+    def active(self):
+        """(active pixels, tiles that hold one) (synchronous)."""
+        a, b = C.c_uint32(), C.c_uint32()
+        _check(lib().rtw_accum_active(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def counts(self):
+        """Per-pixel sample counts, (rows, W) uint32 on the host (synchronous)."""
+        c = np.empty((self.params.row_count, self.params.width), np.uint32)
+        _check(lib().rtw_accum_read_counts(self.h, c.ctypes.data))
+        return c
 
     def close(self):
         if self.h:

@@ -63,9 +63,17 @@ class TorchAccumulator:
         acc = TorchAccumulator(renderer.scene, params)
         for img in acc.passes(cam, 20):     # the rgb tensor after each pass
             ...
+
+    Adaptive sampling (Accumulator): set_mask() / set_adaptive()
+    before or between passes; passes() then also stops when no pixel is
+    active.  In that state every pass begins with a small synchronising
+    readback, and needs the same workspace as an unmasked pass.
     """
 
-    def __init__(self, target, params: Params, device: int | torch.device | None = None):
+    def __init__(self, target, params: Params, device: int | torch.device | None = None,
+                 workspace: torch.Tensor | None = None):
+        """workspace (optional): a uint8 tensor to render the passes into, for instance another
+        accumulator's workspace(); replaced by a larger one when a pass needs more."""
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the rtw render path has no CPU fallback")
         if device is None:
@@ -74,7 +82,7 @@ class TorchAccumulator:
         torch.cuda.set_device(self.device)
         self.params = params
         self.acc = Accumulator(target, params)
-        self._ws = None
+        self._ws = workspace
         shape = (params.row_count, params.width, 3)
         self.rgb = torch.empty(shape, dtype=torch.uint8, device=self.device)
         self.mean = torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -87,19 +95,28 @@ class TorchAccumulator:
         ptr = (base + 255) & ~255
         return ptr, self._ws.numel() - (ptr - base)
 
+    def workspace(self, pass_spp: int) -> torch.Tensor:
+        """The workspace tensor (uint8) the passes of pass_spp samples render into."""
+        self._ws_ptr(pass_spp)
+        return self._ws
+
     def render_pass(self, cam: Camera, pass_spp: int, timer: Timer | None = None) -> torch.Tensor:
         """One pass and its resolve, asynchronous; returns the rgb tensor (rows, W, 3) uint8
         (self.mean holds the f32 mean).  The tensors are reused by the next pass."""
         ptr, nbytes = self._ws_ptr(pass_spp)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self.acc.render_pass(cam, pass_spp, ptr, nbytes, stream, timer)
-        self.acc.resolve(self.rgb.data_ptr(), self.mean.data_ptr(), stream)
+        if self.acc.samples() > 0:  # (a masked pass with no active pixel renders nothing)
+            self.acc.resolve(self.rgb.data_ptr(), self.mean.data_ptr(), stream)
         return self.rgb
 
     def passes(self, cam: Camera, pass_spp: int, max_noise: float | None = None):
         """Yield the image after each pass of pass_spp samples (the last one may
-        be shorter) until the frame's spp, or until noise() <= max_noise."""
+        be shorter) until the frame's spp, until noise() <= max_noise, or (with a
+        mask or a per-pixel budget) until no pixel is active."""
         while self.acc.samples() < self.params.spp:
+            if self.acc.masked and self.acc.active()[0] == 0:
+                return
             yield self.render_pass(cam, min(pass_spp, self.params.spp - self.acc.samples()))
             if max_noise is not None and self.acc.samples() >= 2 * self.acc.chunk and self.noise() <= max_noise:
                 return
@@ -109,6 +126,24 @@ class TorchAccumulator:
 
     def samples(self) -> int:
         return self.acc.samples()
+
+    def set_mask(self, mask):
+        self.acc.set_mask(mask)
+
+    def set_adaptive(self, tol: float, min_spp: int = 0):
+        self.acc.set_adaptive(tol, min_spp)
+
+    def active(self):
+        return self.acc.active()
+
+    def counts(self):
+        return self.acc.counts()
+
+    def read(self):
+        return self.acc.read()
+
+    def load(self, sum_, stat, samples_done: int, counts=None):
+        self.acc.load(sum_, stat, samples_done, counts)
 
     def close(self):
         self.acc.close()
