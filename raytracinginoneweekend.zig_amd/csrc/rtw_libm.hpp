@@ -9,11 +9,16 @@
 // noise colour.  The world kernel and the Tier-B oracle (oracle/ro_libm.h,
 // an independent C restatement of the same algorithms) therefore share this
 // definition; tests/test_world_cpu.py::test_tierb_libm_product_equals_oracle_and_glibc
-// (driving tests/native/libm_check.cpp) checks host builds of both against
-// each other bit for bit and against glibc (<= 1 ulp).  Compiled with
-// -ffp-contract=off: one IEEE operation per source operation.  sin/cos with
-// |x| >= 2^20 * pi/2 (the Payne-Hanek range, never produced by the
-// reference's scenes) return the platform libm's value.
+// (driving tests/native/libm_check.cpp) checks HOST builds of both against
+// each other bit for bit and against glibc (<= 1 ulp); the gfx950 build, the
+// one that runs, is checked against the oracle on the device by
+// tests/native/gpu_contract_check.hip (tests/test_gpu_contract.py) over the
+// same inputs plus the sphere-UV edges and every interval bound.  Compiled
+// with -ffp-contract=off: one IEEE operation per source operation.  sin/cos
+// with |x| >= 2^20 * pi/2 (the Payne-Hanek range, never produced by the
+// reference's scenes) return the platform libm's value — ocml's on the
+// device, glibc's in the oracle: outside the contract, and they do differ
+// (3 % of results, by 1 ulp; the device check prints the count; DESIGN.md, "Tier-B libm").
 #pragma once
 #include <cmath>
 #include <cstdint>

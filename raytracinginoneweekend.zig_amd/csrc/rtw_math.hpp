@@ -10,9 +10,17 @@
 //    the smallest |a - k*pi| a double in range can have, so
 //    sign(sin(a)) = (-1)^k * sign(r) is exact for |a| < 2^19 (else: libm sin).
 //    A faithful sin (glibc, ocml, musl in Zig) returns that same sign.
+//    checker_odd multiplies the three signs where the reference multiplies
+//    the three sines: the same answer unless that product underflows to +-0
+//    (|product| < 2^-1075; 2^-150 in the f32 Tier B), i.e. for a hit point
+//    within ~1e-108 (f32: ~1e-16) of the origin on all three axes at once.
 // 2. div_rn(x, b, y): RN(x / b) given y = RN(1 / b) (Markstein):
 //    q = RN(x*y) is within 1 ulp; r = x - b*q is exact (FMA);
-//    RN(q + r*y) = RN(x / b).  Outside the normal range it falls back to x/b.
+//    RN(q + r*y) = RN(x / b).  Outside the normal range it falls back to x/b:
+//    the f32 form when the quotient or the DIVIDEND is tiny (r = x - b*q has
+//    bits down to ~2^-47 |x|, which must not fall below the subnormal
+//    quantum for r to be exact); the f64 form tests the quotient only, so it
+//    is RN(x / b) for |x| >= 2^-968 and unchecked below that.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -89,7 +97,9 @@ RTW_HD float div_rn(float x, float b, float y) {
   const float r = std::fma(-q, b, x);
   float q1 = std::fma(r, y, q);
   const float aq = std::fabs(q1);
-  if (__builtin_expect(!(aq < 0x1p120f && aq > 0x1p-100f), 0)) {
+  // |x| > 2^-100 as well: r's last bit is ~2^-47 |x|, and below 2^-149 it is no longer exact
+  // (tests/native/gpu_contract_check.hip: subnormal and tiny dividends with mid-range quotients)
+  if (__builtin_expect(!(aq < 0x1p120f && aq > 0x1p-100f && std::fabs(x) > 0x1p-100f), 0)) {
     RTW_NO_SPECULATE();
     q1 = x / b;
   }

@@ -369,3 +369,137 @@ def mixed_bvh_world(W, earth, n_boxes, n_spheres, seed, swap=False, drop=(), var
         body.append(sph(chain_to_object(x, (-9.5, 0.9, 0.5)), 0.9, 4, "base", add_xf(x)))
     prims = head + body + tail
     return [p for p in prims if p["cls"] not in drop], xf, tex, mats, perl, imgs
+
+
+# ------------------------------------------- texture tables past index 0 ----
+# A world whose texture records name image 0-3 and Perlin table 0-2, so that the
+# kernel's table strides (W.perlin + index * (256*3+384), W.image + 4 * index)
+# and the images' running byte offsets are met away from 0
+# (tests/test_gpu_world_textures.py; tests/test_world_cpu.py checks on the oracle
+# alone that every table is visible, so the GPU tests cannot pass vacuously).
+TEXTURED_CAMERA = dict(look_from=(0.0, 7.5, 20.0), look_at=(0.0, 2.6, 0.0), vfov=38.0, aperture=0.0, focus=20.0)
+TEXTURED_BG = (0.7, 0.8, 1.0)
+TEXTURED_PERLIN_SEEDS = (7, 8, 9)
+TEXTURED_NOISE_SCALES = (4.0, 0.0, -2.5)
+
+
+def textured_images(earth):
+    """The four images, in table order: 1x1 opaque; a PORTRAIT 5x9 (height >
+    width: the reference clamps the row against width - 1, texture.zig:130, so
+    rows 5-8 are never shown and row 4 stands in for them); the earth map (the
+    later byte offsets are large and not round); a landscape 7x3 with alpha-0
+    texels (shown as (0, 0, 1), texture.zig:140).  Hard-edged colours: every
+    texel of the small images differs from its neighbours by >= 60 in a channel."""
+    one = np.array([[[230, 40, 200, 255]]], np.uint8)
+    portrait = np.zeros((9, 5, 4), np.uint8)
+    for j in range(9):
+        for i in range(5):
+            portrait[j, i] = (250 - 60 * (i % 4) if j % 2 else 20 + 55 * i, (40 + 90 * j) % 256, 240 if (i + j) % 2 else 15, 255)
+    portrait[5:] = portrait[5:, ::-1] // 2 + np.array([0, 100, 0, 0], np.uint8)  # rows the clamp hides: other colours
+    portrait[..., 3] = 255
+    land = np.zeros((3, 7, 4), np.uint8)
+    for j in range(3):
+        for i in range(7):
+            land[j, i] = (255 if (i + j) % 2 else 30, 35 + 100 * j, 30 + 35 * i, 0 if (i + 2 * j) % 3 == 0 else 255)
+    land[land[..., 3] == 0, :3] = (255, 255, 0)  # rgb of an alpha-0 texel is never shown (yellow if it were)
+    return [one, portrait, np.ascontiguousarray(earth, np.uint8), land]
+
+
+def perlin_table(W, seed):
+    """The Perlin table the library's scene 3 builds from `seed`, as the dict _to_desc takes."""
+    scene3 = W.BuiltScene(3, seed)  # (kept alive while its table is copied: desc points into it)
+    pl = scene3.desc.perlins[0]
+    return {"ranvec": [list(pl.ranvec[k]) for k in range(256)], "perm": [list(pl.perm[a]) for a in range(3)]}
+
+
+def textured_world(W, earth, variant=None, filler=0, images=None, perlins=None):
+    """Every image on a sphere (sphere UV through the Tier-B libm) AND on a rect
+    of each orientation; three noise textures (TEXTURED_NOISE_SCALES) on three
+    Perlin tables; image textures on two WMAT_LIGHT rects (the mkind == 3 image
+    path); an earth sphere and a portrait rect under Translate / RotateY
+    chains.  At most 32 primitives (the linear loop) unless `filler` adds that
+    many untextured small spheres (> 32: a BVH).  variant: None; "noise" (the
+    image primitives and tables left out); "image" (the noise ones left out;
+    the ground and back wall become solid); or "image_spheres" (spheres only,
+    no chains: every image on a Lambertian sphere, two on emitting spheres —
+    the world kernel compiles a feature set of its own for such worlds, and
+    with `filler` the per-lane BVH walk's).  The kept textures keep index > 0.
+    images / perlins replace the tables (the vacuity guards exchange entries).
+
+    Returns (prims, xforms, textures, mats, perlins, images).  Camera: TEXTURED_CAMERA."""
+    S, XY, XZ, YZ = W.PRIM_SPHERE, W.PRIM_XY_RECT, W.PRIM_XZ_RECT, W.PRIM_YZ_RECT
+    noise, image = variant not in ("image", "image_spheres"), variant != "noise"
+    imgs = (images if images is not None else textured_images(earth)) if image else []
+    perl = (perlins if perlins is not None else [perlin_table(W, s) for s in TEXTURED_PERLIN_SEEDS]) if noise else []
+    tex = [dict(kind=W.TEX_SOLID, color=(7.0, 6.5, 6.0)), dict(kind=W.TEX_SOLID, color=(0.55, 0.55, 0.5)),
+           dict(kind=W.TEX_SOLID, color=(0.7, 0.3, 0.2))]
+    mats = [dict(kind=W.WMAT_LIGHT, tex=0), dict(kind=W.WMAT_LAMBERT, tex=1), dict(kind=W.WMAT_LAMBERT, tex=2),
+            dict(kind=W.WMAT_METAL, albedo=(0.8, 0.8, 0.9), fuzz=0.1)]
+    LIGHT, GREY, FILL_A, FILL_B = 0, 1, 2, 3
+    img_mat, img_light, noise_mat = {}, {}, {}
+    if image:
+        for k in range(4):
+            tex.append(dict(kind=W.TEX_IMAGE, image=k))
+            mats.append(dict(kind=W.WMAT_LAMBERT, tex=len(tex) - 1))
+            img_mat[k] = len(mats) - 1
+        for k in (1, 3):
+            tex.append(dict(kind=W.TEX_IMAGE, image=k))
+            mats.append(dict(kind=W.WMAT_LIGHT, tex=len(tex) - 1))
+            img_light[k] = len(mats) - 1
+    if noise:
+        for k, sc in enumerate(TEXTURED_NOISE_SCALES):
+            tex.append(dict(kind=W.TEX_NOISE, perlin=k, scale=sc))
+            mats.append(dict(kind=W.WMAT_LAMBERT, tex=len(tex) - 1))
+            noise_mat[k] = len(mats) - 1
+    prims, xf = [], []
+
+    def sph(c, r, mat, xform=-1):
+        return dict(kind=S, mat=mat, xform=xform, a=[c[0], c[1], c[2], c[0], c[1], c[2], r, 0, 0])
+
+    def rect(kind, a, mat, xform=-1):
+        return dict(kind=kind, mat=mat, xform=xform, a=list(a))
+
+    if variant == "image_spheres":
+        prims.append(sph((0, -1000, 0), 1000.0, GREY))
+        prims.append(sph((0, 60, 10), 30.0, LIGHT))
+        for k in range(4):
+            cx = -7.2 + 4.8 * k
+            prims.append(sph((cx, 2.0, 0.0), 2.0, img_mat[k]))
+            prims.append(sph((cx + 1.2, 0.9, 4.5), 0.9, img_mat[3 - k]))
+        prims.append(sph((-3.0, 6.0, -4.0), 1.6, img_light[1]))
+        prims.append(sph((3.0, 6.0, -4.0), 1.6, img_light[3]))
+        image = False  # (the rects and chains below are not part of this variant)
+    else:
+        prims.append(sph((0, -1000, 0), 1000.0, noise_mat.get(0, GREY)))             # ground: noise 0
+        prims.append(rect(XY, [-11, 11, 0, 9, -7.0], noise_mat.get(1, GREY)))         # back wall: noise 1
+        prims.append(rect(XZ, [-6, 6, -5, 5, 13.0], LIGHT))
+    if noise:
+        prims.append(sph((0.0, 1.5, 5.0), 1.5, noise_mat[2]))                        # noise 2, and under a chain:
+        x = dict(n=2, op=[W.XF_TRANSLATE, W.XF_ROTATE_Y], v=[(0.5, 0.0, -1.0), _rot(0.6)])
+        xf.append(x)
+        prims.append(sph(chain_to_object(x, (-4.6, 1.1, 6.0)), 1.1, noise_mat[2], len(xf) - 1))
+    if image:
+        for k in range(4):
+            cx = -7.8 + 5.2 * k
+            m = img_mat[k]
+            prims.append(sph((cx, 1.3, 0.5), 1.3, m))
+            prims.append(rect(XY, [cx - 1.5, cx + 1.5, 3.2, 5.8, -3.0], m))
+            prims.append(rect(XZ, [cx - 1.4, cx + 1.4, 2.4, 4.6, 0.02], m))
+            side = -10.5 if k < 2 else 10.5
+            y0 = 0.3 if k % 2 == 0 else 4.0
+            prims.append(rect(YZ, [y0, y0 + 3.4, -6.8, -0.5, side], m))
+        prims.append(rect(XY, [-4.6, -0.4, 6.2, 8.6, -6.9], img_light[1]))            # the portrait, emitting
+        prims.append(rect(XY, [0.4, 4.6, 6.2, 8.6, -6.9], img_light[3]))              # the alpha-0 image, emitting
+        x = dict(n=2, op=[W.XF_ROTATE_Y, W.XF_TRANSLATE], v=[_rot(-0.7), (2.0, 0.0, 1.0)])
+        xf.append(x)
+        prims.append(sph(chain_to_object(x, (4.4, 1.0, 7.0)), 1.0, img_mat[2], len(xf) - 1))
+        x = dict(n=3, op=[W.XF_TRANSLATE, W.XF_ROTATE_Y, W.XF_TRANSLATE], v=[(1.0, 0.5, 0.0), _rot(0.35), (-0.5, 0.0, 2.0)])
+        xf.append(x)
+        o = chain_to_object(x, (8.2, 1.5, 5.0))
+        prims.append(rect(XY, [o[0] - 1.2, o[0] + 1.2, o[1] - 1.2, o[1] + 1.2, o[2]], img_mat[1], len(xf) - 1))
+    assert len(prims) <= 32
+    rng = np.random.default_rng(11)
+    for i in range(filler):
+        r = float(rng.uniform(0.12, 0.3))
+        prims.append(sph((float(rng.uniform(-10, 10)), r, float(rng.uniform(-6, 9))), r, FILL_A if i % 2 else FILL_B))
+    return prims, xf, tex, mats, perl, imgs

@@ -2,7 +2,9 @@
 // oracle's independent restatement (oracle/ro_libm.h) — must agree bit for
 // bit — and against glibc (must be within 1 ulp).  Inputs: random doubles
 // over many magnitudes, the exact multiples/cancellation points of pi/2 that
-// select the argument-reduction branches, and special values.
+// select the argument-reduction branches, and special values
+// (libm_inputs.hpp, shared with tests/native/gpu_contract_check.hip, which
+// checks the gfx950 build), and that header's sphere-UV edges.
 // Usage: libm_check N seed  -> "cases C mismatch M maxulp U"
 #include <cinttypes>
 #include <cmath>
@@ -11,6 +13,7 @@
 #include <random>
 #include <vector>
 
+#include "libm_inputs.hpp"
 #include "ro_libm.h"
 #include "rtw_libm.hpp"
 
@@ -30,17 +33,11 @@ static bool same(double a, double b) {
 }
 
 int main(int argc, char** argv) {
-  const long n = argc > 1 ? atol(argv[1]) : 1000000;
-  std::mt19937_64 g(argc > 2 ? atol(argv[2]) : 1);
-  std::uniform_real_distribution<double> U(-1.0, 1.0), E(-8.0, 6.5);
-  std::vector<double> xs;
-  for (long i = 0; i < n; ++i) xs.push_back(U(g) * std::pow(10.0, E(g)));
-  const double pio2 = 1.57079632679489661923;
-  for (int k = -64; k <= 64; ++k)  // branch points of __rem_pio2
-    for (int d = -3; d <= 3; ++d) xs.push_back(std::nextafter(k * pio2, d < 0 ? -INFINITY : INFINITY) + d * 1e-16 * k);
-  const double sp[] = {0.0, -0.0, 1.0, -1.0, 0.5, -0.5, 1e-300, -1e-300, 5e-324, INFINITY, -INFINITY, NAN,
-                       0.4375, 1.1875, 2.4375, 0x1p66, 0x1p-27, 0x1p20 * pio2 * 0.999};
-  for (double s : sp) xs.push_back(s);
+  // the generator lives in libm_inputs.hpp (shared with the device check), followed by the
+  // sphere-UV edges and interval bounds that check adds
+  std::vector<double> xs = libm_inputs(argc > 1 ? atol(argv[1]) : 1000000, argc > 2 ? atol(argv[2]) : 1);
+  std::vector<double> ey, ex, ec;
+  sphere_uv_edges(ey, ex, ec);
   long cases = 0, mismatch = 0;
   int64_t maxulp = 0;
   auto chk = [&](double a, double b, double ref) {
@@ -56,11 +53,13 @@ int main(int argc, char** argv) {
     const double x = xs[i];
     chk(rtwl::sin(x), ro_sin(x), std::sin(x));
     chk(rtwl::cos(x), ro_cos(x), std::cos(x));
-    const double y = xs[(i * 7919 + 13) % xs.size()];
+    const double y = libm_atan2_partner(xs, i);
     chk(rtwl::atan2(y, x), ro_atan2(y, x), std::atan2(y, x));
-    const double c = std::fmod(x, 1.0);
+    const double c = libm_acos_arg(x);
     chk(rtwl::acos(c), ro_acos(c), std::acos(c));
   }
+  for (size_t i = 0; i < ey.size(); ++i) chk(rtwl::atan2(ey[i], ex[i]), ro_atan2(ey[i], ex[i]), std::atan2(ey[i], ex[i]));
+  for (double c : ec) chk(rtwl::acos(c), ro_acos(c), std::acos(c));
   printf("cases %ld mismatch %ld maxulp %" PRId64 "\n", cases, mismatch, maxulp);
   return mismatch == 0 && maxulp <= 1 ? 0 : 1;
 }

@@ -50,6 +50,23 @@ int main(int argc, char** argv) {
     const float xf = (float)x, bf = (float)b;
     if (rtwm::div_rn(xf, bf, 1.0f / bf) != xf / bf) bad_divf++;
   }
+  // f32: tiny and subnormal dividends with quotients inside div_rn's fast range (x - b*q is not
+  // exact there: the case behind the |x| > 2^-100 test), subnormal divisors, both tiny
+  auto fbits = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+  for (long i = 0; i < N; ++i) {
+    const uint64_t z = g(), w = g();
+    const uint32_t mx = (uint32_t)w & 0x7FFFFFu, mb = (uint32_t)z & 0x7FFFFFu;
+    float xf, bf;
+    switch (i % 4) {
+      case 0: xf = fbits(mx), bf = fbits(mb | ((uint32_t)(127 - 60 + (z >> 32) % 121) << 23)); break;
+      case 1: xf = fbits(mx | ((uint32_t)(1 + (w >> 32) % 40) << 23)), bf = fbits(mb | 1u); break;
+      case 2: xf = fbits(mx), bf = fbits(mb | 1u); break;
+      default: xf = fbits(mx | ((uint32_t)(1 + (w >> 32) % 30) << 23)), bf = fbits(mb | ((uint32_t)(1 + (z >> 32) % 30) << 23));
+    }
+    if (w >> 63) xf = -xf;
+    const float q = rtwm::div_rn(xf, bf, 1.0f / bf), r = xf / bf;
+    if (std::memcmp(&q, &r, 4) != 0 && !(q != q && r != r)) bad_divf++;
+  }
   // small integers / typical operands of the kernel (W-1, radii, |d|^2)
   for (int w = 2; w < 5000; ++w) {
     const double b = w - 1.0, y = 1.0 / b;

@@ -247,3 +247,90 @@ def test_cli_pass_spp_writes_the_same_image(rtw, tmp_path):
         r = subprocess.run(args, capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, r.stderr
     assert cone.read_bytes() == cprog.read_bytes()
+
+
+# ------------------------------------------------- quantisation edges ----
+QW, QH = 31, 29  # 899 pixels: room for the ~2,600 values of one n, and no multiple of the 8x8 tile
+
+
+def _quantize_values(q, n):
+    """Sums whose quantisation sits on an edge, for a frame of n samples.  For
+    every k in 1..255: n (k/256)^2 and its two neighbours on each side; and,
+    found by bisection with the oracle's ro_quantize, the SMALLEST double that
+    quantises to k with its two neighbours on each side — that group holds both
+    outputs k - 1 and k by construction (the first group alone does so for
+    most (n, k) only: 1/n is inexact, and t (1/n) can land a few ulps off).
+    Then 0, -0.0, a subnormal, a negative sum, the neighbours of n 0.999^2,
+    1e300, +inf and NaN.  Returns (values, number of first groups that straddle)."""
+    scale = 1.0 / n
+    vals, straddle = [], 0
+
+    def around(t):
+        g, lo, hi = [t], t, t
+        for _ in range(2):
+            lo, hi = np.nextafter(lo, -np.inf), np.nextafter(hi, np.inf)
+            g = [lo] + g + [hi]
+        return [float(x) for x in g]
+
+    for k in range(1, 256):
+        t = float(np.float64(n) * (np.float64(k) / 256) ** 2)
+        g = around(t)
+        straddle += {k - 1, k} <= {q(x, scale) for x in g}
+        lo, hi = np.float64(t * (1 - 1e-9)).view(np.int64), np.float64(t * (1 + 1e-9)).view(np.int64)
+        assert q(float(lo.view(np.float64)), scale) == k - 1 and q(float(hi.view(np.float64)), scale) == k
+        while hi - lo > 1:  # monotone in the bit pattern
+            mid = np.int64((int(lo) + int(hi)) // 2)
+            if q(float(mid.view(np.float64)), scale) >= k:
+                hi = mid
+            else:
+                lo = mid
+        edge = around(float(hi.view(np.float64)))
+        assert [q(x, scale) for x in edge] == [k - 1, k - 1, k, k, k], (n, k)
+        vals += g + edge
+    top = float(np.float64(n) * np.float64(0.999) ** 2)
+    vals += around(top) + [0.0, -0.0, 5e-324, 1e-310, -1e-310, -0.25 * n, -1e300, 1e300, float("inf"), float("nan"),
+                           0.25 * n, float(n), 2.0 * n]
+    return vals, straddle
+
+
+@pytest.mark.parametrize("n", [1, 3, 7, 45, 500])
+def test_resolve_quantisation_edges(rtw, oracle, cover, n):
+    """accum_resolve_kernel's sqrt, clamp to 0.999, (uint8_t)(256 cl) and NaN ->
+    255 on sums a test chooses (rtw_accum_load, then the resolve), value by
+    value against ro_quantize(t, 1.0 / n), and the f32 mean against
+    np.float32(t * (1.0 / n)) bit for bit (two NaNs are equal).  rtw_accum_load
+    takes non-finite sums as they are: a saved state may hold them."""
+    import torch
+    from rtw_amd.device import TorchAccumulator
+    _, _, _, scene = cover
+    q = oracle.lib().ro_quantize
+    vals, straddle = _quantize_values(q, n)
+    print("n", n, "values", len(vals), "first groups holding both k - 1 and k:", straddle, "of 255")
+    flat = np.full(QW * QH * 3, 0.5 * n)
+    assert len(vals) <= flat.size
+    flat[:len(vals)] = vals
+    ta = TorchAccumulator(scene, rtw.make_params(QW, QH, n))
+    try:
+        ta.acc.load(flat.reshape(QH, QW, 3), np.zeros((QH, QW, 2)), n)
+        assert ta.samples() == n
+        ta.acc.resolve(ta.rgb.data_ptr(), ta.mean.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        rgb, mean = ta.rgb.cpu().numpy().ravel(), ta.mean.cpu().numpy().ravel()
+        back, _ = ta.acc.read()
+    finally:
+        ta.close()
+    assert np.array_equal(back.ravel().view(np.uint64), flat.view(np.uint64))  # loaded as given, NaN and -0.0 included
+    scale = 1.0 / n
+    want = np.array([q(float(t), scale) for t in flat], np.uint8)
+    wrong = np.flatnonzero(rgb != want)
+    assert wrong.size == 0, [(float.hex(float(flat[i])), int(rgb[i]), int(want[i])) for i in wrong[:8]]
+    with np.errstate(over="ignore", invalid="ignore"):
+        wmean = (flat * scale).astype(np.float32)
+    same = (mean.view(np.uint32) == wmean.view(np.uint32)) | (np.isnan(mean) & np.isnan(wmean))
+    assert same.all(), [(float.hex(float(flat[i])), float(mean[i]), float(wmean[i])) for i in np.flatnonzero(~same)[:8]]
+    # what the rules give at the ends (oracle/rtw_oracle.c ro_quantize, tests/test_oracle_kat.py)
+    at = {float.hex(v) if v == v else "nan": int(rgb[i]) for i, v in enumerate(vals)}
+    assert at[float.hex(0.0)] == 0 and at[float.hex(-0.0)] == 0 and at[float.hex(5e-324)] == 0
+    assert at["nan"] == 255 and at[float.hex(float("inf"))] == 255 and at[float.hex(1e300)] == 255
+    assert at[float.hex(-0.25 * n)] == 255  # sqrt of a negative sum is NaN, and @min(NaN, 0.999) = 0.999
+    assert at[float.hex(0.25 * n)] == 128 and at[float.hex(float(n))] == 255

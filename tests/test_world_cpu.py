@@ -103,6 +103,9 @@ def test_tierb_libm_product_equals_oracle_and_glibc(tmp_path):
     p = subprocess.run([exe, "1000000", "7"], capture_output=True, text=True)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "mismatch 0" in p.stdout
+    # the generator moved into libm_inputs.hpp (shared with the device check): no case was lost
+    # (4,003,684 before the move), and the sphere-UV edges came on top
+    assert int(re.search(r"cases (\d+)", p.stdout).group(1)) > 4003684
 
 
 def _lemire(next_u64, at_least, less_than):
@@ -586,3 +589,120 @@ def test_prim_box_check_has_teeth(tmp_path):
         p = subprocess.run([exe, "20000", "1"], capture_output=True, text=True)
         m = re.search(r"violations (\d+)/(\d+)", p.stdout)
         assert m and int(m.group(1)) > 0 and p.returncode == 1, (name, p.stdout)
+
+
+# ------------------------------------------------------------------------
+# The textured world of tests/test_gpu_world_textures.py (helpers.textured_world),
+# on the oracle alone: every image and every Perlin table is visible at its own
+# index, the portrait image's row clamp bites and the alpha-0 colour is seen.
+def _textured_oracle_camera(oracle, aspect=16 / 9):
+    from helpers import TEXTURED_CAMERA as m
+    cam = oracle.Camera()
+    arr = C.c_double * 3
+    oracle.lib().ro_camera_init(C.byref(cam), arr(*m["look_from"]), arr(*m["look_at"]), arr(0, 1, 0), m["vfov"],
+                                aspect, m["aperture"], m["focus"], 0.0, 1.0)
+    return cam
+
+
+@pytest.fixture(scope="module")
+def textured_render(W, oracle, earth):
+    """Oracle Tier B at 96x54x8 (the GPU tests' frame) of a textured world -> rgb."""
+    from helpers import TEXTURED_BG, TEXTURED_PERLIN_SEEDS, perlin_table, textured_images, textured_world
+    base_imgs = textured_images(earth)
+    base_perl = [perlin_table(W, s) for s in TEXTURED_PERLIN_SEEDS]
+
+    def get(images=None, perlins=None, **kw):
+        t = textured_world(W, earth, images=images or base_imgs, perlins=perlins or base_perl, **kw)
+        o = oracle.TableWorld(*t, background=TEXTURED_BG)
+        return o.render_tier_b(_textured_oracle_camera(oracle), 96, 54, 8, bg=TEXTURED_BG, threads=8)[0], t
+    return get, base_imgs, base_perl
+
+
+def _changed(a, b):
+    return float((a != b).any(axis=2).mean())
+
+
+def test_textured_world_every_table_is_visible(textured_render):
+    """Exchanging any two images, or any two Perlin tables, changes >= 1 % of
+    the pixels of the oracle's 96x54x8 frame: a kernel that read table 0 for
+    every index, or strode the tables wrongly, cannot pass the GPU tests."""
+    get, imgs, perl = textured_render
+    full, t = get()
+    assert len(t[0]) <= 32 and full.std() > 5
+    assert [x["image"] for x in t[2] if x["kind"] == 3] == [0, 1, 2, 3, 1, 3]
+    assert [(x["perlin"], x["scale"]) for x in t[2] if x["kind"] == 2] == [(0, 4.0), (1, 0.0), (2, -2.5)]
+    assert imgs[1].shape == (9, 5, 4) and imgs[3].shape == (3, 7, 4) and imgs[0].shape == (1, 1, 4) and imgs[2].shape[1] == 500
+    for a in range(4):
+        for b in range(a + 1, 4):
+            sw = list(imgs)
+            sw[a], sw[b] = sw[b], sw[a]
+            frac = _changed(get(images=sw)[0], full)
+            print("images", a, b, "exchanged: changed pixels", frac)
+            assert frac >= 0.01, (a, b, frac)
+    for a in range(3):
+        for b in range(a + 1, 3):
+            sw = list(perl)
+            sw[a], sw[b] = sw[b], sw[a]
+            frac = _changed(get(perlins=sw)[0], full)
+            print("perlin tables", a, b, "exchanged: changed pixels", frac)
+            assert frac >= 0.01, (a, b, frac)
+
+
+def test_textured_world_row_clamp_and_alpha_zero_are_visible(textured_render):
+    """The portrait image (5 wide, 9 high): the reference clamps the ROW against
+    width - 1 (texture.zig:130), so row 4 is shown wherever rows 4-8 would be
+    and rows 5-8 never — repainting row 4 changes the frame, repainting rows
+    5-8 does not (a kernel clamping against height - 1 would show them).  The
+    alpha-0 texels of the 7x3 image are shown as (0, 0, 1): their rgb never
+    shows, their alpha does."""
+    get, imgs, _ = textured_render
+    full, _ = get()
+
+    def with_image(k, edit):
+        sw = [i.copy() for i in imgs]
+        edit(sw[k])
+        return get(images=sw)[0]
+
+    def row4(im):
+        im[4, :, :3] = 255 - im[4, :, :3]
+
+    def hidden_rows(im):
+        im[5:, :, :3] = 255 - im[5:, :, :3]
+
+    frac = _changed(with_image(1, row4), full)
+    print("portrait row 4 repainted: changed pixels", frac)
+    assert frac >= 0.01
+    assert _changed(with_image(1, hidden_rows), full) == 0.0
+    a0 = imgs[3][..., 3] == 0
+    assert 5 <= a0.sum() <= 10
+
+    def alpha0_rgb(im):
+        im[a0, :3] = (0, 255, 0)
+
+    def alpha0_opaque(im):
+        im[a0, 3] = 255
+
+    assert _changed(with_image(3, alpha0_rgb), full) == 0.0
+    frac = _changed(with_image(3, alpha0_opaque), full)
+    print("alpha-0 texels made opaque: changed pixels", frac)
+    assert frac >= 0.01
+    # the emitting rect shows the colour itself: (0, 0, 1) -> bytes (0, 0, 255) in pixels no other colour reaches
+    assert ((full[..., 0] == 0) & (full[..., 1] == 0) & (full[..., 2] == 255)).sum() >= 10
+
+
+def test_textured_world_variants(W, earth):
+    from helpers import textured_world
+    n = {v: textured_world(W, earth, variant=v) for v in (None, "noise", "image")}
+    assert all(len(t[0]) <= 32 for t in n.values())
+    assert not n["noise"][5] and len(n["noise"][4]) == 3 and max(x.get("perlin", 0) for x in n["noise"][2]) == 2
+    assert not n["image"][4] and len(n["image"][5]) == 4 and max(x.get("image", 0) for x in n["image"][2]) == 3
+    assert any(p["xform"] >= 0 and n[v][3][p["mat"]]["kind"] == W.WMAT_LAMBERT for v in n for p in n[v][0])
+    big = textured_world(W, earth, filler=40)
+    assert len(big[0]) > 32 and big[0][:len(n[None][0])] == n[None][0]
+    # spheres only, no chains, every image (and both emitting ones): the world kernel's image-only feature set
+    sp = textured_world(W, earth, variant="image_spheres", filler=40)
+    assert all(p["kind"] == W.PRIM_SPHERE and p["xform"] < 0 for p in sp[0]) and not sp[1] and not sp[4]
+    img = [(sp[3][p["mat"]]["kind"], sp[2][sp[3][p["mat"]]["tex"]]["image"]) for p in sp[0]
+           if "tex" in sp[3][p["mat"]] and sp[2][sp[3][p["mat"]]["tex"]]["kind"] == W.TEX_IMAGE]
+    assert {k for _, k in img} == {0, 1, 2, 3} and len(sp[0]) > 32
+    assert sorted(k for m, k in img if m == W.WMAT_LIGHT) == [1, 3]
