@@ -529,6 +529,97 @@ int rtw_accum_read_counts(rtw_accum a, uint32_t *cnt_out);
 int rtw_accum_load_counts(rtw_accum a, const double *sum, const double *stat, const uint32_t *cnt,
                           uint32_t samples_done);
 
+/* ================================================= feature-guided denoiser ===
+ *   An image-space filter for previews and finished frames:
+ * first-hit feature buffers ("guides") from a deterministic ray per pixel, and
+ * an edge-avoiding a-trous wavelet filter steered by them and by the
+ * accumulator's per-pixel luminance variance.  New symbols only: a render
+ * without these calls is untouched.
+ *
+ * Guides.  One record per output pixel, rows in output order like d_rgb.  The
+ * feature ray of pixel (x, image row y, top first) draws nothing from the RNG:
+ * Camera.getRay (main.zig:91-100) with its two random draws replaced by their
+ * means — s = (x + 0.5) / (W - 1), t = ((H - 1 - y) + 0.5) / (H - 1), lens
+ * offset 0 (origin = cam.origin, direction = llc + s*horizontal + t*vertical -
+ * origin), time = time0 + 0.5 * (time1 - time0), t_min = 0.001, t_max = inf —
+ * in f64, each field rounded to f32 on store. */
+typedef struct {
+  float normal[3];   /* the hit record's normal (facing the ray); 0,0,0 on a miss */
+  float depth;       /* ray parameter t of the hit (direction not normalised); 0 on a miss */
+  float albedo[3];   /* Lambert: the texture's value at the hit; Metal: its albedo; Dielectric: 1,1,1;
+                        Light: the emit texture's value; the frame's background on a miss */
+  uint32_t prim;     /* primitive (world) or sphere (scene) list index + 1; 0 on a miss */
+} rtw_guide;         /* 32 bytes; buffers of it are 16-byte aligned */
+
+/* Asynchronous on `stream`; d_guides: W * row_count records of device memory.
+ * Of params only width, height, row_begin, row_stride, row_count and
+ * background matter.  No workspace. */
+int rtw_scene_guides_device(rtw_scene scene, const rtw_camera *cam, const rtw_params *params,
+                            rtw_guide *d_guides, void *stream);
+int rtw_world_guides_device(rtw_world world, const rtw_camera *cam, const rtw_params *params,
+                            rtw_guide *d_guides, void *stream);
+
+/* The filter (csrc/rtw_denoise.hpp has the weight functions): `levels`
+ * iterations of 5x5 B3-spline taps spaced 1, 2, 4, ... pixels; a tap's weight
+ * is the product of the spline weight and of colour, normal, depth and albedo
+ * terms; variance is filtered along with the colour.  Every field 0 = its
+ * default (5 levels; sigmas 2, 0.1, 0.25, 0.1). */
+#define RTW_DENOISE_NO_COLOR 1u   /* flags bit 0: drop the colour term */
+#define RTW_DENOISE_DIRECT 2u     /* flags bit 1: every level reads its taps from global memory, none through
+                                     LDS tiles (the same bytes; for measurement) */
+#define RTW_DENOISE_MAX_LEVELS 6u
+typedef struct {
+  uint32_t levels;                /* 1..6, 0 = 5 */
+  double sigma_color;             /* in standard errors of the centre's luminance */
+  double sigma_normal;            /* 1 - dot(n_p, n_q) at which the normal term reaches 0 */
+  double sigma_depth;             /* relative to the larger of the two depths */
+  double sigma_albedo;            /* in units of linear albedo */
+  uint32_t flags;                 /* RTW_DENOISE_* */
+} rtw_denoise_opts;
+
+/* Variance values: >= 0 known; RTW_VAR_UNKNOWN: the colour term is dropped at
+ * that pixel; RTW_VAR_EMPTY: the pixel holds no sample — it contributes to
+ * nobody and stays 0. */
+#define RTW_VAR_UNKNOWN (-1.0f)
+#define RTW_VAR_EMPTY (-2.0f)
+
+/* Two ping-pong images of {r, g, b, var} f32.  0 on bad arguments. */
+size_t rtw_denoise_workspace_bytes(uint32_t width, uint32_t height, const rtw_denoise_opts *opts);
+/* Denoise a W x H image of contiguous rows.  d_mean: W*H*3 floats (linear);
+ * d_var: W*H floats (the variance of the pixel's luminance, see above) or NULL
+ * (all unknown); d_guides: W*H records or NULL (the guide terms are dropped);
+ * opts: NULL = defaults.  Outputs: d_rgb_out (W*H*3 bytes, quantised as a
+ * render's) and/or d_mean_out (W*H*3 floats), at least one.  The inputs are
+ * not modified and may not alias the outputs.  Plain device buffers,
+ * asynchronous on `stream`, graph-capturable; no state, no atomics: the same
+ * inputs give the same bytes, and those are rtw_denoise_host's. */
+int rtw_denoise_device(const float *d_mean, const float *d_var, const rtw_guide *d_guides, uint32_t width,
+                       uint32_t height, const rtw_denoise_opts *opts, void *workspace, size_t workspace_bytes,
+                       uint8_t *d_rgb_out, float *d_mean_out, void *stream);
+/* The same filter on HOST buffers (workspace included), on the CPU: needs no
+ * GPU.  `stream` is ignored. */
+int rtw_denoise_host(const float *mean, const float *var, const rtw_guide *guides, uint32_t width,
+                     uint32_t height, const rtw_denoise_opts *opts, void *workspace, size_t workspace_bytes,
+                     uint8_t *rgb_out, float *mean_out, void *stream);
+
+/* The accumulator's per-pixel variance, asynchronous on `stream`: d_var
+ * (W*row_count floats) = f32 of the squared standard error of the pixel's mean
+ * luminance (rtw_accum_noise's per-pixel term, in the mean image's units),
+ * each pixel with its own m = count / chunk in the masked state;
+ * RTW_VAR_UNKNOWN where m < 2, RTW_VAR_EMPTY where the pixel has no sample. */
+int rtw_accum_variance_device(rtw_accum a, float *d_var, void *stream);
+/* Resolve, variance, filter: the denoised image of the samples so far into
+ * d_rgb and/or d_mean (optional each, not both NULL).  d_guides may be NULL.
+ * workspace: rtw_accum_denoise_workspace_bytes(a, opts) bytes of device memory,
+ * 16-byte aligned — the filter's two images plus the resolved mean, the
+ * variance and the resolve's rgb8 (19 bytes per pixel).  The accumulator's
+ * state is not modified: passes may continue.  Rows must be contiguous image
+ * rows: RTW_UNSUPPORTED when params.row_stride != 1. */
+size_t rtw_accum_denoise_workspace_bytes(rtw_accum a, const rtw_denoise_opts *opts);
+int rtw_accum_denoise_device(rtw_accum a, const rtw_guide *d_guides, const rtw_denoise_opts *opts,
+                             void *workspace, size_t workspace_bytes, uint8_t *d_rgb, float *d_mean,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

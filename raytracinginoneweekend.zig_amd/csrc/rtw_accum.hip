@@ -363,16 +363,19 @@ namespace rtw {
 
 std::vector<uint8_t> renderProgressive(const rtw_camera& cam, const rtw_params& p, uint32_t pass_spp,
                                        const FlatScene* scene, const rtw_world_desc* world, double max_noise,
-                                       const PassFn& on_pass, uint32_t* samples_used, const AdaptiveOpts* adaptive) {
+                                       const PassFn& on_pass, uint32_t* samples_used, const AdaptiveOpts* adaptive,
+                                       const rtw_denoise_opts* denoise) {
   if ((scene != nullptr) == (world != nullptr)) throw Error(RTW_EINVAL, "renderProgressive: a scene or a world");
   struct Dev {  // released on every way out
     rtw_scene sc = nullptr;
     rtw_world w = nullptr;
     rtw_accum acc = nullptr;
-    void *ws = nullptr, *rgb = nullptr;
+    void *ws = nullptr, *rgb = nullptr, *guides = nullptr, *dn_ws = nullptr;
     ~Dev() {
       if (ws) (void)hipFree(ws);
       if (rgb) (void)hipFree(rgb);
+      if (guides) (void)hipFree(guides);
+      if (dn_ws) (void)hipFree(dn_ws);
       rtw_accum_destroy(acc);
       rtw_scene_destroy(sc);
       rtw_world_destroy(w);
@@ -395,6 +398,16 @@ std::vector<uint8_t> renderProgressive(const rtw_camera& cam, const rtw_params& 
   std::vector<uint8_t> rgb((size_t)p.width * p.row_count * 3);
   if (hipMalloc(&d.ws, wsb) != hipSuccess || hipMalloc(&d.rgb, rgb.size()) != hipSuccess)
     throw Error(RTW_ENOMEM, "renderProgressive: device allocation failed");
+  size_t dn_bytes = 0;
+  if (denoise) {  // the guides, once per run
+    dn_bytes = rtw_accum_denoise_workspace_bytes(d.acc, denoise);
+    if (dn_bytes == 0) throw Error(RTW_EINVAL, rtw_last_error());
+    if (hipMalloc(&d.guides, (size_t)p.width * p.row_count * sizeof(rtw_guide)) != hipSuccess ||
+        hipMalloc(&d.dn_ws, dn_bytes) != hipSuccess)
+      throw Error(RTW_ENOMEM, "renderProgressive: device allocation failed");
+    ok(scene ? rtw_scene_guides_device(d.sc, &cam, &p, static_cast<rtw_guide*>(d.guides), nullptr)
+             : rtw_world_guides_device(d.w, &cam, &p, static_cast<rtw_guide*>(d.guides), nullptr));
+  }
   uint32_t done = 0;
   for (uint32_t pass = 1; done < p.spp; ++pass) {
     if (budget) {  // every pixel within its budget: the frame is done
@@ -405,7 +418,11 @@ std::vector<uint8_t> renderProgressive(const rtw_camera& cam, const rtw_params& 
     const uint32_t n = std::min(pass_spp, p.spp - done);
     ok(scene ? rtw_accum_render_device(d.acc, d.sc, &cam, n, d.ws, wsb, nullptr, nullptr)
              : rtw_accum_world_render_device(d.acc, d.w, &cam, n, d.ws, wsb, nullptr, nullptr));
-    ok(rtw_accum_resolve_device(d.acc, static_cast<uint8_t*>(d.rgb), nullptr, nullptr));
+    if (denoise)
+      ok(rtw_accum_denoise_device(d.acc, static_cast<const rtw_guide*>(d.guides), denoise, d.dn_ws, dn_bytes,
+                                  static_cast<uint8_t*>(d.rgb), nullptr, nullptr));
+    else
+      ok(rtw_accum_resolve_device(d.acc, static_cast<uint8_t*>(d.rgb), nullptr, nullptr));
     if (hipMemcpy(rgb.data(), d.rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)
       throw Error(RTW_EHIP, "renderProgressive: the pass failed on the device");
     ok(rtw_accum_samples(d.acc, &done));

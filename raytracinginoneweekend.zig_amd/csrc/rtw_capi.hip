@@ -892,6 +892,23 @@ int rtw_render_device(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, 
   return launch_all(sc, cam, p, workspace, ws_bytes, d_rgb, d_mean, static_cast<hipStream_t>(stream), timer, 0);
 }
 
+// The scene's feature buffers (rtw_guides.hip).
+int rtw_scene_guides_device(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, rtw_guide* d_guides,
+                            void* stream) {
+  if (!sc) return fail(RTW_EINVAL, "rtw_scene_guides_device: scene is NULL");
+  rtwk::SceneGuideArgs a;
+  const int st = rtw_guide_ray_fill(a.r, "rtw_scene_guides_device", cam, p, d_guides);
+  if (st != RTW_OK) return st;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != sc->device)
+    return fail(RTW_EINVAL, "rtw_scene_guides_device: scene lives on device %d, current is %d", sc->device, dev);
+  a.sc = sc->v64;
+  const hipError_t e = rtwk::launch_scene_guides(a, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(RTW_EHIP, "guide kernel launch: %s", hipGetErrorString(e));
+  return RTW_OK;
+}
+
 // The statistics pass: one render in counting mode, the kernels' 32 statistics
 // words copied back (rtw_hip.h RTW_STAT_*; words 16.. are the diagnostic
 // build's phase stamps).

@@ -54,6 +54,8 @@ void rtw_fill_trace_args(rtwk::TraceArgs<double>& a, const rtw_camera* cam, cons
                          uint64_t seed_adv);
 int rtw_launch_finalize(const rtw_params* p, unsigned char* ws, uint8_t* d_rgb, float* d_mean, hipStream_t s);
 int rtw_timer_mark(rtw_timer t, hipStream_t s, bool start);
+// feature buffers (rtw_guides.hip): checks the arguments of a guide entry and fills the feature ray
+int rtw_guide_ray_fill(rtwk::GuideRay& g, const char* who, const rtw_camera* cam, const rtw_params* p, void* d_guides);
 // accumulator passes
 bool rtw_accum_size_params(const rtw_params* p, uint32_t n, rtw_params* pp);
 int rtw_accum_pass_begin(rtw_accum a, uint32_t pass_spp, rtw_params* pp, uint64_t* seed_adv);

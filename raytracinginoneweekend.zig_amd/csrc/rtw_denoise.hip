@@ -1,0 +1,270 @@
+// rtw_denoise.hip — device side of the feature-guided denoiser (rtw_hip.h
+// rtw_denoise_device, rtw_accum_variance_device, rtw_accum_denoise_device;
+// DESIGN.md §14).  The filter itself is rtw_denoise.hpp's filter_pixel, the
+// function rtw_denoise_host runs: the kernels here only decide where a tap's
+// records come from, so the device's bytes are the host's.
+//
+// One launch per level.  A workgroup is a tile of 64 x 4 pixels, a wave one row
+// of 64 consecutive x: centre loads and stores are coalesced, and every tap
+// reads whole 16-byte records (colour + variance one dwordx4, the guide two).
+//   direct form: a tap reads global memory (the working set, 48 B per pixel,
+//                stays in L2 / the Infinity Cache between levels);
+//   tiled form:  tap spacing S = 1 or 2 — the tile's footprint with its halo
+//                of 2 S pixels, (64 + 4 S) x (4 + 4 S) records, is staged in LDS
+//                first (S = 2: 864 records, 40.5 KiB); a cell outside the image
+//                is staged as an empty pixel, which filter_pixel drops as it
+//                drops the out-of-image tap.  Wider spacings do not fit.
+// Which form runs a level: kTiledMaxStep, chosen by the A/B in DESIGN.md §14.
+// The first level reads the caller's mean (3 floats) and variance, the last one
+// writes the caller's mean and rgb8; the levels between ping-pong in the
+// workspace.  No atomics, no state.  -ffp-contract=off (Makefile).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "rtw_adaptive.hpp"
+#include "rtw_capi_shared.hpp"
+#include "rtw_denoise.hpp"
+
+namespace rtwk {
+
+namespace {
+
+using rtwd::Guide;
+using rtwd::Px;
+
+constexpr int kDnTileW = 64, kDnTileH = 4;  // a wave = one row of the tile
+constexpr int kDnBlock = kDnTileW * kDnTileH;
+// Levels of tap spacing <= this run the tiled form (0: none).
+#ifndef RTW_DENOISE_TILED_MAX_STEP
+#define RTW_DENOISE_TILED_MAX_STEP 2
+#endif
+constexpr int kTiledMaxStep = RTW_DENOISE_TILED_MAX_STEP;
+
+struct DenoiseArgs {
+  const float* mean;  // first level: the caller's image
+  const float* var;   // first level: optional
+  const Px* in;       // later levels (null at the first)
+  const Guide* guides;
+  Px* out;            // every level but the last
+  float* mean_out;    // last level (each optional)
+  uint8_t* rgb_out;
+  int W, H, step, last;
+  rtwd::Params P;
+};
+
+__device__ __forceinline__ Px load_px(const DenoiseArgs& A, size_t i) {
+  if (A.in) return A.in[i];  // (uniform)
+  return Px{A.mean[3 * i], A.mean[3 * i + 1], A.mean[3 * i + 2], A.var ? A.var[i] : rtwd::kVarUnknown};
+}
+
+__device__ __forceinline__ void store_px(const DenoiseArgs& A, size_t i, const Px& r) {
+  if (!A.last) {  // (uniform)
+    A.out[i] = r;
+    return;
+  }
+  if (A.mean_out) A.mean_out[3 * i] = r.r, A.mean_out[3 * i + 1] = r.g, A.mean_out[3 * i + 2] = r.b;
+  if (A.rgb_out) {
+    A.rgb_out[3 * i] = rtwd::quantise((double)r.r);
+    A.rgb_out[3 * i + 1] = rtwd::quantise((double)r.g);
+    A.rgb_out[3 * i + 2] = rtwd::quantise((double)r.b);
+  }
+}
+
+// S = 0: the direct form; S = 1, 2: the tiled form for tap spacing S.
+template <bool GUIDES, int S>
+__global__ void __launch_bounds__(kDnBlock) denoise_level_kernel(DenoiseArgs A) {
+  const int lx = (int)(threadIdx.x & (kDnTileW - 1)), ly = (int)(threadIdx.x >> 6);
+  const int x0 = (int)blockIdx.x * kDnTileW, y0 = (int)blockIdx.y * kDnTileH;
+  const int x = x0 + lx, y = y0 + ly;
+  if constexpr (S == 0) {
+    if (x >= A.W || y >= A.H) return;
+    auto px = [&](int qx, int qy) { return load_px(A, (size_t)qy * A.W + qx); };
+    auto gd = [&](int qx, int qy) { return A.guides[(size_t)qy * A.W + qx]; };
+    const Px r = rtwd::filter_pixel<GUIDES>(x, y, A.W, A.H, A.step, A.P, px, gd);
+    store_px(A, (size_t)y * A.W + x, r);
+  } else {
+    constexpr int TW = kDnTileW + 4 * S, TH = kDnTileH + 4 * S;
+    __shared__ Px t_px[TW * TH];
+    __shared__ Guide t_gd[GUIDES ? TW * TH : 1];
+    const int tx0 = x0 - 2 * S, ty0 = y0 - 2 * S;
+    for (int c = (int)threadIdx.x; c < TW * TH; c += kDnBlock) {
+      const int cy = c / TW, cx = c - cy * TW;
+      const int gx = tx0 + cx, gy = ty0 + cy;
+      if (gx >= 0 && gx < A.W && gy >= 0 && gy < A.H) {
+        const size_t i = (size_t)gy * A.W + gx;
+        t_px[c] = load_px(A, i);
+        if constexpr (GUIDES) t_gd[c] = A.guides[i];
+      } else {  // outside the image: an empty pixel (never read as a tap: the filter checks the bounds first)
+        t_px[c] = Px{0.0f, 0.0f, 0.0f, rtwd::kVarEmpty};
+        if constexpr (GUIDES) t_gd[c] = Guide{};
+      }
+    }
+    __syncthreads();
+    if (x >= A.W || y >= A.H) return;
+    auto px = [&](int qx, int qy) { return t_px[(qy - ty0) * TW + (qx - tx0)]; };
+    auto gd = [&](int qx, int qy) { return t_gd[GUIDES ? (qy - ty0) * TW + (qx - tx0) : 0]; };
+    const Px r = rtwd::filter_pixel<GUIDES>(x, y, A.W, A.H, S, A.P, px, gd);
+    store_px(A, (size_t)y * A.W + x, r);
+  }
+}
+
+template <bool GUIDES>
+hipError_t launch_level(const DenoiseArgs& a, bool tiled, hipStream_t s) {
+  const dim3 grid((a.W + kDnTileW - 1) / kDnTileW, (a.H + kDnTileH - 1) / kDnTileH), block(kDnBlock);
+  if (tiled && a.step == 1)
+    hipLaunchKernelGGL((denoise_level_kernel<GUIDES, 1>), grid, block, 0, s, a);
+  else if (tiled && a.step == 2)
+    hipLaunchKernelGGL((denoise_level_kernel<GUIDES, 2>), grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL((denoise_level_kernel<GUIDES, 0>), grid, block, 0, s, a);
+  return hipGetLastError();
+}
+
+// rtw_accum_variance_device: the squared standard error of the pixel's mean
+// luminance (rtw_adaptive.hpp pixel_se2) as an f32, with the pixel's own count
+// in the masked state (cnt), else `done`.
+struct VarianceArgs {
+  const double* stat;
+  const uint32_t* cnt;  // masked state, else null
+  float* var;
+  uint32_t npix, done, chunk;
+};
+__global__ void __launch_bounds__(256) accum_variance_kernel(VarianceArgs V) {
+  const double2* stat2 = reinterpret_cast<const double2*>(V.stat);
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < V.npix; i += gridDim.x * 256u) {
+    const uint32_t n = V.cnt ? V.cnt[i] : V.done;
+    const uint32_t m = n / V.chunk;
+    float v = rtwd::kVarUnknown;
+    if (n == 0u) {
+      v = rtwd::kVarEmpty;
+    } else if (m >= 2u) {
+      const double2 y = stat2[i];
+      v = (float)rtwa::pixel_se2(y.x, y.y, m, V.chunk);
+    }
+    V.var[i] = v;
+  }
+}
+
+}  // namespace
+
+}  // namespace rtwk
+
+namespace {
+
+int hip_fail(const char* what, hipError_t e) { return rtw_fail(RTW_EHIP, "%s: %s", what, hipGetErrorString(e)); }
+
+// The levels of one call on stream s.  force_direct: every level in the direct form.
+int run_levels(const float* d_mean, const float* d_var, const rtw_guide* d_guides, uint32_t W, uint32_t H,
+               const rtwd::Params& P, void* workspace, uint8_t* d_rgb_out, float* d_mean_out, hipStream_t s) {
+  using namespace rtwk;
+  Px* buf[2] = {static_cast<Px*>(workspace),
+                reinterpret_cast<Px*>(static_cast<unsigned char*>(workspace) + rtwd::image_bytes(W, H))};
+  const bool force_direct = (P.flags & rtwd::kFlagDirect) != 0;
+  for (uint32_t l = 0; l < P.levels; ++l) {
+    DenoiseArgs a;
+    a.mean = d_mean;
+    a.var = d_var;
+    a.in = l ? buf[(l - 1) & 1u] : nullptr;
+    a.guides = reinterpret_cast<const Guide*>(d_guides);
+    a.out = buf[l & 1u];
+    a.mean_out = d_mean_out;
+    a.rgb_out = d_rgb_out;
+    a.W = (int)W, a.H = (int)H, a.step = 1 << l;
+    a.last = l + 1 == P.levels;
+    a.P = P;
+    const bool tiled = !force_direct && a.step <= kTiledMaxStep;
+    const hipError_t e = d_guides ? launch_level<true>(a, tiled, s) : launch_level<false>(a, tiled, s);
+    if (e != hipSuccess) return hip_fail("denoise kernel launch", e);
+  }
+  return RTW_OK;
+}
+
+int accum_here(rtw_accum a, const char* who) {
+  if (!a) return rtw_fail(RTW_EINVAL, "%s: accumulator is NULL", who);
+  int dev = 0;
+  const hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_fail("hipGetDevice", e);
+  if (dev != a->device)
+    return rtw_fail(RTW_EINVAL, "%s: accumulator lives on device %d but the current device is %d", who, a->device, dev);
+  return RTW_OK;
+}
+
+size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+int rtw_denoise_device(const float* d_mean, const float* d_var, const rtw_guide* d_guides, uint32_t W, uint32_t H,
+                       const rtw_denoise_opts* o, void* workspace, size_t workspace_bytes, uint8_t* d_rgb_out,
+                       float* d_mean_out, void* stream) {
+  const rtw_denoise_opts dflt{};
+  if (!o) o = &dflt;
+  rtwd::Params P;
+  const int st = rtwd::check_call("rtw_denoise_device", d_mean, W, H, o->levels, o->sigma_color, o->sigma_normal,
+                                  o->sigma_depth, o->sigma_albedo, o->flags, workspace, workspace_bytes, d_rgb_out,
+                                  d_mean_out, P);
+  if (st != RTW_OK) return st;
+  if (((uintptr_t)d_guides & 15u) != 0) return rtw_fail(RTW_EINVAL, "rtw_denoise_device: d_guides is not 16-byte aligned");
+  return run_levels(d_mean, d_var, d_guides, W, H, P, workspace, d_rgb_out, d_mean_out, static_cast<hipStream_t>(stream));
+}
+
+int rtw_accum_variance_device(rtw_accum a, float* d_var, void* stream) {
+  const int st = accum_here(a, "rtw_accum_variance_device");
+  if (st != RTW_OK) return st;
+  if (!d_var) return rtw_fail(RTW_EINVAL, "rtw_accum_variance_device: d_var is NULL");
+  if (a->done == 0) return rtw_fail(RTW_EINVAL, "rtw_accum_variance_device: no sample accumulated yet");
+  rtwk::VarianceArgs v;
+  v.stat = a->stat;
+  v.cnt = a->masked ? a->cnt : nullptr;
+  v.var = d_var;
+  v.npix = a->npix;
+  v.done = a->done;
+  v.chunk = a->chunk;
+  const uint32_t grid = std::min((a->npix + 255u) / 256u, 2048u);
+  hipLaunchKernelGGL(rtwk::accum_variance_kernel, dim3(grid ? grid : 1), dim3(256), 0, static_cast<hipStream_t>(stream), v);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail("variance kernel launch", e);
+  return RTW_OK;
+}
+
+// Workspace of rtw_accum_denoise_device: the filter's two images, then the
+// resolved mean (npix x 3 f32), the variance (npix f32) and the resolve's rgb8.
+size_t rtw_accum_denoise_workspace_bytes(rtw_accum a, const rtw_denoise_opts* o) {
+  if (!a) {
+    rtw_fail(RTW_EINVAL, "rtw_accum_denoise_workspace_bytes: accumulator is NULL");
+    return 0;
+  }
+  const size_t f = rtw_denoise_workspace_bytes(a->p.width, a->p.row_count, o);
+  if (f == 0) return 0;
+  return f + al256((size_t)a->npix * 12) + al256((size_t)a->npix * 4) + al256((size_t)a->npix * 3);
+}
+
+int rtw_accum_denoise_device(rtw_accum a, const rtw_guide* d_guides, const rtw_denoise_opts* o, void* workspace,
+                             size_t workspace_bytes, uint8_t* d_rgb, float* d_mean, void* stream) {
+  int st = accum_here(a, "rtw_accum_denoise_device");
+  if (st != RTW_OK) return st;
+  if (a->p.row_stride != 1)
+    return rtw_fail(RTW_UNSUPPORTED, "rtw_accum_denoise_device: row_stride %u: the filter needs contiguous image rows",
+                    a->p.row_stride);
+  if (a->done == 0) return rtw_fail(RTW_EINVAL, "rtw_accum_denoise_device: no sample accumulated yet");
+  if (!workspace) return rtw_fail(RTW_EINVAL, "rtw_accum_denoise_device: workspace is NULL");
+  const size_t need = rtw_accum_denoise_workspace_bytes(a, o);
+  if (need == 0) return RTW_EINVAL;
+  if (workspace_bytes < need)
+    return rtw_fail(RTW_EINVAL, "rtw_accum_denoise_device: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  const uint32_t W = a->p.width, H = a->p.row_count;
+  const size_t f = 2 * rtwd::image_bytes(W, H);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  float* mean = reinterpret_cast<float*>(ws + f);
+  float* var = reinterpret_cast<float*>(ws + f + al256((size_t)a->npix * 12));
+  uint8_t* rgb = ws + f + al256((size_t)a->npix * 12) + al256((size_t)a->npix * 4);
+  st = rtw_accum_resolve_device(a, rgb, mean, stream);
+  if (st != RTW_OK) return st;
+  st = rtw_accum_variance_device(a, var, stream);
+  if (st != RTW_OK) return st;
+  return rtw_denoise_device(mean, var, d_guides, W, H, o, workspace, f, d_rgb, d_mean, stream);
+}
+
+}  // extern "C"

@@ -213,10 +213,16 @@ struct PassInfo {
   double noise;      // rtw_accum_noise, < 0 while fewer than two full chunks are in
 };
 using PassFn = std::function<void(const PassInfo&, const std::vector<uint8_t>& rgb)>;
+// `denoise` (optional): every image the loop hands out — each
+// pass's and the returned one — is the feature-guided denoiser's
+// (rtw_accum_denoise_device) instead of the plain resolve; the guides are
+// computed once, before the first pass.  The accumulator, and so the noise
+// estimates and the adaptive counts, are the undenoised run's.
 std::vector<uint8_t> renderProgressive(const rtw_camera& cam, const rtw_params& p, uint32_t pass_spp,
                                        const FlatScene* scene, const rtw_world_desc* world, double max_noise,
                                        const PassFn& on_pass, uint32_t* samples_used,
-                                       const AdaptiveOpts* adaptive = nullptr);
+                                       const AdaptiveOpts* adaptive = nullptr,
+                                       const rtw_denoise_opts* denoise = nullptr);
 // The sample-count map as a binary PGM: 8-bit when the largest count fits, else 16-bit (big-endian).
 void writeCountsPGM(const std::string& path, const std::vector<uint32_t>& counts, uint32_t w, uint32_t h);
 

@@ -390,4 +390,28 @@ int world_blocks_per_cu(size_t lds, int occ, int fs);
 constexpr int kWorldBlock = 256;
 size_t world_lds_bytes(uint32_t n_perlins, int fs);
 
+// ------------------------------------------------------- feature buffers --
+// rtw_guides.hip (scenes) / rtw_world.hip (worlds): one rtw_guide per output
+// pixel from the pixel's feature ray (rtw_hip.h) — Camera.getRay
+// with its random draws replaced by their means, in f64.  One lane per pixel,
+// a workgroup = kGuideTileW x kGuideTileH pixels (a wave = one row).
+constexpr uint32_t kGuideTileW = 64, kGuideTileH = 4;
+struct GuideRay {
+  double origin[3], horizontal[3], vertical[3], llc[3];
+  double time;   // time0 + 0.5 * (time1 - time0)
+  double bg[3];  // a miss's albedo
+  uint32_t W, H, row_begin, row_stride, row_count;
+  void* out;     // [row_count][W] rtw_guide
+};
+struct SceneGuideArgs {
+  SceneView<double> sc;
+  GuideRay r;
+};
+struct WorldGuideArgs {
+  WorldView w;
+  GuideRay r;
+};
+hipError_t launch_scene_guides(const SceneGuideArgs& a, hipStream_t s);
+hipError_t launch_world_guides(const WorldGuideArgs& a, hipStream_t s);
+
 }  // namespace rtwk

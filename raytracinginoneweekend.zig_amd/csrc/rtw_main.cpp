@@ -7,6 +7,7 @@
 //              [--chunk C] [--image earth.png] [--out out.ppm]
 //              [--pass-spp N [--preview-dir DIR] [--max-noise X]
 //                            [--pixel-noise X [--min-spp N] [--spp-map FILE]]]
+//              [--denoise [--denoise-levels N]]
 // --pass-spp N renders the frame progressively, N samples per pass (a multiple
 // of the chunk): the same --out bytes as without it.  --preview-dir DIR writes
 // the image after every pass to DIR/pass_NNNN.ppm; --max-noise X stops once the
@@ -16,12 +17,18 @@
 // when every pixel has stopped or at --spp, and each pixel of --out is the
 // one-shot render's with that pixel's own sample count; --spp-map FILE writes
 // the counts as a binary PGM (8-bit, or 16-bit when a count exceeds 255).
+// --denoise writes the feature-guided denoiser's image to --out
+// and to every preview of --preview-dir: the guides are computed once per run,
+// the frame goes through the accumulator (as one pass of --spp samples without
+// --pass-spp) and is filtered with --denoise-levels N iterations (1-6, default
+// 5).  Without --denoise the output bytes are unchanged.
 // Defaults are the reference's: scene 6 (main.zig:313) with that scene's own
 // size, spp, camera and background (main.zig:316-362); --width/--aspect/--spp
 // override them.  Scenes 4 and 7 need --image (assets/sekaichizu.png).
 #include <sys/stat.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -120,8 +127,16 @@ int main(int argc, char** argv) {
   double aspect = 0, max_noise = 0, pixel_noise = 0;
   uint64_t seed = 42;
   std::string out = "out.ppm", image_path, preview_dir, spp_map;
-  for (int i = 1; i + 1 < argc; i += 2) {
+  bool denoise = false;
+  uint32_t denoise_levels = 0;
+  for (int i = 1; i < argc; i += 2) {
     const std::string k = argv[i];
+    if (k == "--denoise") {  // (the one option without a value)
+      denoise = true;
+      --i;
+      continue;
+    }
+    if (i + 1 >= argc) break;
     const char* v = argv[i + 1];
     if (k == "--scene") scene = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--width") width = (uint32_t)std::strtoul(v, nullptr, 10);
@@ -140,6 +155,7 @@ int main(int argc, char** argv) {
     else if (k == "--pixel-noise") pixel_noise = std::atof(v);
     else if (k == "--min-spp") min_spp = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--spp-map") spp_map = v;
+    else if (k == "--denoise-levels") denoise_levels = (uint32_t)std::strtoul(v, nullptr, 10);
     else {
       std::fprintf(stderr, "unknown option %s\n", k.c_str());
       return 2;
@@ -147,6 +163,10 @@ int main(int argc, char** argv) {
   }
   if (pass_spp == 0 && (!preview_dir.empty() || max_noise > 0 || pixel_noise > 0)) {
     std::fprintf(stderr, "--preview-dir, --max-noise and --pixel-noise need --pass-spp\n");
+    return 2;
+  }
+  if (denoise_levels && !denoise) {
+    std::fprintf(stderr, "--denoise-levels needs --denoise\n");
     return 2;
   }
   if (!(pixel_noise > 0) && (min_spp || !spp_map.empty())) {
@@ -168,6 +188,19 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> counts;
     rtw::AdaptiveOpts adaptive;
     adaptive.pixel_noise = pixel_noise, adaptive.min_spp = min_spp, adaptive.counts = &counts;
+    rtw_denoise_opts dn;
+    std::memset(&dn, 0, sizeof(dn));
+    dn.levels = denoise_levels;
+    if (denoise && pass_spp == 0) pass_spp = S;  // the whole frame as one pass of the accumulator
+    if (denoise) {
+      // The colour term needs a variance, and the variance two full chunks (without it the
+      // filter blurs what no guide describes — reflections, shadows — and a 20-spp preview gets worse).
+      const uint32_t c = std::min(chunk ? chunk : RTW_DEFAULT_CHUNK, S);
+      if (std::min(pass_spp, S) / c < 2)
+        std::fprintf(stderr,
+                     "note: the first image holds fewer than two chunks of %u samples, so its variance is unknown and the "
+                     "denoiser's colour term is off for it; --chunk %u gives it one\n", c, std::max(1u, std::min(pass_spp, S) / 2));
+    }
     // --pass-spp: the frame through the accumulator, a preview per pass
     auto progressive = [&](const rtw_params& p, const rtw::FlatScene* fs, const rtw_world_desc* wd) {
       if (!preview_dir.empty()) (void)mkdir(preview_dir.c_str(), 0777);  // (an existing directory is fine)
@@ -179,7 +212,7 @@ int main(int argc, char** argv) {
                                       std::snprintf(name, sizeof(name), "/pass_%04u.ppm", i.pass);
                                       rtw::writePPM(preview_dir + name, img, W, H);
                                     },
-                                    &used, pixel_noise > 0 ? &adaptive : nullptr);
+                                    &used, pixel_noise > 0 ? &adaptive : nullptr, denoise ? &dn : nullptr);
     };
     rtw_params p;
     std::memset(&p, 0, sizeof(p));

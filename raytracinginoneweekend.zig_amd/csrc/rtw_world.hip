@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "rtw_device.hpp"
+#include "rtw_guides.hpp"
 #include "rtw_libm.hpp"
 
 // (Measured choices that are now the only code: the BVH stack's top entry in a
@@ -768,6 +769,80 @@ __device__ __forceinline__ V tex_value(const WV& W, uint32_t ti, D u, D v, V p) 
     default:
       return ld3(t + 2);
   }
+}
+
+// The world's feature buffers (rtw_hip.h rtw_world_guides_device, DESIGN.md
+// §14): one lane per pixel, the pixel's feature ray through the reference's
+// literal sequential loop (seq_hit: no BVH, no LDS — the kernel runs once per
+// frame, and the loop is the one traversal with nothing to get wrong), then the
+// winner's hit record and texture value as world_kernel's shade computes them.
+// The general feature set: every primitive, texture and transform.
+__global__ void __launch_bounds__(kGuideTileW* kGuideTileH) world_guides_kernel(WorldGuideArgs A) {
+  uint32_t x, q;
+  if (!guide_pixel(A.r, x, q)) return;
+  const WorldView& W = A.w;
+  V o0, d0;
+  guide_ray(A.r, x, q, o0, d0);
+  const D time = A.r.time;
+  WHit h;
+  h.nan = 0u;
+  seq_hit<kFeatAll>(W, W.order, o0, d0, time, (D)0.001, h);
+  if (h.pos < 0) {
+    guide_store(A.r, x, q, mk(0.0, 0.0, 0.0), 0.0, ld3(A.r.bg), 0u);
+    return;
+  }
+  const D* r = W.prim + kWorldRec * h.pos;
+  const uint32_t* mt = meta_of(r);
+  const uint32_t kind = mt[0] & 0xFFu;
+  const int xf = (int)(mt[0] >> 8) - 1;
+  V o = o0, d = d0;
+  if (xf >= 0) to_object(W.xform + kWorldRec * xf, o, d);
+  V p = add(o, mul(d, h.t)), nrm;
+  D tu = 0.0, tv = 0.0;
+  const D* mp = W.mat + 8 * mt[1];
+  const uint32_t* mh = reinterpret_cast<const uint32_t*>(mp);
+  const uint32_t mkind = mh[0], mtex = mh[1];
+  const bool image_tex =
+      (mkind == 0u || mkind == 3u) && *reinterpret_cast<const uint32_t*>(W.tex + kWorldRec * mtex) == 3u;
+  if (kind <= 1u) {
+    V c = ld3(r);
+    if (kind == 1u) c = add(c, mul(ld3(r + 3), (time - r[7]) / r[8]));
+    const V outward = divs(sub(p, c), r[6]);
+    nrm = dot(outward, d) < 0.0 ? outward : mul(outward, -1.0);
+    if (kind == 0u && image_tex) {  // getSphereUv (hittable.zig:145-150)
+      const D pi = 3.14159265358979323846;
+      tu = (rtwl::atan2(-outward.z, outward.x) + pi) / (2.0 * pi);
+      tv = rtwl::acos(-outward.y) / pi;
+    }
+  } else {
+    D oa, ob, da, db;
+    V n0;
+    if (kind == 2u) {
+      oa = o.x, ob = o.y, da = d.x, db = d.y, n0 = mk(0.0, 0.0, 1.0);
+    } else if (kind == 3u) {
+      oa = o.x, ob = o.z, da = d.x, db = d.z, n0 = mk(0.0, 1.0, 0.0);
+    } else {
+      oa = o.y, ob = o.z, da = d.y, db = d.z, n0 = mk(1.0, 0.0, 0.0);
+    }
+    tu = (oa + h.t * da - r[0]) / r[5];
+    tv = (ob + h.t * db - r[2]) / r[6];
+    nrm = dot(n0, d) < 0.0 ? n0 : mul(n0, -1.0);
+  }
+  if (xf >= 0) to_world(W.xform + kWorldRec * xf, p, nrm);
+  V albedo;
+  if (mkind == 1u)
+    albedo = ld3(mp + 1);
+  else if (mkind == 2u)
+    albedo = mk(1.0, 1.0, 1.0);
+  else
+    albedo = tex_value<kFeatAll>(W, mtex, tu, tv, p);
+  guide_store(A.r, x, q, nrm, h.t, albedo, (uint32_t)h.orig + 1u);
+}
+
+hipError_t launch_world_guides(const WorldGuideArgs& a, hipStream_t s) {
+  const dim3 grid((a.r.W + kGuideTileW - 1) / kGuideTileW, (a.r.row_count + kGuideTileH - 1) / kGuideTileH);
+  hipLaunchKernelGGL(world_guides_kernel, grid, dim3(kGuideTileW * kGuideTileH), 0, s, a);
+  return hipGetLastError();
 }
 
 // OCC: minimum resident workgroups per CU asked of the register allocator

@@ -292,6 +292,23 @@ int rtw_world_render_device(rtw_world w, const rtw_camera* cam, const rtw_params
   return world_launch(w, cam, p, ws, ws_bytes, d_rgb, d_mean, static_cast<hipStream_t>(stream), timer, 0);
 }
 
+// The world's feature buffers (rtw_world.hip world_guides_kernel).
+int rtw_world_guides_device(rtw_world w, const rtw_camera* cam, const rtw_params* p, rtw_guide* d_guides,
+                            void* stream) {
+  if (!w) return rtw_fail(RTW_EINVAL, "rtw_world_guides_device: world is NULL");
+  rtwk::WorldGuideArgs a;
+  const int st = rtw_guide_ray_fill(a.r, "rtw_world_guides_device", cam, p, d_guides);
+  if (st != RTW_OK) return st;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != w->device)
+    return rtw_fail(RTW_EINVAL, "rtw_world_guides_device: world lives on device %d, current is %d", w->device, dev);
+  a.w = w->view;
+  const hipError_t e = rtwk::launch_world_guides(a, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "guide kernel launch: %s", hipGetErrorString(e));
+  return RTW_OK;
+}
+
 size_t rtw_accum_world_workspace_bytes(rtw_world w, const rtw_params* p, uint32_t pass_spp) {
   rtw_params pp;
   if (!w || !rtw_accum_size_params(p, pass_spp, &pp)) return 0;

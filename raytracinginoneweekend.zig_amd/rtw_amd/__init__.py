@@ -76,6 +76,28 @@ class Params(C.Structure):
                 ("wf_bounces", C.c_uint32), ("wf_passes", C.c_uint32)]
 
 
+class Guide(C.Structure):
+    """rtw_guide: a pixel's first-hit features (32 bytes)."""
+    _fields_ = [("normal", C.c_float * 3), ("depth", C.c_float), ("albedo", C.c_float * 3), ("prim", C.c_uint32)]
+
+
+GUIDE_DTYPE = np.dtype([("normal", np.float32, 3), ("depth", np.float32), ("albedo", np.float32, 3),
+                        ("prim", np.uint32)])
+VAR_UNKNOWN, VAR_EMPTY = -1.0, -2.0  # rtw_hip.h RTW_VAR_*
+DENOISE_NO_COLOR, DENOISE_DIRECT = 1, 2  # rtw_denoise_opts.flags
+
+
+class DenoiseOpts(C.Structure):
+    """rtw_denoise_opts: every field 0 = its default."""
+    _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_double), ("sigma_normal", C.c_double),
+                ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double), ("flags", C.c_uint32)]
+
+
+def denoise_opts(levels=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, sigma_albedo=0.0,
+                 flags=0) -> DenoiseOpts:
+    return DenoiseOpts(levels, sigma_color, sigma_normal, sigma_depth, sigma_albedo, flags)
+
+
 _lib = None
 
 
@@ -147,6 +169,19 @@ def lib() -> C.CDLL:
         L.rtw_accum_active.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_uint32)]
         L.rtw_accum_read_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.rtw_accum_load_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    if hasattr(L, "rtw_denoise_device"):  # feature-guided denoiser (an older A/B build has none)
+        for f in (L.rtw_scene_guides_device, L.rtw_world_guides_device):
+            f.argtypes = [C.c_void_p, P(Camera), P(Params), C.c_void_p, C.c_void_p]
+        L.rtw_denoise_workspace_bytes.restype = C.c_size_t
+        L.rtw_denoise_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32, P(DenoiseOpts)]
+        for f in (L.rtw_denoise_device, L.rtw_denoise_host):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(DenoiseOpts), C.c_void_p,
+                          C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rtw_accum_variance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rtw_accum_denoise_workspace_bytes.restype = C.c_size_t
+        L.rtw_accum_denoise_workspace_bytes.argtypes = [C.c_void_p, P(DenoiseOpts)]
+        L.rtw_accum_denoise_device.argtypes = [C.c_void_p, C.c_void_p, P(DenoiseOpts), C.c_void_p, C.c_size_t,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -302,6 +337,12 @@ class DeviceScene:
                                        C.c_void_p(stream) if stream else None,
                                        timer.h if timer is not None else None))
 
+    def guides(self, cam: Camera, params: Params, guides_ptr: int, stream: int | None = None):
+        """The scene's feature buffers (rtw_scene_guides_device): row_count x W rtw_guide
+        records (32 bytes each) into device memory, asynchronous on `stream`."""
+        _check(lib().rtw_scene_guides_device(self.h, C.byref(cam), C.byref(params), C.c_void_p(guides_ptr),
+                                             C.c_void_p(stream) if stream else None))
+
     def counts(self, cam: Camera, params: Params, workspace_ptr: int, workspace_bytes_: int) -> dict:
         out = (C.c_uint64 * 6)()
         _check(lib().rtw_render_counts_ex(self.h, C.byref(cam), C.byref(params), C.c_void_p(workspace_ptr),
@@ -326,6 +367,45 @@ class DeviceScene:
             self.close()
         except Exception:
             pass
+
+
+def denoise_workspace_bytes(width: int, height: int, opts: DenoiseOpts | None = None) -> int:
+    n = lib().rtw_denoise_workspace_bytes(width, height, C.byref(opts) if opts is not None else None)
+    if n == 0:
+        _check(RTW_EINVAL)
+    return int(n)
+
+
+def denoise_host(mean, var=None, guides=None, opts: DenoiseOpts | None = None):
+    """The denoiser on the CPU (rtw_denoise_host; needs no GPU): mean (H, W, 3)
+    f32, var (H, W) f32 or None, guides (H, W) GUIDE_DTYPE or None ->
+    (rgb (H, W, 3) uint8, mean (H, W, 3) f32).  The device entries give these bytes."""
+    m = np.ascontiguousarray(mean, np.float32)
+    h, w = m.shape[:2]
+    v = None if var is None else np.ascontiguousarray(var, np.float32)
+    g = None if guides is None else np.ascontiguousarray(guides, GUIDE_DTYPE)
+    if (v is not None and v.size != h * w) or (g is not None and g.size != h * w):
+        raise ValueError("var / guides do not have the image's size")
+    nbytes = denoise_workspace_bytes(w, h, opts)
+    ws = np.empty(nbytes // 16 + 1, np.dtype([("p", np.float32, 4)]))  # (16-byte records; numpy aligns to 16)
+    ptr = (ws.ctypes.data + 15) & ~15
+    rgb, out = np.empty((h, w, 3), np.uint8), np.empty((h, w, 3), np.float32)
+    _check(lib().rtw_denoise_host(m.ctypes.data, v.ctypes.data if v is not None else None,
+                                  g.ctypes.data if g is not None else None, w, h,
+                                  C.byref(opts) if opts is not None else None, C.c_void_p(ptr),
+                                  ws.nbytes - (ptr - ws.ctypes.data), rgb.ctypes.data, out.ctypes.data, None))
+    return rgb, out
+
+
+def denoise_device(mean_ptr: int, var_ptr: int | None, guides_ptr: int | None, width: int, height: int,
+                   opts: DenoiseOpts | None, workspace_ptr: int, workspace_bytes_: int, rgb_ptr: int | None,
+                   mean_out_ptr: int | None, stream: int | None = None):
+    """rtw_denoise_device on plain device buffers, asynchronous on `stream`."""
+    def vp(x):
+        return C.c_void_p(x) if x else None
+    _check(lib().rtw_denoise_device(vp(mean_ptr), vp(var_ptr), vp(guides_ptr), width, height,
+                                    C.byref(opts) if opts is not None else None, vp(workspace_ptr), workspace_bytes_,
+                                    vp(rgb_ptr), vp(mean_out_ptr), vp(stream)))
 
 
 def effective_chunk(params: Params) -> int:
@@ -383,6 +463,27 @@ class Accumulator:
         """The image of the samples so far into device buffers (rtw_accum_resolve_device)."""
         _check(lib().rtw_accum_resolve_device(self.h, C.c_void_p(rgb_ptr), C.c_void_p(mean_ptr) if mean_ptr else None,
                                               C.c_void_p(stream) if stream else None))
+
+    def variance(self, var_ptr: int, stream: int | None = None):
+        """Per-pixel variance of the mean luminance, (rows, W) f32 into device memory
+        (rtw_accum_variance_device): VAR_UNKNOWN below two full chunks, VAR_EMPTY without a sample."""
+        _check(lib().rtw_accum_variance_device(self.h, C.c_void_p(var_ptr), C.c_void_p(stream) if stream else None))
+
+    def denoise_workspace_bytes(self, opts: DenoiseOpts | None = None) -> int:
+        n = lib().rtw_accum_denoise_workspace_bytes(self.h, C.byref(opts) if opts is not None else None)
+        if n == 0:
+            _check(RTW_EINVAL)
+        return int(n)
+
+    def denoise(self, guides_ptr: int | None, workspace_ptr: int, workspace_bytes_: int, rgb_ptr: int | None,
+                mean_ptr: int | None = None, opts: DenoiseOpts | None = None, stream: int | None = None):
+        """The denoised image of the samples so far (rtw_accum_denoise_device: resolve,
+        variance, filter) into device buffers.  The accumulator is not modified."""
+        def vp(x):
+            return C.c_void_p(x) if x else None
+        _check(lib().rtw_accum_denoise_device(self.h, vp(guides_ptr), C.byref(opts) if opts is not None else None,
+                                              vp(workspace_ptr), workspace_bytes_, vp(rgb_ptr), vp(mean_ptr),
+                                              vp(stream)))
 
     def samples(self) -> int:
         n = C.c_uint32()

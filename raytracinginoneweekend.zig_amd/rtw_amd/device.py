@@ -121,6 +121,30 @@ class TorchAccumulator:
             if max_noise is not None and self.acc.samples() >= 2 * self.acc.chunk and self.noise() <= max_noise:
                 return
 
+    def guides(self, cam: Camera) -> torch.Tensor:
+        """The frame's feature buffers (rtw_guide records as (rows, W, 32) uint8) from the
+        accumulator's scene or world, on torch's current stream.  Compute them once per frame."""
+        p = self.params
+        g = torch.empty((p.row_count, p.width, 32), dtype=torch.uint8, device=self.device)
+        self.acc.target.guides(cam, p, g.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        return g
+
+    def denoised(self, guides: torch.Tensor | None = None, opts=None):
+        """(rgb uint8, mean f32) tensors of the denoised image of the samples so far
+        (rtw_accum_denoise_device), on torch's current stream; `guides` from guides(), or
+        None for the variance-guided filter alone.  The accumulator is not modified."""
+        need = self.acc.denoise_workspace_bytes(opts)
+        if getattr(self, "_dn_ws", None) is None or self._dn_ws.numel() < need + 256:
+            self._dn_ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        base = self._dn_ws.data_ptr()
+        ptr = (base + 255) & ~255
+        shape = (self.params.row_count, self.params.width, 3)
+        rgb = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        mean = torch.empty(shape, dtype=torch.float32, device=self.device)
+        self.acc.denoise(guides.data_ptr() if guides is not None else None, ptr, self._dn_ws.numel() - (ptr - base),
+                         rgb.data_ptr(), mean.data_ptr(), opts, torch.cuda.current_stream(self.device).cuda_stream)
+        return rgb, mean
+
     def noise(self) -> float:
         return self.acc.noise(torch.cuda.current_stream(self.device).cuda_stream)
 

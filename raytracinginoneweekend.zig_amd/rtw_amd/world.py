@@ -304,6 +304,12 @@ class DeviceWorld:
                                                C.c_void_p(stream) if stream else None,
                                                timer.h if timer is not None else None))
 
+    def guides(self, cam: Camera, params: Params, guides_ptr: int, stream: int | None = None):
+        """The world's feature buffers (rtw_world_guides_device): row_count x W rtw_guide
+        records (32 bytes each) into device memory, asynchronous on `stream`."""
+        _check(_wlib().rtw_world_guides_device(self.h, C.byref(cam), C.byref(params), C.c_void_p(guides_ptr),
+                                               C.c_void_p(stream) if stream else None))
+
     def launch_info(self, params: Params) -> dict:
         """rtw_world_launch_info: how a render with these params launches on the
         current device — the traversal that runs (after AUTO and the world's
