@@ -567,6 +567,8 @@ int rtw_world_guides_device(rtw_world world, const rtw_camera *cam, const rtw_pa
 #define RTW_DENOISE_NO_COLOR 1u   /* flags bit 0: drop the colour term */
 #define RTW_DENOISE_DIRECT 2u     /* flags bit 1: every level reads its taps from global memory, none through
                                      LDS tiles (the same bytes; for measurement) */
+#define RTW_DENOISE_SPATIAL_VAR 4u /* flags bit 2: before the first level every RTW_VAR_UNKNOWN variance (all of
+                                     them when d_var is NULL) is replaced by the spatial estimate below */
 #define RTW_DENOISE_MAX_LEVELS 6u
 typedef struct {
   uint32_t levels;                /* 1..6, 0 = 5 */
@@ -602,6 +604,29 @@ int rtw_denoise_host(const float *mean, const float *var, const rtw_guide *guide
                      uint32_t height, const rtw_denoise_opts *opts, void *workspace, size_t workspace_bytes,
                      uint8_t *rgb_out, float *mean_out, void *stream);
 
+/* The spatial variance estimate (csrc/rtw_denoise.hpp
+ * spatial_variance_pixel): for an image of fewer than two chunks, whose
+ * variance the accumulator does not know yet.  var_out (W*H floats) = var_in
+ * with every RTW_VAR_UNKNOWN pixel replaced by the guide-weighted variance of
+ * the mean's luminance over the pixel's 7x7 window — weights: the filter's
+ * normal, depth and albedo terms with the call's sigmas, 1 without guides;
+ * taps outside the image, empty taps and taps across the hit / miss border
+ * dropped.  Known (>= 0) and RTW_VAR_EMPTY pixels come back bit for bit; a
+ * pixel with fewer than 4 usable taps stays RTW_VAR_UNKNOWN.  var_in NULL:
+ * all unknown; guides NULL: unweighted.  Of opts only the three guide sigmas
+ * and RTW_DENOISE_DIRECT (the device reads its taps from global memory, not
+ * through an LDS tile: the same bytes) matter.  No workspace; var_out may not
+ * alias an input.  The device form is asynchronous on `stream`,
+ * graph-capturable, without atomics, and gives the host form's bytes.
+ * rtw_denoise_* with RTW_DENOISE_SPATIAL_VAR give the bytes of the unflagged
+ * call on this map; the workspace sizes are the unflagged ones. */
+int rtw_denoise_spatial_variance_device(const float *d_mean, const float *d_var_in, const rtw_guide *d_guides,
+                                        uint32_t width, uint32_t height, const rtw_denoise_opts *opts,
+                                        float *d_var_out, void *stream);
+int rtw_denoise_spatial_variance_host(const float *mean, const float *var_in, const rtw_guide *guides,
+                                      uint32_t width, uint32_t height, const rtw_denoise_opts *opts, float *var_out,
+                                      void *stream);
+
 /* The accumulator's per-pixel variance, asynchronous on `stream`: d_var
  * (W*row_count floats) = f32 of the squared standard error of the pixel's mean
  * luminance (rtw_accum_noise's per-pixel term, in the mean image's units),
@@ -614,7 +639,9 @@ int rtw_accum_variance_device(rtw_accum a, float *d_var, void *stream);
  * 16-byte aligned — the filter's two images plus the resolved mean, the
  * variance and the resolve's rgb8 (19 bytes per pixel).  The accumulator's
  * state is not modified: passes may continue.  Rows must be contiguous image
- * rows: RTW_UNSUPPORTED when params.row_stride != 1. */
+ * rows: RTW_UNSUPPORTED when params.row_stride != 1.  With
+ * RTW_DENOISE_SPATIAL_VAR the pixels with m < 2 — every pixel after a single
+ * chunk — get the spatial estimate; RTW_VAR_EMPTY pixels stay empty and 0. */
 size_t rtw_accum_denoise_workspace_bytes(rtw_accum a, const rtw_denoise_opts *opts);
 int rtw_accum_denoise_device(rtw_accum a, const rtw_guide *d_guides, const rtw_denoise_opts *opts,
                              void *workspace, size_t workspace_bytes, uint8_t *d_rgb, float *d_mean,

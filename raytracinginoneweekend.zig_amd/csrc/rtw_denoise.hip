@@ -1,6 +1,6 @@
 // rtw_denoise.hip — device side of the feature-guided denoiser (rtw_hip.h
-// rtw_denoise_device, rtw_accum_variance_device, rtw_accum_denoise_device;
-// DESIGN.md §14).  The filter itself is rtw_denoise.hpp's filter_pixel, the
+// rtw_denoise_device, rtw_denoise_spatial_variance_device,
+// rtw_accum_variance_device, rtw_accum_denoise_device).  The filter itself is rtw_denoise.hpp's filter_pixel, the
 // function rtw_denoise_host runs: the kernels here only decide where a tap's
 // records come from, so the device's bytes are the host's.
 //
@@ -17,7 +17,10 @@
 // Which form runs a level: kTiledMaxStep, chosen by the A/B in DESIGN.md §14.
 // The first level reads the caller's mean (3 floats) and variance, the last one
 // writes the caller's mean and rgb8; the levels between ping-pong in the
-// workspace.  No atomics, no state.  -ffp-contract=off (Makefile).
+// workspace.  With RTW_DENOISE_SPATIAL_VAR one launch of spatial_variance_kernel
+// precedes the levels (§14.6); its map lives in the second workspace image,
+// which no level writes before the second.  No atomics, no state.
+// -ffp-contract=off (Makefile).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -121,6 +124,102 @@ hipError_t launch_level(const DenoiseArgs& a, bool tiled, hipStream_t s) {
   return hipGetLastError();
 }
 
+// The spatial variance estimate (rtw_denoise.hpp spatial_variance_pixel) of every pixel.  The same
+// 64 x 4 tile.  Tiled form: the tile's footprint with its halo of 3 pixels, 70 x 10 cells, is staged
+// in LDS once — per cell the luminance as f64, the emptiness, and the guide as two 16-byte halves
+// in two arrays: a row of lanes then reads consecutive 8- and 16-byte words, which ds_read_b64 /
+// ds_read_b128 serve without a bank conflict (the 32-byte record read as two b128 halves would put
+// lanes l and l + 8 of a 16-lane group on one slot: 2-way).  44 bytes x 700 cells = 30 800 bytes.
+// A cell outside the image is staged as empty.  Direct form: every tap reads global memory.
+struct SpatialArgs {
+  const float* mean;
+  const float* var;  // optional: null = all unknown
+  const Guide* guides;
+  float* out;
+  int W, H;
+  rtwd::Params P;
+};
+
+struct alignas(16) GuideHalf {
+  float a, b, c;
+  uint32_t d;  // (depth / prim as bits)
+};
+
+template <bool GUIDES, bool TILED>
+__global__ void __launch_bounds__(kDnBlock) spatial_variance_kernel(SpatialArgs A) {
+  const int lx = (int)(threadIdx.x & (kDnTileW - 1)), ly = (int)(threadIdx.x >> 6);
+  const int x0 = (int)blockIdx.x * kDnTileW, y0 = (int)blockIdx.y * kDnTileH;
+  const int x = x0 + lx, y = y0 + ly;
+  auto load_tap = [&](size_t i) {
+    return rtwd::sv_tap(Px{A.mean[3 * i], A.mean[3 * i + 1], A.mean[3 * i + 2], A.var ? A.var[i] : rtwd::kVarUnknown});
+  };
+  if constexpr (!TILED) {
+    if (x >= A.W || y >= A.H) return;
+    const size_t i = (size_t)y * A.W + x;
+    auto tap = [&](int qx, int qy) { return load_tap((size_t)qy * A.W + qx); };
+    auto gd = [&](int qx, int qy) { return A.guides[(size_t)qy * A.W + qx]; };
+    const float vp = A.var ? A.var[i] : rtwd::kVarUnknown;
+    A.out[i] = rtwd::spatial_variance_pixel<GUIDES>(x, y, A.W, A.H, A.P, vp, tap, gd);
+  } else {
+    constexpr int R = rtwd::kSpatialRadius;
+    constexpr int TW = kDnTileW + 2 * R, TH = kDnTileH + 2 * R;
+    __shared__ double t_y[TW * TH];
+    __shared__ uint32_t t_e[TW * TH];
+    __shared__ GuideHalf t_g0[GUIDES ? TW * TH : 1], t_g1[GUIDES ? TW * TH : 1];
+    const int tx0 = x0 - R, ty0 = y0 - R;
+    for (int c = (int)threadIdx.x; c < TW * TH; c += kDnBlock) {
+      const int cy = c / TW, cx = c - cy * TW;
+      const int gx = tx0 + cx, gy = ty0 + cy;
+      if (gx >= 0 && gx < A.W && gy >= 0 && gy < A.H) {
+        const size_t i = (size_t)gy * A.W + gx;
+        const rtwd::SvTap t = load_tap(i);
+        t_y[c] = t.y;
+        t_e[c] = t.empty ? 1u : 0u;
+        if constexpr (GUIDES) {
+          const GuideHalf* g = reinterpret_cast<const GuideHalf*>(A.guides + i);
+          t_g0[c] = g[0];
+          t_g1[c] = g[1];
+        }
+      } else {  // outside the image: empty (never read as a tap: the estimate checks the bounds first)
+        t_y[c] = 0.0;
+        t_e[c] = 1u;
+        if constexpr (GUIDES) t_g0[c] = GuideHalf{}, t_g1[c] = GuideHalf{};
+      }
+    }
+    __syncthreads();
+    if (x >= A.W || y >= A.H) return;
+    const size_t i = (size_t)y * A.W + x;
+    auto tap = [&](int qx, int qy) {
+      const int c = (qy - ty0) * TW + (qx - tx0);
+      return rtwd::SvTap{t_y[c], t_e[c] != 0u};
+    };
+    auto gd = [&](int qx, int qy) {
+      const int c = GUIDES ? (qy - ty0) * TW + (qx - tx0) : 0;
+      const GuideHalf h0 = t_g0[c], h1 = t_g1[c];
+      return Guide{{h0.a, h0.b, h0.c}, __uint_as_float(h0.d), {h1.a, h1.b, h1.c}, h1.d};
+    };
+    const float vp = A.var ? A.var[i] : rtwd::kVarUnknown;
+    A.out[i] = rtwd::spatial_variance_pixel<GUIDES>(x, y, A.W, A.H, A.P, vp, tap, gd);
+  }
+}
+
+hipError_t launch_spatial(const SpatialArgs& a, hipStream_t s) {
+  const dim3 grid((a.W + kDnTileW - 1) / kDnTileW, (a.H + kDnTileH - 1) / kDnTileH), block(kDnBlock);
+  const bool tiled = !(a.P.flags & rtwd::kFlagDirect);
+  if (a.guides) {
+    if (tiled)
+      hipLaunchKernelGGL((spatial_variance_kernel<true, true>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((spatial_variance_kernel<true, false>), grid, block, 0, s, a);
+  } else {
+    if (tiled)
+      hipLaunchKernelGGL((spatial_variance_kernel<false, true>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((spatial_variance_kernel<false, false>), grid, block, 0, s, a);
+  }
+  return hipGetLastError();
+}
+
 // rtw_accum_variance_device: the squared standard error of the pixel's mean
 // luminance (rtw_adaptive.hpp pixel_se2) as an f32, with the pixel's own count
 // in the masked state (cnt), else `done`.
@@ -161,6 +260,13 @@ int run_levels(const float* d_mean, const float* d_var, const rtw_guide* d_guide
   Px* buf[2] = {static_cast<Px*>(workspace),
                 reinterpret_cast<Px*>(static_cast<unsigned char*>(workspace) + rtwd::image_bytes(W, H))};
   const bool force_direct = (P.flags & rtwd::kFlagDirect) != 0;
+  if (P.flags & rtwd::kFlagSpatialVar) {  // the estimated map lives in the second image: level 1 only reads it
+    float* est = reinterpret_cast<float*>(buf[1]);
+    const hipError_t e = launch_spatial(SpatialArgs{d_mean, d_var, reinterpret_cast<const Guide*>(d_guides), est,
+                                                    (int)W, (int)H, P}, s);
+    if (e != hipSuccess) return hip_fail("spatial variance kernel launch", e);
+    d_var = est;
+  }
   for (uint32_t l = 0; l < P.levels; ++l) {
     DenoiseArgs a;
     a.mean = d_mean;
@@ -208,6 +314,24 @@ int rtw_denoise_device(const float* d_mean, const float* d_var, const rtw_guide*
   if (st != RTW_OK) return st;
   if (((uintptr_t)d_guides & 15u) != 0) return rtw_fail(RTW_EINVAL, "rtw_denoise_device: d_guides is not 16-byte aligned");
   return run_levels(d_mean, d_var, d_guides, W, H, P, workspace, d_rgb_out, d_mean_out, static_cast<hipStream_t>(stream));
+}
+
+int rtw_denoise_spatial_variance_device(const float* d_mean, const float* d_var_in, const rtw_guide* d_guides, uint32_t W,
+                                        uint32_t H, const rtw_denoise_opts* o, float* d_var_out, void* stream) {
+  const rtw_denoise_opts dflt{};
+  if (!o) o = &dflt;
+  rtwd::Params P;
+  const int st = rtwd::check_spatial_call("rtw_denoise_spatial_variance_device", d_mean, d_var_in, d_guides, W, H,
+                                          o->levels, o->sigma_color, o->sigma_normal, o->sigma_depth, o->sigma_albedo,
+                                          o->flags, d_var_out, P);
+  if (st != RTW_OK) return st;
+  if (((uintptr_t)d_guides & 15u) != 0)
+    return rtw_fail(RTW_EINVAL, "rtw_denoise_spatial_variance_device: d_guides is not 16-byte aligned");
+  const hipError_t e = rtwk::launch_spatial(
+      rtwk::SpatialArgs{d_mean, d_var_in, reinterpret_cast<const rtwk::Guide*>(d_guides), d_var_out, (int)W, (int)H, P},
+      static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail("spatial variance kernel launch", e);
+  return RTW_OK;
 }
 
 int rtw_accum_variance_device(rtw_accum a, float* d_var, void* stream) {

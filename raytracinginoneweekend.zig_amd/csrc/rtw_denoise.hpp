@@ -67,7 +67,8 @@ constexpr double kDefSigmaColor = 2.0, kDefSigmaNormal = 0.1, kDefSigmaDepth = 0
 constexpr double kEpsColor = 1e-3;  // luminance units: the floor of the colour scale at var = 0
 constexpr uint32_t kFlagNoColor = 1u;  // rtw_denoise_opts.flags bit 0: drop the colour term everywhere
 constexpr uint32_t kFlagDirect = 2u;   // bit 1: the device runs every level in its direct form (same bytes; for A/B)
-constexpr uint32_t kFlagsKnown = 3u;
+constexpr uint32_t kFlagSpatialVar = 4u;  // bit 2: unknown variances are estimated from the image first (below)
+constexpr uint32_t kFlagsKnown = 7u;
 constexpr float kVarUnknown = -1.0f, kVarEmpty = -2.0f, kVarEmptyBelow = -1.5f;
 
 struct alignas(16) Px {  // an image pixel of the ping-pong buffers
@@ -206,6 +207,87 @@ RTW_DN_HD inline Px filter_pixel(int x, int y, int W, int H, int step, const Par
   return o;
 }
 
+// ---- the spatial variance estimate (kFlagSpatialVar) ----
+// A pixel whose variance is unknown — fewer than two chunks in the accumulator
+// — gets the guide-weighted variance of the luminance of the image itself over
+// its 7x7 window (SVGF's fallback for a pixel without history):
+//   var = fmax(0, s2 / sw - (s1 / sw)^2),  sw = sum w, s1 = sum w Y_q, s2 = sum w Y_q^2
+// over the 49 taps in row-major order (dy = -3..3 outer, dx inner), the centre
+// included.  w is filter_pixel's weight with the spline and colour terms left
+// out, the same expressions in the same order: w = wn * q^2, q = (z2 * a2) /
+// ((z2 + dz^2) * (a2 + da2)); two misses, or no guides: w = 1.  Dropped: a tap
+// outside the image, an empty tap, a tap across the hit / miss border, a tap
+// with !(w > 0).  Fewer than kSpatialMinTaps kept taps: the pixel stays
+// unknown.  A known or an empty centre keeps its value bit for bit.  The mean
+// image holds a pixel's mean already, so the window variance is in the units of
+// the accumulator's squared standard error and feeds c2 as it is.  No bias
+// correction (measured: never better).  Arithmetic as above: f64, one
+// operation per operator, rounded to f32 once.
+constexpr int kSpatialRadius = 3;
+constexpr int kSpatialMinTaps = 4;
+
+struct SvTap {  // what the estimate reads of a tap's pixel
+  double y;     // luminance of its mean
+  bool empty;
+};
+RTW_DN_HD inline SvTap sv_tap(const Px& p) {
+  return SvTap{luminance((double)p.r, (double)p.g, (double)p.b), p.var <= kVarEmptyBelow};
+}
+
+// The new variance of pixel (x, y), whose variance is var_p.  tap(x, y) ->
+// SvTap and gd(x, y) -> Guide read an in-image pixel (gd only when GUIDES).
+template <bool GUIDES, typename TapAt, typename GuideAt>
+RTW_DN_HD inline float spatial_variance_pixel(int x, int y, int W, int H, const Params& P, float var_p, TapAt tap,
+                                              GuideAt gd) {
+  if (var_p <= kVarEmptyBelow || var_p >= 0.0f) return var_p;
+  Guide g0{};
+  bool miss_p = false;
+  if (GUIDES) {
+    g0 = gd(x, y);
+    miss_p = g0.prim == 0u;
+  }
+  double sw = 0.0, s1 = 0.0, s2 = 0.0;
+  int kept = 0;
+  for (int dy = -kSpatialRadius; dy <= kSpatialRadius; ++dy) {
+    const int qy = y + dy;
+    for (int dx = -kSpatialRadius; dx <= kSpatialRadius; ++dx) {
+      const int qx = x + dx;
+      if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+      const SvTap t = tap(qx, qy);
+      if (t.empty) continue;
+      double w = 1.0;
+      if (GUIDES) {
+        const Guide g1 = gd(qx, qy);
+        if ((g1.prim == 0u) != miss_p) continue;
+        if (!miss_p) {
+          const double dn = ((double)g0.n[0] * (double)g1.n[0] + (double)g0.n[1] * (double)g1.n[1]) +
+                            (double)g0.n[2] * (double)g1.n[2];
+          const double tn = fmax(0.0, 1.0 - (1.0 - fmin(dn, 1.0)) * P.inv_sigma_normal);
+          const double wn = tn * tn;
+          const double zp = g0.depth, zq = g1.depth;
+          const double mz = P.sigma_depth * fmax(zp, zq);
+          const double z2 = mz * mz;
+          const double dz = zp - zq;
+          const double a0 = (double)g0.albedo[0] - (double)g1.albedo[0];
+          const double a1 = (double)g0.albedo[1] - (double)g1.albedo[1];
+          const double a2 = (double)g0.albedo[2] - (double)g1.albedo[2];
+          const double da2 = (a0 * a0 + a1 * a1) + a2 * a2;
+          const double q = (z2 * P.a2) / ((z2 + dz * dz) * (P.a2 + da2));
+          w = wn * (q * q);
+        }
+      }
+      if (!(w > 0.0)) continue;  // (also a NaN from a degenerate guide: 0 / 0)
+      sw += w;
+      s1 += w * t.y;
+      s2 += w * (t.y * t.y);
+      ++kept;
+    }
+  }
+  if (kept < kSpatialMinTaps) return kVarUnknown;
+  const double m1 = s1 / sw;
+  return (float)fmax(0.0, s2 / sw - m1 * m1);
+}
+
 // ---- library internals (rtw_denoise_host.cpp), shared by the host and device entries ----
 // Two ping-pong images of Px, each rounded up to 256 bytes.
 inline size_t image_bytes(uint32_t W, uint32_t H) { return (((size_t)W * H * sizeof(Px)) + 255) & ~(size_t)255; }
@@ -214,5 +296,12 @@ inline size_t image_bytes(uint32_t W, uint32_t H) { return (((size_t)W * H * siz
 int check_call(const char* who, const void* mean, uint32_t W, uint32_t H, uint32_t levels, double sc, double sn,
                double sd, double sa, uint32_t flags, const void* workspace, size_t workspace_bytes, const void* rgb_out,
                const void* mean_out, Params& P);
+// The same for rtw_denoise_spatial_variance_device / _host.
+int check_spatial_call(const char* who, const void* mean, const void* var_in, const void* guides, uint32_t W, uint32_t H,
+                       uint32_t levels, double sc, double sn, double sd, double sa, uint32_t flags, const void* var_out,
+                       Params& P);
+// The estimate over host buffers: var_out[i] for every pixel (var_in NULL: all unknown).
+void spatial_variance_image(const float* mean, const float* var_in, const Guide* guides, uint32_t W, uint32_t H,
+                            const Params& P, float* var_out);
 
 }  // namespace rtwd

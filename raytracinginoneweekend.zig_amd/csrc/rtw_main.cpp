@@ -7,7 +7,7 @@
 //              [--chunk C] [--image earth.png] [--out out.ppm]
 //              [--pass-spp N [--preview-dir DIR] [--max-noise X]
 //                            [--pixel-noise X [--min-spp N] [--spp-map FILE]]]
-//              [--denoise [--denoise-levels N]]
+//              [--denoise [--denoise-levels N] [--denoise-spatial]]
 // --pass-spp N renders the frame progressively, N samples per pass (a multiple
 // of the chunk): the same --out bytes as without it.  --preview-dir DIR writes
 // the image after every pass to DIR/pass_NNNN.ppm; --max-noise X stops once the
@@ -21,7 +21,10 @@
 // and to every preview of --preview-dir: the guides are computed once per run,
 // the frame goes through the accumulator (as one pass of --spp samples without
 // --pass-spp) and is filtered with --denoise-levels N iterations (1-6, default
-// 5).  Without --denoise the output bytes are unchanged.
+// 5).  --denoise-spatial (RTW_DENOISE_SPATIAL_VAR, §14.6) estimates the
+// variance of pixels that hold fewer than two chunks from the image itself: the
+// way to denoise a first preview of a single chunk.  Without --denoise the
+// output bytes are unchanged, and without --denoise-spatial --denoise's are.
 // Defaults are the reference's: scene 6 (main.zig:313) with that scene's own
 // size, spp, camera and background (main.zig:316-362); --width/--aspect/--spp
 // override them.  Scenes 4 and 7 need --image (assets/sekaichizu.png).
@@ -127,12 +130,12 @@ int main(int argc, char** argv) {
   double aspect = 0, max_noise = 0, pixel_noise = 0;
   uint64_t seed = 42;
   std::string out = "out.ppm", image_path, preview_dir, spp_map;
-  bool denoise = false;
+  bool denoise = false, denoise_spatial = false;
   uint32_t denoise_levels = 0;
   for (int i = 1; i < argc; i += 2) {
     const std::string k = argv[i];
-    if (k == "--denoise") {  // (the one option without a value)
-      denoise = true;
+    if (k == "--denoise" || k == "--denoise-spatial") {  // (the options without a value)
+      (k == "--denoise" ? denoise : denoise_spatial) = true;
       --i;
       continue;
     }
@@ -165,8 +168,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--preview-dir, --max-noise and --pixel-noise need --pass-spp\n");
     return 2;
   }
-  if (denoise_levels && !denoise) {
-    std::fprintf(stderr, "--denoise-levels needs --denoise\n");
+  if ((denoise_levels || denoise_spatial) && !denoise) {
+    std::fprintf(stderr, "--denoise-levels and --denoise-spatial need --denoise\n");
     return 2;
   }
   if (!(pixel_noise > 0) && (min_spp || !spp_map.empty())) {
@@ -191,15 +194,21 @@ int main(int argc, char** argv) {
     rtw_denoise_opts dn;
     std::memset(&dn, 0, sizeof(dn));
     dn.levels = denoise_levels;
+    if (denoise_spatial) dn.flags |= RTW_DENOISE_SPATIAL_VAR;
     if (denoise && pass_spp == 0) pass_spp = S;  // the whole frame as one pass of the accumulator
     if (denoise) {
       // The colour term needs a variance, and the variance two full chunks (without it the
       // filter blurs what no guide describes — reflections, shadows — and a 20-spp preview gets worse).
       const uint32_t c = std::min(chunk ? chunk : RTW_DEFAULT_CHUNK, S);
-      if (std::min(pass_spp, S) / c < 2)
+      if (std::min(pass_spp, S) / c < 2 && denoise_spatial)
+        std::fprintf(stderr,
+                     "note: the first image holds fewer than two chunks of %u samples; its variance is estimated from the "
+                     "image itself (--denoise-spatial)\n", c);
+      else if (std::min(pass_spp, S) / c < 2)
         std::fprintf(stderr,
                      "note: the first image holds fewer than two chunks of %u samples, so its variance is unknown and the "
-                     "denoiser's colour term is off for it; --chunk %u gives it one\n", c, std::max(1u, std::min(pass_spp, S) / 2));
+                     "denoiser's colour term is off for it; --chunk %u gives it one, or --denoise-spatial estimates it "
+                     "from the image\n", c, std::max(1u, std::min(pass_spp, S) / 2));
     }
     // --pass-spp: the frame through the accumulator, a preview per pass
     auto progressive = [&](const rtw_params& p, const rtw::FlatScene* fs, const rtw_world_desc* wd) {

@@ -84,7 +84,7 @@ class Guide(C.Structure):
 GUIDE_DTYPE = np.dtype([("normal", np.float32, 3), ("depth", np.float32), ("albedo", np.float32, 3),
                         ("prim", np.uint32)])
 VAR_UNKNOWN, VAR_EMPTY = -1.0, -2.0  # rtw_hip.h RTW_VAR_*
-DENOISE_NO_COLOR, DENOISE_DIRECT = 1, 2  # rtw_denoise_opts.flags
+DENOISE_NO_COLOR, DENOISE_DIRECT, DENOISE_SPATIAL_VAR = 1, 2, 4  # rtw_denoise_opts.flags
 
 
 class DenoiseOpts(C.Structure):
@@ -177,6 +177,10 @@ def lib() -> C.CDLL:
         for f in (L.rtw_denoise_device, L.rtw_denoise_host):
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(DenoiseOpts), C.c_void_p,
                           C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rtw_denoise_spatial_variance_device"):  # (an older A/B build has none)
+            for f in (L.rtw_denoise_spatial_variance_device, L.rtw_denoise_spatial_variance_host):
+                f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(DenoiseOpts), C.c_void_p,
+                              C.c_void_p]
         L.rtw_accum_variance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rtw_accum_denoise_workspace_bytes.restype = C.c_size_t
         L.rtw_accum_denoise_workspace_bytes.argtypes = [C.c_void_p, P(DenoiseOpts)]
@@ -408,6 +412,35 @@ def denoise_device(mean_ptr: int, var_ptr: int | None, guides_ptr: int | None, w
                                     vp(rgb_ptr), vp(mean_out_ptr), vp(stream)))
 
 
+def spatial_variance_host(mean, var=None, guides=None, opts: DenoiseOpts | None = None):
+    """The spatial variance estimate on the CPU (rtw_denoise_spatial_variance_host;
+    needs no GPU): mean (H, W, 3) f32, var (H, W) f32 or None (all unknown),
+    guides (H, W) GUIDE_DTYPE or None -> var (H, W) f32 with every VAR_UNKNOWN
+    pixel replaced by the guide-weighted variance of its 7x7 window's luminance.
+    denoise_host with DENOISE_SPATIAL_VAR is denoise_host on this map."""
+    m = np.ascontiguousarray(mean, np.float32)
+    h, w = m.shape[:2]
+    v = None if var is None else np.ascontiguousarray(var, np.float32)
+    g = None if guides is None else np.ascontiguousarray(guides, GUIDE_DTYPE)
+    if (v is not None and v.size != h * w) or (g is not None and g.size != h * w):
+        raise ValueError("var / guides do not have the image's size")
+    out = np.empty((h, w), np.float32)
+    _check(lib().rtw_denoise_spatial_variance_host(m.ctypes.data, v.ctypes.data if v is not None else None,
+                                                   g.ctypes.data if g is not None else None, w, h,
+                                                   C.byref(opts) if opts is not None else None, out.ctypes.data, None))
+    return out
+
+
+def spatial_variance_device(mean_ptr: int, var_ptr: int | None, guides_ptr: int | None, width: int, height: int,
+                            opts: DenoiseOpts | None, var_out_ptr: int, stream: int | None = None):
+    """rtw_denoise_spatial_variance_device on plain device buffers, asynchronous on `stream`."""
+    def vp(x):
+        return C.c_void_p(x) if x else None
+    _check(lib().rtw_denoise_spatial_variance_device(vp(mean_ptr), vp(var_ptr), vp(guides_ptr), width, height,
+                                                     C.byref(opts) if opts is not None else None, vp(var_out_ptr),
+                                                     vp(stream)))
+
+
 def effective_chunk(params: Params) -> int:
     """The accumulation chunk a render of `params` uses (rtw_hip.h)."""
     return min(params.chunk or DEFAULT_CHUNK, params.spp)
@@ -478,7 +511,9 @@ class Accumulator:
     def denoise(self, guides_ptr: int | None, workspace_ptr: int, workspace_bytes_: int, rgb_ptr: int | None,
                 mean_ptr: int | None = None, opts: DenoiseOpts | None = None, stream: int | None = None):
         """The denoised image of the samples so far (rtw_accum_denoise_device: resolve,
-        variance, filter) into device buffers.  The accumulator is not modified."""
+        variance, filter) into device buffers.  The accumulator is not modified.
+        opts.flags DENOISE_SPATIAL_VAR: pixels below two full chunks — every pixel of a
+        first single-chunk pass — get their variance estimated from the image."""
         def vp(x):
             return C.c_void_p(x) if x else None
         _check(lib().rtw_accum_denoise_device(self.h, vp(guides_ptr), C.byref(opts) if opts is not None else None,

@@ -132,7 +132,9 @@ class TorchAccumulator:
     def denoised(self, guides: torch.Tensor | None = None, opts=None):
         """(rgb uint8, mean f32) tensors of the denoised image of the samples so far
         (rtw_accum_denoise_device), on torch's current stream; `guides` from guides(), or
-        None for the variance-guided filter alone.  The accumulator is not modified."""
+        None for the variance-guided filter alone.  The accumulator is not modified.
+        With opts.flags DENOISE_SPATIAL_VAR a first pass of a single chunk, whose variance the
+        accumulator does not know yet, is filtered with a variance estimated from the image."""
         need = self.acc.denoise_workspace_bytes(opts)
         if getattr(self, "_dn_ws", None) is None or self._dn_ws.numel() < need + 256:
             self._dn_ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)

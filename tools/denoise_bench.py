@@ -5,11 +5,14 @@ pass accumulated.
 
   python tools/denoise_bench.py [--repeats 20] [--warmup 3] [--out FILE] [--no-quality]
   python tools/denoise_bench.py --quality-only --chunk 10   # the quality figures with two chunks in the pass
+  python tools/denoise_bench.py --quality-only --spatial    # ... of the single-chunk pass with RTW_DENOISE_SPATIAL_VAR
 
 Times are HIP events around the calls on one stream, alternating the variants
 in one process after a warm-up: the resolve alone, the variance alone, and the
 denoise entry with 1..5 levels in the product's forms and with every level in
-the direct form (RTW_DENOISE_DIRECT).  A level's time is the difference of
+the direct form (RTW_DENOISE_DIRECT), and the spatial variance estimate
+(rtw_denoise_spatial_variance_device, §14.6) over the all-unknown map in its
+tiled and direct forms, with and without guides.  A level's time is the difference of
 consecutive level counts; levels 1 and 2 (tap spacing 1 and 2) are the ones the
 product runs through LDS tiles, so their two columns are the A/B of the forms.
 Each level is compared with its traffic floor, 48 B read + 16 B written per
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=0,
                     help="params.chunk of the accumulated pass (0 = the default, 20: one chunk in the 20-sample pass, so "
                          "its variance is unknown and the colour term is dropped; 10 or 5 give 2 or 4 chunks)")
+    ap.add_argument("--spatial", action="store_true",
+                    help="quality: add the line of the denoise entry with RTW_DENOISE_SPATIAL_VAR (§14.6)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -97,6 +102,16 @@ def timings(args, R, Wd, torch, ta, rend, cam, p, guides, var, rgb, mean, stream
                 "variance": lambda: ta.acc.variance(var.data_ptr(), stream),
                 "guides cover scene": lambda: rend.scene.guides(cam, p, guides.data_ptr(), stream),
                 "guides globe (scene 7)": lambda: dw7.guides(cam7, p7, g7.data_ptr(), stream)}
+    ta.acc.resolve(rgb.data_ptr(), mean.data_ptr(), stream)  # (the estimate's input: the resolved mean, no variance)
+    est = torch.empty((H, W), dtype=torch.float32, device="cuda:0")
+
+    def spatial(g, flags):
+        R.spatial_variance_device(mean.data_ptr(), None, g, W, H, R.denoise_opts(flags=flags), est.data_ptr(), stream)
+    variants["spatial variance tiled"] = lambda: spatial(guides.data_ptr(), 0)
+    variants["spatial variance direct"] = lambda: spatial(guides.data_ptr(), R.DENOISE_DIRECT)
+    variants["spatial variance tiled, no guides"] = lambda: spatial(None, 0)
+    variants["spatial variance direct, no guides"] = lambda: spatial(None, R.DENOISE_DIRECT)
+    variants["denoise 5 levels spatial"] = lambda: denoise(5, R.DENOISE_SPATIAL_VAR)
     for k in range(1, 6):
         variants[f"denoise {k} levels"] = (lambda k=k: denoise(k))
         variants[f"denoise {k} levels direct"] = (lambda k=k: denoise(k, R.DENOISE_DIRECT))
@@ -128,7 +143,7 @@ def timings(args, R, Wd, torch, ta, rend, cam, p, guides, var, rgb, mean, stream
         f"{args.repeats} alternating repeats after {args.warmup} warm-ups, one process")
     say(f"shader clock over the timed loop: {mhz:.1f} MHz")
     for k in variants:
-        say(f"{k:28s}: median {med[k] * 1e3:9.1f} us  min {min(times[k]) * 1e3:9.1f}  max {max(times[k]) * 1e3:9.1f}")
+        say(f"{k:34s}: median {med[k] * 1e3:9.1f} us  min {min(times[k]) * 1e3:9.1f}  max {max(times[k]) * 1e3:9.1f}")
     floor_us = npix * 64 / (COPY_TBS * 1e12) * 1e6
     say(f"traffic floor of a level: {npix * 64 / 1e6:.1f} MB (48 B read + 16 B written per pixel) at {COPY_TBS} TB/s "
         f"= {floor_us:.1f} us")
@@ -146,6 +161,11 @@ def timings(args, R, Wd, torch, ta, rend, cam, p, guides, var, rgb, mean, stream
     total = med["denoise 5 levels"]
     say(f"total (resolve + variance + 5 levels): {total:.3f} ms = {total / PASS_TRACE_MS:.1%} of the {PASS_TRACE_MS} ms "
         f"trace time of a 20-sample pass; all-direct {med['denoise 5 levels direct']:.3f} ms")
+    level = (med["denoise 5 levels"] - base) / 5
+    ts, td = med["spatial variance tiled"], med["spatial variance direct"]
+    say(f"spatial variance estimate (7x7, every pixel unknown): tiled {ts * 1e3:.1f} us = {ts / level:.2f} mean levels, "
+        f"direct {td * 1e3:.1f} us = {td / level:.2f} mean levels (a mean level: {level * 1e3:.1f} us); the flagged "
+        f"5-level entry {med['denoise 5 levels spatial']:.3f} ms = unflagged + {(med['denoise 5 levels spatial'] - total) * 1e3:.1f} us")
 
 
 def quality(args, R, np, torch, ta, rend, cam, rgb, mean, stream, denoise, say, W, H):
@@ -166,6 +186,12 @@ def quality(args, R, np, torch, ta, rend, cam, rgb, mean, stream, denoise, say, 
     say(f"quality, chunk {args.chunk or R.DEFAULT_CHUNK} ({m} full chunk(s): variance {'known' if m >= 2 else 'unknown, no colour term'}), "
         f"against the {args.ref_spp}-spp frame (RMSE of the linear mean): input 20 spp {e_in:.5f}, unguided "
         f"5-level B3 blur {e_blur:.5f}, denoised {e_den:.5f} = {e_den / e_in:.3f} x input, {e_den / e_blur:.3f} x blur")
+    if args.spatial:
+        denoise(5, R.DENOISE_SPATIAL_VAR)
+        torch.cuda.synchronize()
+        e_sp = rmse(mean.cpu().numpy().astype(np.float64))
+        say(f"quality with RTW_DENOISE_SPATIAL_VAR (variances below two chunks estimated from the image): denoised "
+            f"{e_sp:.5f} = {e_sp / e_in:.3f} x input, {e_sp / e_den:.3f} x the unflagged call")
 
 
 if __name__ == "__main__":
