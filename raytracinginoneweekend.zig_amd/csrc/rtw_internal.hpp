@@ -22,11 +22,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rtw_layout.hpp"  // kMoving, kClusterSlots, kNodeWords, kLeafBit, ...: the layout's constants (no HIP)
+#include "rtw_layout.hpp"  // kMoving, kTileW, kSegCap, HomeRec, PathBuf, kNodeWords, ...: the layout's constants (no HIP)
 
 namespace rtwk {
 
-constexpr uint32_t kTileW = 8, kTileH = 8;  // 64 pixels = one wave's batch
 constexpr uint32_t kBatch = 64;             // work units fetched per atomic
 
 template <typename R>
@@ -175,7 +174,6 @@ struct ResolveArgs {
   uint32_t npix;
   double scale;       // 1.0 / samples folded
 };
-constexpr uint32_t kNoiseGrid = 256;  // workgroups of accum_noise_kernel: fixed, so the sum's order never changes
 struct NoiseArgs {
   const double* stat;  // [npix][2]
   double* part;        // [kNoiseGrid] per-workgroup sums, then [kNoiseGrid] = the frame's noise
@@ -243,31 +241,7 @@ constexpr size_t kCoopLdsBytes = (kTraceBlock / 64) * 768;
 // survivors within a segment (no global atomics), deals units from the
 // segment's reservoir (one global atomic per kWfBatch units), and a segment
 // runs on the same XCD every launch (fixed grid, round-robin dispatch).
-constexpr uint32_t kSegCap = 64;  // paths per segment (one 64-lane wave round)
-constexpr uint32_t kDrainWin = 32;  // wf_drain: samples of a unit dealt ahead of its fold (ring entries per slot)
-// A home slot of the wavefront engine, one 32-B record (one memory sector):
-// a sample end reads and updates the three fields together (separate arrays
-// touched three sectors per access, partially).
-struct alignas(32) HomeRec {
-  double sum[3];      // f64 chunk sum of the unit's finished samples
-  uint32_t unit, s;   // the unit, the sample in flight
-};
-static_assert(sizeof(HomeRec) == 32, "HomeRec is one 32-B sector");
-template <typename R>
-struct PathBuf {
-  R *ox, *oy, *oz, *dx, *dy, *dz, *tx, *ty, *tz, *tm;
-  uint64_t* rs;
-  uint32_t* slot;  // home slot
-  uint32_t* dsk;   // depth | (skip + 1) << 16
-  int32_t* hk;     // fused engine: the table position of the path's closest hit, -1 = miss; with hk >= 0 the path's
-                   // o holds the hit point o + t * d (made where the hit was found: wavefront.hip to_hit_point)
-};
-// Moving bytes per path (one PathBuf entry).
-template <typename R>
-constexpr size_t kPathBytes = 10 * sizeof(R) + 8 + 4 + 4;
-// Home bytes per slot: f64x3 chunk sum, unit id, sample index.
-constexpr size_t kHomeBytes = 24 + 4 + 4;
-
+// (kSegCap, kDrainWin, HomeRec, PathBuf: rtw_layout.hpp)
 template <typename R>
 struct WfArgs {
   TraceArgs<R> t;  // MUST stay at offset 0: kargs<R>() reads it
@@ -378,7 +352,6 @@ struct WorldArgs {
   uint32_t tail_deal;   // 1: lanes the queue left without a unit trace samples of the wave's other units
   uint32_t lane_yield;  // per-lane traversal: a phase pauses once fewer lanes than this still walk (0: never)
 };
-constexpr uint32_t kTailWin = 32;  // world kernel: the last samples of a unit other lanes may trace (ring entries)
 
 // occ: register-allocation target (workgroups per CU): 1 (none), 3 or 4.
 // fs: the kernel's feature set, world_feature_set(features of the world, per-lane

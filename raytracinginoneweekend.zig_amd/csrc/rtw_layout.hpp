@@ -51,5 +51,32 @@ constexpr uint32_t kMaxLeafPrims = RTW_MAX_LEAF_PRIMS;
 #define RTW_SAH_BINS 256  // bins of the builder's SAH sweep (profiles/r01/world_sah_bins_ab.txt)
 #endif
 constexpr uint32_t kWorldHasSpheres = 1;  // WorldView.flags
+constexpr uint32_t kTailWin = 32;  // world kernel: the last samples of a unit other lanes may trace (ring entries)
+
+// ------------------------------------------- work units and the workspace --
+// (what the render plan, rtw_plan.hpp, sizes: the kernels' side is rtw_internal.hpp)
+constexpr uint32_t kTileW = 8, kTileH = 8;  // 64 pixels = one wave's batch
+constexpr uint32_t kNoiseGrid = 256;  // workgroups of accum_noise_kernel: fixed, so the sum's order never changes
+constexpr uint32_t kSegCap = 64;    // wavefront engine: paths per segment (one 64-lane wave round)
+constexpr uint32_t kDrainWin = 32;  // wf_drain: samples of a unit dealt ahead of its fold (ring entries per slot)
+// A home slot of the wavefront engine, one 32-B record (one memory sector):
+// a sample end reads and updates the three fields together (separate arrays
+// touched three sectors per access, partially).
+struct alignas(32) HomeRec {
+  double sum[3];      // f64 chunk sum of the unit's finished samples
+  uint32_t unit, s;   // the unit, the sample in flight
+};
+static_assert(sizeof(HomeRec) == 32, "HomeRec is one 32-B sector");
+// One SoA path queue of the wavefront engine: an array per member, in this
+// order in the workspace (rtw_plan.cpp wf_set_layout).
+template <typename R>
+struct PathBuf {
+  R *ox, *oy, *oz, *dx, *dy, *dz, *tx, *ty, *tz, *tm;
+  uint64_t* rs;
+  uint32_t* slot;  // home slot
+  uint32_t* dsk;   // depth | (skip + 1) << 16
+  int32_t* hk;     // fused engine: the table position of the path's closest hit, -1 = miss; with hk >= 0 the path's
+                   // o holds the hit point o + t * d (made where the hit was found: wavefront.hip to_hit_point)
+};
 
 }  // namespace rtwk

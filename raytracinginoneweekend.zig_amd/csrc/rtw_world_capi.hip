@@ -133,7 +133,7 @@ double bvh_margin(const rtw_world_s* w, const rtw_camera* cam) {
 // instantiation (feature set), register budget, LDS, persistent grid, and the
 // tail dealing's ring bytes (one kTailWin-entry f64x3 ring per lane of the
 // grid, WorldArgs::ring), which live in the caller's workspace after the
-// common region (rtw_ws_total), so renders on different streams with their
+// common region (rtwp::world_ring_off), so renders on different streams with their
 // own workspaces never share one.
 struct WorldLaunchCfg {
   int fs, oi, bpc;
@@ -176,10 +176,9 @@ WorldLaunchCfg world_cfg(const rtw_world_s* w, const rtw_params* p, int dev) {
     bpc = bpc_cache[c.fs][c.oi];
   }
   c.bpc = bpc;
-  const uint32_t units = rtw_total_units(p);
-  const uint32_t want = (units + 255) / 256;
+  const uint32_t want = ((uint32_t)rtwp::total_units(p) + 255) / 256;
   c.grid = std::max(1u, std::min((uint32_t)(rtw_device_cus(dev) * bpc), want));
-  c.ring_off = (rtw_ws_total(p) + 255) & ~(size_t)255;
+  c.ring_off = rtwp::world_ring_off(p);
   c.ring_bytes = (size_t)c.grid * rtwk::kWorldBlock * rtwk::kTailWin * 3 * sizeof(double);
   return c;
 }
@@ -194,34 +193,23 @@ int world_launch(rtw_world w, const rtw_camera* cam, const rtw_params* p, void* 
     return rtw_fail(RTW_UNSUPPORTED, "world renders run in f64 on the megakernel engine");
   if (w->has_moving && w->view.n_nodes && (cam->time0 < 0.0 || cam->time1 > 1.0))
     return rtw_fail(RTW_UNSUPPORTED, "BVH boxes of moving spheres cover shutter times [0, 1] only");
-  const size_t need = rtw_ws_total(p);
-  if (!ws || ws_bytes < need) return rtw_fail(RTW_EINVAL, "workspace %zu bytes < required %zu", ws_bytes, need);
-  if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return rtw_fail(RTW_EINVAL, "workspace not 256-B aligned");
+  const rtwp::WsLayout L = rtwp::ws_layout(p);
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
-  if (dev != w->device) return rtw_fail(RTW_EINVAL, "world lives on device %d, current is %d", w->device, dev);
-  auto* wsb = static_cast<unsigned char*>(ws);
-  // A pass of a masked accumulator deals its active tiles only; with none it launches nothing.
-  const uint32_t* m_list = nullptr;
-  const uint64_t* m_mask = nullptr;
-  uint32_t m_tiles = 0;
-  if (acc) {
-    const int st = rtw_accum_pass_map(acc, &m_list, &m_mask, &m_tiles);
-    if (st != RTW_OK) return st;
-    if (m_list && m_tiles == 0) {  // nothing launched: the timer holds no interval (not the previous pass's)
-      if (timer) timer->recorded = false;
-      if (tail_ran) *tail_ran = 0u;
-      return RTW_OK;
-    }
+  RtwPassMap map;  // a pass of a masked accumulator deals its active tiles only; with none it launches nothing
+  bool launch = true;
+  const int st0 = rtw_launch_begin(L, ws, ws_bytes, w->device, "world lives on device %d, current is %d", acc, timer,
+                                   stream, &dev, &map, &launch);
+  if (st0 != RTW_OK || !launch) {
+    if (st0 == RTW_OK && tail_ran) *tail_ran = 0u;
+    return st0;
   }
-  if (hipMemsetAsync(wsb + rtw_ws_counter_off(p), 0, 512, stream) != hipSuccess)
-    return rtw_fail(RTW_EHIP, "workspace reset failed");
+  auto* wsb = static_cast<unsigned char*>(ws);
   rtwk::WorldArgs a;
   std::memset(&a, 0, sizeof(a));
   rtw_fill_trace_args(a.t, cam, p, wsb, seed_adv);
   a.w = w->view;
   a.margin = bvh_margin(w, cam);
-  a.counts = reinterpret_cast<unsigned long long*>(wsb + rtw_ws_stats_off(p));
+  a.counts = reinterpret_cast<unsigned long long*>(wsb + L.stats_off);
   const WorldLaunchCfg c = world_cfg(w, p, dev);
   // Tail dealing (default; development knob RTW_WORLD_TAIL=0: off) needs the
   // rings in the workspace (rtw_world_workspace_bytes); a workspace of only
@@ -237,12 +225,9 @@ int world_launch(rtw_world w, const rtw_camera* cam, const rtw_params* p, void* 
   if (tail_ran) *tail_ran = a.tail_deal;
   const size_t lds = c.lds;
   uint32_t grid = c.grid;
-  if (m_list) {  // (the rings are sized for c.grid: a smaller grid uses their head)
-    a.t.tile_list = m_list;
-    a.t.tile_mask = m_mask;
-    a.t.total_units = m_tiles * 64u * a.t.n_chunks;
+  map.apply(a.t);
+  if (map.list)  // (the rings are sized for c.grid: a smaller grid uses their head)
     grid = std::max(1u, std::min(grid, (a.t.total_units + 255u) / 256u));
-  }
   const int oi = c.oi, fs = c.fs;
   if (timer && rtw_timer_mark(timer, stream, true) != RTW_OK) return RTW_EHIP;
   hipError_t e = rtwk::launch_world(a, grid, lds, stream, mode, oi, fs);
@@ -338,7 +323,7 @@ int rtw_world_render_counts_ex(rtw_world w, const rtw_camera* cam, const rtw_par
     if (st2 != RTW_OK) return st2;
     unsigned long long q[5];
     if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(q, static_cast<unsigned char*>(ws) + rtw_ws_stats_off(p) + 8 * 8, sizeof(q), hipMemcpyDeviceToHost) !=
+        hipMemcpy(q, static_cast<unsigned char*>(ws) + rtwp::ws_layout(p).stats_off + 8 * 8, sizeof(q), hipMemcpyDeviceToHost) !=
             hipSuccess)
       return rtw_fail(RTW_EHIP, "world phase pass failed");
     double tot = 0;
@@ -352,7 +337,7 @@ int rtw_world_render_counts_ex(rtw_world w, const rtw_camera* cam, const rtw_par
   if (st != RTW_OK) return st;
   if (hipDeviceSynchronize() != hipSuccess) return rtw_fail(RTW_EHIP, "world counts pass failed");
   unsigned long long c[7];
-  if (hipMemcpy(c, static_cast<unsigned char*>(ws) + rtw_ws_stats_off(p), sizeof(c), hipMemcpyDeviceToHost) !=
+  if (hipMemcpy(c, static_cast<unsigned char*>(ws) + rtwp::ws_layout(p).stats_off, sizeof(c), hipMemcpyDeviceToHost) !=
       hipSuccess)
     return rtw_fail(RTW_EHIP, "counts copy failed");
   for (int i = 0; i < 5; ++i) counts_out[i] = c[i];  // samples, segments, node visits, primitive tests, wave iterations
@@ -377,33 +362,16 @@ int rtw_world_render(const rtw_camera* cam, const rtw_world_desc* desc, const rt
   if (!cam || !desc || !rgb_out) return rtw_fail(RTW_EINVAL, "camera/desc/rgb_out is NULL");
   const int v = rtw_validate_params(p);
   if (v != RTW_OK) return v;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rtw_fail(RTW_ENODEV, "no HIP device visible");
-  int prev = 0;
-  if (hipGetDevice(&prev) != hipSuccess) return rtw_fail(RTW_EHIP, "hipGetDevice failed");
-  const int dev = p->device < 0 ? prev : p->device;
-  if (dev >= ndev) return rtw_fail(RTW_EINVAL, "device %d >= device count %d", dev, ndev);
-  if (hipSetDevice(dev) != hipSuccess) return rtw_fail(RTW_EHIP, "hipSetDevice failed");
+  RtwOneShot o;
+  int st = o.enter(p);
+  if (st != RTW_OK) return st;
   rtw_world w = nullptr;
-  int st = rtw_world_create(desc, 0, &w);
-  const size_t wsb = st == RTW_OK ? rtw_world_workspace_bytes(w, p) : 0, pix = (size_t)p->row_count * p->width * 3;
-  void *ws = nullptr, *d_rgb = nullptr, *d_mean = nullptr;
-  if (st == RTW_OK && (hipMalloc(&ws, wsb) != hipSuccess || hipMalloc(&d_rgb, pix) != hipSuccess ||
-                       (mean_out && hipMalloc(&d_mean, pix * sizeof(float)) != hipSuccess)))
-    st = rtw_fail(RTW_ENOMEM, "rtw_world_render: device allocation failed");
-  if (st == RTW_OK)
-    st = world_launch(w, cam, p, ws, wsb, static_cast<uint8_t*>(d_rgb), static_cast<float*>(d_mean), nullptr,
-                      nullptr, 0);
+  st = rtw_world_create(desc, 0, &w);
+  if (st == RTW_OK) st = o.alloc("rtw_world_render", rtw_world_workspace_bytes(w, p), p, mean_out != nullptr);
+  if (st == RTW_OK) st = world_launch(w, cam, p, o.ws, o.ws_bytes, o.d_rgb, o.d_mean, nullptr, nullptr, 0);
   if (st == RTW_OK && hipDeviceSynchronize() != hipSuccess) st = rtw_fail(RTW_EHIP, "world render failed on the device");
-  if (st == RTW_OK && hipMemcpy(rgb_out, d_rgb, pix, hipMemcpyDeviceToHost) != hipSuccess)
-    st = rtw_fail(RTW_EHIP, "copy of rgb_out failed");
-  if (st == RTW_OK && mean_out && hipMemcpy(mean_out, d_mean, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-    st = rtw_fail(RTW_EHIP, "copy of mean_out failed");
-  if (ws) (void)hipFree(ws);
-  if (d_rgb) (void)hipFree(d_rgb);
-  if (d_mean) (void)hipFree(d_mean);
+  if (st == RTW_OK) st = o.copy_back(rgb_out, mean_out);
   rtw_world_destroy(w);
-  (void)hipSetDevice(prev);
   return st;
 }
 

@@ -116,7 +116,7 @@ def test_workspace_bytes_wavefront(rtw, monkeypatch, sets, ring):
     hit winner per path; its hit point rides in the path's origin since round 6),
     the split engine's hit arrays, the home
     slots and (wf_drain only: params.wf_drain RTW_WF_DRAIN_SAMPLES) its ring of 32 R x3 sample
-    radiances (rtw_capi.hip ws_layout) per in-flight path, + per-segment
+    radiances (rtw_plan.cpp wf_set_layout) per in-flight path, + per-segment
     words; wf_paths is split over params.wf_sets queue sets, so the bytes per
     path do not grow with the sets (exact bounds: an upper bound per path,
     ADVICE r3)."""
@@ -134,6 +134,24 @@ def test_workspace_bytes_wavefront(rtw, monkeypatch, sets, ring):
             assert extra <= n * (per_path + 1) + sets * (64 * per_path + 64 * 256)  # per-path upper bound
     d = rtw.make_params(64, 36, 1, engine="wavefront")
     assert rtw.workspace_bytes(d) > rtw.DEFAULT_WF_PATHS * 100
+
+
+def test_workspace_bytes_are_the_recorded_ones(rtw):
+    """rtw_workspace_bytes, and rtw_accum_workspace_bytes for passes of one chunk, two chunks and the whole
+    frame, return what the library returned before its sizes moved into the render plan (csrc/rtw_plan.cpp):
+    tests/golden/workspace_bytes.json, recorded over both engines and precisions, every wf_sets, wf_drain and
+    a list of wf_paths, images (one a row shard) and (spp, chunk) pairs.  0 = the call refuses the pass size."""
+    with open(os.path.join(GOLDEN, "workspace_bytes.json")) as f:
+        g = json.load(f)
+    names = g["fields"][:-4]
+    assert len(g["rows"]) >= 200
+    for row in g["rows"]:
+        kw = dict(zip(names, row))
+        p = rtw.make_params(**kw)
+        chunk = min(kw["chunk"] or rtw.DEFAULT_CHUNK, kw["spp"])
+        got = [rtw.lib().rtw_workspace_bytes(C.byref(p))] + [
+            rtw.lib().rtw_accum_workspace_bytes(C.byref(p), n) for n in (chunk, 2 * chunk, kw["spp"])]
+        assert got == row[-4:], kw
 
 
 ENV_KNOBS = {  # every environment variable a development (-DRTW_MEASURE) build reads
