@@ -243,10 +243,23 @@ enum {
   RTW_STAT_CAND_WAVE_ITERS = 3, RTW_STAT_CAND_LANES = 4, RTW_STAT_DISC_GE0_LANES = 5,
   RTW_STAT_SPHERE_LOOP_WAVE_ITERS = 6, RTW_STAT_CULL_SURVIVOR_LANES = 7, RTW_STAT_CULL_EXACT_WAVE_ITERS = 8,
   RTW_STAT_DRAIN_SEGMENTS = 9, RTW_STAT_DRAIN_SAMPLES = 10, RTW_STAT_CLUSTER_WAVE_TESTS = 11,
-  RTW_STAT_CLUSTER_WAVE_SKIPS = 12, RTW_STAT_DRAIN_WAVE_ITERS = 13
+  RTW_STAT_CLUSTER_WAVE_SKIPS = 12, RTW_STAT_DRAIN_WAVE_ITERS = 13,
+  /* megakernel, primary-first loop: wave-iterations with a primary phase; lanes whose sample ended in
+   * it (a camera ray that missed, or max_depth 0) and sat out the rest of that iteration */
+  RTW_STAT_PRIMARY_ROUNDS = 14, RTW_STAT_PRIMARY_IDLE_LANES = 15
 };
 int rtw_render_stats(rtw_scene scene, const rtw_camera *cam, const rtw_params *params,
                      void *workspace, size_t workspace_bytes, uint64_t stats_out[RTW_STATS_WORDS]);
+/* The same pass with the first n_words <= RTW_STATS_WORDS_EX words: the RTW_STAT_* ones, then the
+ * words added since (additive: rtw_render_stats keeps its 16). */
+#define RTW_STATS_WORDS_EX 24
+enum {
+  /* megakernel, primary-first loop: the fetched unit batches' tile masks, their popcounts summed
+   * (spheres the batch's camera rays are tested against per lane) */
+  RTW_STAT_PRIMARY_MASK_POPCOUNT = 16
+};
+int rtw_render_stats_ex(rtw_scene scene, const rtw_camera *cam, const rtw_params *params,
+                        void *workspace, size_t workspace_bytes, uint64_t *stats_out, uint32_t n_words);
 
 /* =================================================== general worlds ===
  * Every other scene of the reference (main.zig:123-290) and BASELINE.json

@@ -306,6 +306,12 @@ int launch_engine(const rtwk::SceneView<R>& view, const rtw_camera* cam, const r
   map.apply(a);
   a.sc.cluster_on = cl_on;
   if (!cl_on) a.sc.n_clusters = 0u;  // nothing to stage (lds_bytes)
+  // The primary-first loop (kVarPrimaryFirst): the megakernel with the clusters on and every clustered slot in
+  // one 64-slot block (a lane's tile mask is two words); else the kernel runs the rotated loop.
+  a.primary_on = (p->engine == RTW_ENGINE_MEGAKERNEL && (var & rtwk::kVarPrimaryFirstBit) != 0 && cl_on &&
+                  a.sc.n_clusters * rtwk::kClusterSlots <= 64u)
+                     ? 1u
+                     : 0u;
   if (p->engine == RTW_ENGINE_WAVEFRONT) {
     if (mode == 2) return rtw_fail(RTW_UNSUPPORTED, "phase profile runs on the megakernel engine");
     return rtw_run_wavefront<R>(a, p, ws, L, dev, lds, stream, mode == 1);
@@ -351,7 +357,8 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
   size_t lds = lds_bytes(sc, (int)p->precision, cl_on ? sc->v64.n_clusters : 0u);
   if (p->engine == RTW_ENGINE_MEGAKERNEL && (var & rtwk::kVarHomeLdsBit) != 0)
     lds += 8 + (rtwk::kHomeLdsBytesPerWave + ((var & rtwk::kVarPathLdsBit) ? rtwk::kPathLdsBytesPerWave : 0) +
-                ((var & rtwk::kVarUnitBaseBit) ? rtwk::kUnitBaseLdsBytesPerWave : 0)) *
+                ((var & rtwk::kVarUnitBaseBit) ? rtwk::kUnitBaseLdsBytesPerWave : 0) +
+                ((var & rtwk::kVarPrimaryFirstBit) ? rtwk::kPrimaryLdsBytesPerWave : 0)) *
                    (rtwk::kTraceBlock / 64);  // (8: alignment of the home block)
   if (lds > 64 * 1024) return rtw_fail(RTW_UNSUPPORTED, "scene tables need %zu B of LDS", lds);
   const uint32_t grid_cap = (uint32_t)(device_cus(dev) * blocks_per_cu(dev, (int)p->precision, lds, var));
@@ -498,18 +505,19 @@ static int stats_pass(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, 
   if (mode == 1 && dev_knob("RTW_COUNTS_VERBOSE")) {
     fprintf(stderr, "[rtw counts] samples %llu segments %llu skipped %llu cand_wave_iters %llu cand_lanes %llu "
             "disc_ge0_lanes %llu sphere_loop_wave_iters %llu cull_survivor_lanes %llu cull_exact_wave_iters %llu "
-            "cluster_wave_tests %llu cluster_wave_skips %llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8],
-            st[11], st[12]);
+            "cluster_wave_tests %llu cluster_wave_skips %llu primary_rounds %llu primary_idle_lanes %llu "
+            "mask_popcount_sum %llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8],
+            st[11], st[12], st[14], st[15], st[16]);
     if (st[13])  // wavefront engine, wf_drain
       fprintf(stderr, "[rtw counts] drain wave iterations %llu, drained segments per wave iteration %.2f of 64\n",
               st[13], (double)st[9] / (double)st[13]);
   }
   if (mode == 2) {
     const char* names[10] = {"refill",  "start_sample", "wide+pretest", "hit+kind",    "tail",
-                             "loop_top", "exact_survivors", "coop_ball", "hitrec+scatter", "-"};
+                             "loop_top", "exact_survivors", "coop_ball", "hitrec+scatter", "primary"};
     unsigned long long tot = 0;
     for (int i = 0; i < 10; ++i) tot += st[16 + i];
-    for (int i = 0; i < 9; ++i)
+    for (int i = 0; i < 10; ++i)
       fprintf(stderr, "[rtw phase] %-15s %6.2f%%  (%llu wave-cycles)\n", names[i], tot ? 100.0 * st[16 + i] / tot : 0.0,
               st[16 + i]);
   }
@@ -523,6 +531,16 @@ int rtw_render_stats(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, v
   const int r = stats_pass(sc, cam, p, workspace, ws_bytes, st);
   if (r != RTW_OK) return r;
   for (int i = 0; i < RTW_STATS_WORDS; ++i) stats_out[i] = st[i];
+  return RTW_OK;
+}
+
+int rtw_render_stats_ex(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* workspace, size_t ws_bytes,
+                        uint64_t* stats_out, uint32_t n_words) {
+  if (!stats_out || n_words > RTW_STATS_WORDS_EX) return rtw_fail(RTW_EINVAL, "stats is NULL or n_words > %d", RTW_STATS_WORDS_EX);
+  unsigned long long st[32];
+  const int r = stats_pass(sc, cam, p, workspace, ws_bytes, st);
+  if (r != RTW_OK) return r;
+  for (uint32_t i = 0; i < n_words; ++i) stats_out[i] = st[i];
   return RTW_OK;
 }
 

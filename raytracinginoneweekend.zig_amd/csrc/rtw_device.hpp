@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "rtw_beam.hpp"
 #include "rtw_cull.hpp"
 #include "rtw_internal.hpp"
 #include "rtw_math.hpp"
@@ -98,7 +99,9 @@ constexpr int kVarPathLds = 33554432;
 constexpr int kVarUnitBase = 67108864;
 // kVarLaneDisk (with kVarMergedStart): new samples' lens-disk points from each
 // lane's own rejection loop after the cooperative pass, not inside it
-// (measurement: 4.8 % slower, profiles/r06/mk_var_ab.txt).
+// (measurement: 4.8 % slower in the rotated loop, profiles/r06/mk_var_ab.txt;
+// with kVarPrimaryFirst, where the disk point is needed before the pass, it
+// is 0.6 % faster than a disk-only pass and the default).
 constexpr int kVarLaneDisk = 134217728;
 // kVarMasked: a masked accumulator pass — the take maps the dealt tile through
 // TraceArgs::tile_list and skips the units of inactive pixels (tile_mask).
@@ -107,6 +110,12 @@ constexpr int kVarMasked = 268435456;
 // a wave skips a cluster's member pretests when every lane's line provably
 // misses the cluster's bounding sphere.
 constexpr int kVarCluster = 2097152;
+// kVarPrimaryFirst (with kVarMergedStart, kVarCluster, kVarHomeLds; f64): a lane
+// that starts a sample resolves its camera ray itself, before the cooperative
+// pass — wide spheres, then the exact per-lane survivor loop over the mask of
+// its unit batch's tile (rtw_beam.hpp) — and shades that hit in the same
+// iteration (rtw_trace.hip).  Runs when TraceArgs::primary_on is set.
+constexpr int kVarPrimaryFirst = kVarPrimaryFirstBit;
 // Measurement only (phase duplication): the clustered path's survivor
 // loop runs twice, the first pass's result discarded (same image).
 constexpr int kVarDupSurvivors = 8388608;
@@ -876,6 +885,9 @@ struct KStats {
   unsigned long long candwave = 0, candlane = 0, disc = 0, wave_iters = 0;
   unsigned long long cull_lanes = 0, cull_iters = 0;
   unsigned long long cl_tests = 0, cl_skips = 0;  // clustered pretest: (wave, cluster) pairs, skipped ones
+  // kVarPrimaryFirst: wave-iterations with a primary phase, lanes whose sample ended in it (idle for the rest
+  // of the iteration), the batches' mask popcounts summed
+  unsigned long long prim_rounds = 0, prim_idle = 0, mask_pop = 0;
   uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t t_last = 0;
 };
@@ -899,9 +911,14 @@ struct KStats {
 // SV: SceneView<R> (a copy in registers) or `const RTW_CONST SceneView<R>`
 // (the kernel argument itself, re-read with scalar loads where used: keeps
 // the scene fields out of the SGPR budget of the rest of the loop).
-template <typename R, bool F32, int MODE, int VAR, typename SV>
+// PRIMARY (kVarPrimaryFirst; f64, clusters on, one 64-slot block): a camera
+// ray — the wide spheres exactly, then the per-lane exact tests of the slots
+// in (pm0, pm1), the mask of the lane's tile, in place of the pretest.
+template <typename R, bool F32, int MODE, int VAR, bool PRIMARY = false, typename SV>
 __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, const Lane<R>& L, R tmin,
-                                            R pre_k, uint32_t lid, KStats& st, int& hit, R& tmax) {
+                                            R pre_k, uint32_t lid, KStats& st, int& hit, R& tmax, uint32_t pm0 = 0u,
+                                            uint32_t pm1 = 0u) {
+  static_assert(!PRIMARY || !F32, "the primary form is f64 only (clustered tables)");
   constexpr bool STATS = MODE == 1;
   constexpr bool CULL = !(VAR & 64);  // packed-f32 pretest for narrow spheres
   constexpr int kSphUnroll = (VAR & 2) ? 2 : 1;
@@ -1018,7 +1035,52 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
       }
     }
   };
-  if (!CULL || !S.cull_on) {
+  int fr_g = -1;  // phase B: time group of fr_v
+  R fr_v = (R)0;
+  // Per lane: the exact test on the survivors of a 64-slot block (bit 31-r
+  // of m0 / m1 = slot base+r / base+32+r); `clustered`: slots of the
+  // clustered tables (T.cpos), else the narrow order of the cull table.
+  // (Dealing the survivors across the wave instead — owners list their
+  // pairs in LDS, every lane tests one with its owner's ray via ds_bpermute
+  // — was 18 % slower: profiles/r03/survivor_compaction_ab.txt.)
+  auto run_survivors = [&](uint32_t m0, uint32_t m1, uint32_t base, bool clustered) {
+      while (m0 | m1) {  // per lane: the exact test on the survivors
+        if constexpr (STATS) {
+          if (lid == (uint32_t)__builtin_ctzll(__ballot(true))) st.cull_iters++;
+        }
+        uint32_t r;
+        if (m0) {
+          r = __clz(m0);
+          m0 &= ~(0x80000000u >> r);
+        } else {
+          r = __clz(m1);
+          m1 &= ~(0x80000000u >> r);
+          r += 32u;
+        }
+        const uint32_t j = base + r;
+        const uint32_t k = clustered ? T.cpos[j] : (j < S.n_sn ? S.g_static_wide + j : S.g_moving_wide + (j - S.n_sn));
+        const R* sp = T.sph + 8 * k;
+        const uint32_t meta = T.meta[k];
+        R cx = sp[0], cy = sp[1], cz = sp[2];
+        if (meta & kMoving) {
+          const int g = (int)((meta >> 2) & 63u);
+          if (g != fr_g) {  // per lane: usually once per segment
+            fr_g = g;
+            fr_v = rtwm::div_rn(L.time - T.tg[4 * g], T.tg[4 * g + 1] - T.tg[4 * g], T.tg[4 * g + 2]);
+          }
+          cx = cx + sp[3] * fr_v;
+          cy = cy + sp[4] * fr_v;
+          cz = cz + sp[5] * fr_v;
+        }
+        test(k, meta, cx, cy, cz, sp[6]);
+      }
+  };
+  if constexpr (PRIMARY) {
+    static_range(0u, S.g_static_wide);
+    moving_range(S.g_static, S.g_moving_wide);
+    const RTW_CONST uint32_t* cval = cptr(S.cvalid);
+    run_survivors(pm0 & cval[0], pm1 & cval[1], 0u, true);
+  } else if (!CULL || !S.cull_on) {
     static_range(F32 ? S.g_static_wide : 0u, S.g_static);
     moving_range(F32 ? S.g_moving_wide : S.g_static, S.n);
   } else {
@@ -1051,8 +1113,6 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
     const RTW_CONST float* ctf = cptr(S.tg_f);
     const float tf = (float)L.time;
     const uint32_t np_static = S.n_sn >> 1;  // pairs with two static spheres
-    int fr_g = -1;  // phase B: time group of fr_v
-    R fr_v = (R)0;
     // The pretest of one 64-sphere block: bit 31-r of sk[h] set = sphere
     // base+32h+r proven to miss.
     auto pretest_block = [&](uint32_t base, uint32_t (&sk)[2]) {
@@ -1094,44 +1154,6 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
         const uint32_t cnt = p1 > p0 ? 2u * (p1 - p0) : 0u;
         sk[h] = cnt == 0u ? 0u : (cnt == 32u ? sk[h] : sk[h] << (32u - cnt));
       }
-    };
-    // Per lane: the exact test on the survivors of a 64-slot block (bit 31-r
-    // of m0 / m1 = slot base+r / base+32+r); `clustered`: slots of the
-    // clustered tables (T.cpos), else the narrow order of the cull table.
-    // (Dealing the survivors across the wave instead — owners list their
-    // pairs in LDS, every lane tests one with its owner's ray via ds_bpermute
-    // — was 18 % slower: profiles/r03/survivor_compaction_ab.txt.)
-    auto run_survivors = [&](uint32_t m0, uint32_t m1, uint32_t base, bool clustered) {
-        while (m0 | m1) {  // per lane: the exact test on the survivors
-          if constexpr (STATS) {
-            if (lid == (uint32_t)__builtin_ctzll(__ballot(true))) st.cull_iters++;
-          }
-          uint32_t r;
-          if (m0) {
-            r = __clz(m0);
-            m0 &= ~(0x80000000u >> r);
-          } else {
-            r = __clz(m1);
-            m1 &= ~(0x80000000u >> r);
-            r += 32u;
-          }
-          const uint32_t j = base + r;
-          const uint32_t k = clustered ? T.cpos[j] : (j < S.n_sn ? S.g_static_wide + j : S.g_moving_wide + (j - S.n_sn));
-          const R* sp = T.sph + 8 * k;
-          const uint32_t meta = T.meta[k];
-          R cx = sp[0], cy = sp[1], cz = sp[2];
-          if (meta & kMoving) {
-            const int g = (int)((meta >> 2) & 63u);
-            if (g != fr_g) {  // per lane: usually once per segment
-              fr_g = g;
-              fr_v = rtwm::div_rn(L.time - T.tg[4 * g], T.tg[4 * g + 1] - T.tg[4 * g], T.tg[4 * g + 2]);
-            }
-            cx = cx + sp[3] * fr_v;
-            cy = cy + sp[4] * fr_v;
-            cz = cz + sp[5] * fr_v;
-          }
-          test(k, meta, cx, cy, cz, sp[6]);
-        }
     };
     bool clustered_done = false;
     if constexpr ((VAR & kVarCluster) != 0 && !F32) {

@@ -76,6 +76,7 @@ struct TraceArgs {
   uint32_t total_units;
   uint32_t upt_m, upt_sh, tx_m, tx_sh;  // rtwm::udiv magic of units per tile (64 * n_chunks) and tiles_x
   uint32_t unit_order;            // rtw_device.hpp dealt_unit: 0 image order, 1 last-first
+  uint32_t primary_on;            // kVarPrimaryFirst: the primary-first loop runs (clusters on, one 64-slot block)
   uint64_t seed_base;             // SplitMix64(seed).next()
   double* partial;                // [n_chunks][row_count*W][3] chunk sums
   uint32_t* counter;              // work-queue head (zeroed before launch)
@@ -114,9 +115,12 @@ int trace_blocks_per_cu(int precision, size_t lds, int var);
 // the kernel argument too: +0.6 %, profiles/r02/var1024_ab.txt) + kVarHomeLds
 // (round 3, +0.6 %, profiles/r03/home_lds_ab.txt), f32 5 waves/SIMD (8) +
 // kVarHomeLds (+1.3 %, profiles/r03/home_lds_f32_ab.txt).
+// f64 since round 11: kVarPrimaryFirst (camera rays per lane from a per-tile sphere mask, rtw_beam.hpp)
+// with kVarLaneDisk (the lens-disk point of a new sample from the lane's own loop, before its camera ray).
 // Every other variant exists only in the -DRTW_MEASURE build.
-#ifndef RTW_DEFAULT_VAR_F64  // (A/B builds override it)
-#define RTW_DEFAULT_VAR_F64 (4 + 512 + 1024 + 32768 + 131072 + 262144 + 524288 + 2097152 + 16777216)  // 19826180
+#ifndef RTW_DEFAULT_VAR_F64  // (A/B builds override it; 19826180: the round-6 default)
+#define RTW_DEFAULT_VAR_F64 \
+  (4 + 512 + 1024 + 32768 + 131072 + 262144 + 524288 + 2097152 + 16777216 + 4194304 + 134217728)  // 158238212
 #endif
 constexpr int kDefaultVarF64 = RTW_DEFAULT_VAR_F64;
 constexpr int kVarClusterBit = 2097152;  // rtw_device.hpp kVarCluster (clustered pretest, f64)
@@ -139,6 +143,11 @@ constexpr size_t kPathLdsBytesPerWave = 4 * 64 * 8;
 // + (kVarUnitBase) the unit's RNG base and f64 pixel column / reference row
 constexpr int kVarUnitBaseBit = 67108864;
 constexpr size_t kUnitBaseLdsBytesPerWave = 3 * 64 * 8;
+// + (kVarPrimaryFirst) the mask of the lane's unit batch: which clustered slots its tile's camera rays may
+// hit (two words per lane, bit order of SceneView::cvalid), then the wave's current batch's (a copy per lane);
+// right after the kHomeLdsBytesPerWave block
+constexpr int kVarPrimaryFirstBit = 4194304;
+constexpr size_t kPrimaryLdsBytesPerWave = 4 * 64 * 4;
 #ifndef RTW_DEFAULT_VAR_F32  // (A/B builds override it)
 #define RTW_DEFAULT_VAR_F32 (8 + 512 + 131072 + 262144 + 524288 + 16777216)  // 17695240
 #endif
@@ -149,7 +158,8 @@ constexpr int kVarMaskedBit = 268435456;
 // The masked instantiation of each precision.  f32 is built for 4 waves per SIMD (VAR bit 2, 128 VGPRs) where
 // the unmasked kernel has 5 (bit 3, 96): at 96 the map's two loads spilled (32 B of scratch against the unmasked
 // kernel's 16; decoding per batch, kVarBatchDecode, spilled 64).
-constexpr int kMaskedVarF64 = kDefaultVarF64 | kVarMaskedBit;
+// (f64: without kVarPrimaryFirst and its kVarLaneDisk, 134217728 — the masked pass keeps the round-6 loop)
+constexpr int kMaskedVarF64 = (kDefaultVarF64 & ~(kVarPrimaryFirstBit | 134217728)) | kVarMaskedBit;
 constexpr int kMaskedVarF32 = ((kDefaultVarF32 & ~8) | 4) | kVarMaskedBit;
 bool trace_variant_built(int precision, int var);
 constexpr int kTraceBlock = 256;

@@ -15,7 +15,14 @@
 //    of different length share the wave without padding to the longest.  The
 //    default variant rotates the iteration so that the lens-disk points of the
 //    new samples and the unit-ball points of the hits come from ONE
-//    cooperative rejection pass (kVarMergedStart, below).
+//    cooperative rejection pass (kVarMergedStart, below).  The f64 default
+//    goes one step further (kVarPrimaryFirst, the primary-first loop below):
+//    a lane that starts a sample resolves its camera ray itself — the wide
+//    spheres, then the exact tests of the few spheres in the mask of its
+//    tile (rtw_beam.hpp, made once per 64-unit batch in take_units) — and
+//    shades that hit in the same iteration, so a sample whose camera ray hits
+//    takes one wave-iteration less; only secondary rays go through the
+//    wave-uniform pretest.
 //  * The closest-hit loop over the sphere list is wave-UNIFORM: every lane
 //    tests sphere k at the same time, so sphere k's record is fetched with
 //    scalar loads (s_load, SGPR operands of the VALU ops): zero VGPRs and zero
@@ -29,6 +36,8 @@
 // The oracle's tierb_core.h is the written contract this file implements.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "rtw_device.hpp"
 
 // (Round 4) The lane's state flags (have_unit, have_ray, done, shading) as bits of one
@@ -38,8 +47,11 @@
 // lane ops, 2 -> 1 scratch pairs; -1.4 % per configs[1] frame
 // (profiles/r04/trace_lane_flags_ab.txt).
 
-namespace rtwk {
+#ifndef RTW_PRIMARY_ROUND2  // (the primary-first loop's second primary round: lane threshold, 0 = none)
+#define RTW_PRIMARY_ROUND2 0
+#endif
 
+namespace rtwk {
 
 // VAR (tuning variants, selected at launch): bit0 = sphere records from LDS
 // instead of scalar loads; bit1 = unroll the sphere loop by 2; bit2 = ask for
@@ -50,8 +62,9 @@ namespace rtwk {
 // argument; bit10 (1024) = the loop's other argument fields too; bits 11-14 =
 // phase-duplication measurement builds (RTW_MEASURE); rtw_device.hpp: 32768
 // kVarFastSqrt, 65536 kVarYOnly, 131072 kVarR0Table, 262144 kVarMergedStart,
-// 524288 kVarPreDraw, 1048576 kVarBatchDecode.  Defaults: rtw_capi.hip
-// kernel_variant; A/B tables: profiles/r01/ab_*.txt.
+// 524288 kVarPreDraw, 1048576 kVarBatchDecode, 4194304 kVarPrimaryFirst,
+// 134217728 kVarLaneDisk.  Defaults: rtw_capi.hip kernel_variant; A/B tables:
+// profiles/r01/ab_*.txt, profiles/r11/README.md.
 template <typename R, bool F32, int MODE, int VAR>
 __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 1)) trace_kernel(TraceArgs<R> A) {
   constexpr bool STATS = MODE == 1;
@@ -79,15 +92,18 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
   if constexpr (HOME) {
     const size_t off = (size_t)(reinterpret_cast<unsigned char*>(T.cpos + kClusterSlots * S.n_clusters) - lds_raw);
     constexpr size_t kPathB = (VAR & kVarPathLds) ? kPathLdsBytesPerWave : 0;
+    constexpr size_t kPrimB = (VAR & kVarPrimaryFirst) ? kPrimaryLdsBytesPerWave : 0;
     constexpr size_t kHomeStride =
-        kHomeLdsBytesPerWave + kPathB + ((VAR & kVarUnitBase) ? kUnitBaseLdsBytesPerWave : 0);
+        kHomeLdsBytesPerWave + kPathB + ((VAR & kVarUnitBase) ? kUnitBaseLdsBytesPerWave : 0) + kPrimB;
     unsigned char* hb = lds_raw + ((off + 7) & ~(size_t)7) + (threadIdx.x >> 6) * kHomeStride;
     h_sum = reinterpret_cast<double*>(hb);
     h_u32 = reinterpret_cast<uint32_t*>(hb + 3 * 64 * 8);
-    h_t = reinterpret_cast<R*>(hb + 2560);
-    h_rs = reinterpret_cast<uint64_t*>(hb + 2560 + 3 * 64 * 8);
-    h_base = reinterpret_cast<uint64_t*>(hb + 2560 + kPathB);
-    h_pxj = reinterpret_cast<R*>(hb + 2560 + kPathB + 64 * 8);
+    // (the masks are h_u32[256 ...]: right after it, the same address register with other offsets)
+    constexpr size_t kHome0 = kHomeLdsBytesPerWave + kPrimB;
+    h_t = reinterpret_cast<R*>(hb + kHome0);
+    h_rs = reinterpret_cast<uint64_t*>(hb + kHome0 + 3 * 64 * 8);
+    h_base = reinterpret_cast<uint64_t*>(hb + kHome0 + kPathB);
+    h_pxj = reinterpret_cast<R*>(hb + kHome0 + kPathB + 64 * 8);
   }
   constexpr bool UBASE = HOME && (VAR & kVarUnitBase) != 0;
   constexpr bool PLDS = HOME && (VAR & kVarPathLds) != 0 && (VAR & kVarMergedStart) != 0;
@@ -130,6 +146,16 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
   // build of it spilled 64 B of scratch: rtw_internal.hpp).
   constexpr bool MASKED = (VAR & kVarMasked) != 0;
   uint64_t cur_mask = 0, nb_mask = 0;  // (kVarBatchDecode: the batch's tile mask, wave-uniform)
+  // VAR kVarPrimaryFirst: the sphere mask of a unit batch's tile (wave-uniform; bit order of
+  // SceneView::cvalid), in LDS, not in registers held across the loop: h_u32[kPm + 64 h + lid] = word h
+  // of the mask of the lane's own batch, h_u32[kBm + 64 h + lid] = of the wave's current batch (a copy
+  // per lane: every LDS address of the take is the lane's h_u32 address plus a constant).
+  constexpr uint32_t kPm = 4 * 64, kBm = 6 * 64;
+  uint32_t* const h_me = h_u32 + lid;
+  constexpr bool PF = (VAR & kVarPrimaryFirst) != 0;
+  static_assert(!PF || (HOME && !F32 && (VAR & kVarMergedStart) && (VAR & kVarCluster) &&
+                        !(VAR & (kVarPathLds | kVarMasked))),
+                "kVarPrimaryFirst: the f64 rotated loop with clusters and the home block");
   auto decode_batch = [&](uint32_t base, uint32_t& tx, uint32_t& ty, uint32_t& c, uint64_t& tmask) {
     const uint32_t b64 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 6));
     const uint32_t nc = RTW_KA(n_chunks), txs = RTW_KA(tiles_x);
@@ -156,13 +182,56 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
       if (n > rem) {
         uint32_t b = 0;
         if (lid == 0) b = atomicAdd(RTW_KA(counter), kBatch);
-        base2 = __shfl(b, 0);
+        if constexpr (PF)  // (lane 0's value by a constant address: __shfl's lane arithmetic was held in a register)
+          base2 = (uint32_t)__builtin_amdgcn_ds_bpermute(0, (int)b);
+        else
+          base2 = __shfl(b, 0);
       }
-      if constexpr ((VAR & kVarBatchDecode) != 0) {
+      if constexpr ((VAR & kVarBatchDecode) != 0 || PF) {
         // A batch is 64 aligned units = one (tile, chunk): decoded once per
         // batch (wave-uniform) instead of two integer divisions per refill.
         if (n > rem)  // (a dealt batch is a 64-aligned batch in every order)
           decode_batch(dealt_unit(base2, *opaque(kargs<R>())) & ~63u, nb_tx, nb_ty, nb_c, nb_mask);
+      }
+      uint32_t nb_bm0 = 0u, nb_bm1 = 0u;
+      if constexpr (PF) {
+        // The new batch's mask: which clustered slots can a camera ray of its
+        // tile hit (rtw_beam.hpp)?  Lane j answers for slot j; every lane of
+        // the wave is here (wave-uniform branch at the loop's top).  A batch
+        // past the queue's end names no tile: its units are refused below.
+        if (n > rem && RTW_KA(primary_on)) {
+          const auto* ka = opaque(kargs<R>());
+          const double org[3] = {ka->origin[0], ka->origin[1], ka->origin[2]};
+          const double llc[3] = {ka->llc[0], ka->llc[1], ka->llc[2]};
+          const double hor[3] = {ka->horizontal[0], ka->horizontal[1], ka->horizontal[2]};
+          const double ver[3] = {ka->vertical[0], ka->vertical[1], ka->vertical[2]};
+          const double cu[3] = {ka->cu[0], ka->cu[1], ka->cu[2]}, cv[3] = {ka->cv[0], ka->cv[1], ka->cv[2]};
+          const uint32_t px0 = nb_tx * kTileW, ly0 = nb_ty * kTileH;
+          const uint32_t px1 = min(px0 + (kTileW - 1u), ka->W - 1u), ly1 = min(ly0 + (kTileH - 1u), ka->row_count - 1u);
+          const rtwb::Beam beam =
+              rtwb::tile_beam(org, llc, hor, ver, cu, cv, ka->lens_radius, ka->W, ka->H, px0, px1,
+                              ka->row_begin + ly0 * ka->row_stride, ka->row_begin + ly1 * ka->row_stride);
+          bool may = false;
+          if (lid < kClusterSlots * ka->sc.n_clusters) {  // (primary_on: one 64-slot block)
+            uint32_t slot = lid;  // (laundered: the table's address is made here, not held across the loop)
+            asm volatile("" : "+v"(slot));
+            const uint32_t k = T.cpos[slot];
+            const uint32_t meta = T.meta[k];
+            const bool mv = (meta & kMoving) != 0;
+            const uint32_t g = mv ? (meta >> 2) & 63u : 0u;
+            const double g0 = mv ? (double)T.tg[4 * g] : 0.0, g1 = mv ? (double)T.tg[4 * g + 1] : 1.0;
+            const double c0[3] = {(double)T.sph[8 * k], (double)T.sph[8 * k + 1], (double)T.sph[8 * k + 2]};
+            const double dc[3] = {(double)T.sph[8 * k + 3], (double)T.sph[8 * k + 4], (double)T.sph[8 * k + 5]};
+            may = rtwb::beam_may_hit(beam, c0, dc, (double)T.rad[k], mv, g0, g1, ka->time0, ka->time1);
+          }
+          const uint64_t bal = wballot(may);  // bit j = slot j; the survivor loop wants slot 32h + r at bit 31 - r of word h
+          nb_bm0 = __builtin_bitreverse32((uint32_t)bal);
+          nb_bm1 = __builtin_bitreverse32((uint32_t)(bal >> 32));
+          if constexpr (STATS) {
+            const RTW_CONST uint32_t* cval = cptr(ka->sc.cvalid);  // (dummy slots answer for table position 0)
+            if (lid == 0 && base2 < RTW_KA(total_units)) st.mask_pop += __popc(nb_bm0 & cval[0]) + __popc(nb_bm1 & cval[1]);
+          }
+        }
       }
       if (need) {
         const uint32_t unit = rank < rem ? qnext + rank : base2 + (rank - rem);
@@ -210,6 +279,10 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
               h_u32[128 + lid] = c;
               h_u32[192 + lid] = min(L.s + RTW_KA(chunk), RTW_KA(spp));
               h_sum[lid] = h_sum[64 + lid] = h_sum[128 + lid] = z;
+              if constexpr (PF) {  // the mask of the lane's own batch, current or new
+                h_me[kPm] = rank < rem ? h_me[kBm] : nb_bm0;
+                h_me[kPm + 64] = rank < rem ? h_me[kBm + 64] : nb_bm1;
+              }
               if constexpr (UBASE) {  // start_sample_uv's per-pixel part, once per unit
                 const uint32_t y = RTW_KA(row_begin) + ly * RTW_KA(row_stride);
                 const uint64_t pixel = (uint64_t)y * RTW_KA(W) + px;
@@ -232,6 +305,9 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
         qnext = base2 + (n - rem);
         qend = base2 + kBatch;
         if constexpr ((VAR & kVarBatchDecode) != 0) cur_tx = nb_tx, cur_ty = nb_ty, cur_c = nb_c, cur_mask = nb_mask;
+        if constexpr (PF) {  // after the takes above read the old one
+          h_me[kBm] = nb_bm0, h_me[kBm + 64] = nb_bm1;
+        }
       } else {
         qnext += n;
       }
@@ -268,19 +344,24 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
   // to be shaded.  (A result code, not two bool& outputs: the optimiser merged
   // their stores through a selected pointer, which put both flags in scratch
   // memory — a store + load per iteration on the critical path.)
-  auto bounce = [&](uint32_t& kind, int& hit, R& tmax) -> int {
+  // prim (kVarPrimaryFirst): the lane's camera ray, from the mask of its tile
+  // (closest_hit's PRIMARY form) instead of the wave's pretest.
+  auto bounce = [&](uint32_t& kind, int& hit, R& tmax, auto prim) -> int {
+    constexpr bool PRIM = decltype(prim)::value;
     if (L.depth == RTW_KA(max_depth)) {  // rayColor depth == 0 (main.zig:105-108)
       return 1;
     }
     if (STATS) st.segments++;
     if constexpr (STATS) {
-      if (lid == (uint32_t)__builtin_ctzll(__ballot(true))) st.wave_iters++;
+      if (lid == (uint32_t)__builtin_ctzll(__ballot(true))) (PRIM ? st.prim_rounds : st.wave_iters)++;
     }
+    uint32_t pm0 = 0u, pm1 = 0u;
+    if constexpr (PRIM) pm0 = h_me[kPm], pm1 = h_me[kPm + 64];
     if constexpr (VAR & 512)  // scene fields re-read from the kernel argument (SGPR budget)
-      closest_hit<R, F32, MODE, VAR>(opaque(kargs<R>())->sc, T, L, RTW_KA(tmin), RTW_KA(pre_k), lid, st, hit,
-                                     tmax);
+      closest_hit<R, F32, MODE, VAR, PRIM>(opaque(kargs<R>())->sc, T, L, RTW_KA(tmin), RTW_KA(pre_k), lid, st, hit,
+                                           tmax, pm0, pm1);
     else
-      closest_hit<R, F32, MODE, VAR>(S, T, L, tmin, A.pre_k, lid, st, hit, tmax);
+      closest_hit<R, F32, MODE, VAR, PRIM>(S, T, L, tmin, A.pre_k, lid, st, hit, tmax, pm0, pm1);
     if (hit < 0) {  // miss: background (main.zig:109-112)
       V3<R> tt = L.T;
       if constexpr (PLDS) tt = t_load();
@@ -300,7 +381,105 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
     return 2;
   };
 
-  if constexpr ((VAR & kVarMergedStart) != 0) {
+  bool primary_ran = false;
+  if constexpr (PF) {
+    if (A.primary_on) {
+      // Primary-first loop (kVarPrimaryFirst; TraceArgs::primary_on): [take
+      // units] -> [new samples, per lane: u, v, the lens-disk point from the
+      // lane's own loop, the camera ray and ITS closest hit — the wide spheres,
+      // then the exact tests of the spheres in the mask of the lane's tile; a
+      // miss ends the sample here] -> ONE coop pass: unit-ball points and
+      // dielectric draws of the hits of this iteration's camera rays and of the
+      // previous step's secondary rays -> [scatter] -> [closest hit of the
+      // scattered rays through the wave's pretest].  A sample whose camera ray
+      // hits takes one wave-iteration less than in the rotated loop; each
+      // sample's draws are in the reference's order, and the exact tests, the
+      // tie rule and the NaN fallback are closest_hit's.
+      primary_ran = true;
+      LaneFlag<8u> shading{lane_flags};
+      uint32_t kind = 0;
+      int hit = -1;
+      R tmax = kInf;
+      for (;;) {
+        RTW_STAMP(5)
+        take_units();
+        if (!__any(have_unit)) {
+          if (__all(done)) break;
+          continue;
+        }
+        RTW_STAMP(0)
+        // (at the loop's top a lane has a ray exactly when it is shading)
+        // kVarLaneDisk (the default): the lens-disk point from the lane's own loop; without it, from a
+        // disk-only cooperative pass before the camera rays (0.6 % slower, profiles/r11/README.md).
+        constexpr bool LDISK = (VAR & kVarLaneDisk) != 0;
+        for (uint32_t round = 0;; ++round) {
+          const bool ns = have_unit && !have_ray;
+          R u = (R)0, v = (R)0, dk[2] = {(R)0, (R)0};
+          auto uv = [&]() {
+            if constexpr (UBASE) {
+              start_sample_uv_base<R>(kargs<R>(), L, h_base[lid], h_pxj[lid * TS], h_pxj[(64 + lid) * TS], u, v);
+            } else {
+              L.px = h_u32[lid];
+              L.ly = h_u32[64 + lid];
+              start_sample_uv<R>(kargs<R>(), L, u, v);
+            }
+          };
+          if constexpr (!LDISK) {
+            if (__any(ns)) {  // wave-uniform: coop_reject runs converged
+              if (ns) uv();
+              coop_reject<R, 2, true>(ns, L.rs, dk, slots, lid);
+            }
+          }
+          if (ns) {
+            if constexpr (LDISK) {
+              uv();
+              for (;;) {  // randomPointInUnitDisk (rand.zig:30-36)
+                dk[0] = rrange_m11<R>(L.rs);
+                dk[1] = rrange_m11<R>(L.rs);
+                if (in_unit_ball<R, 2>(dk)) break;
+              }
+            }
+            start_sample_ray<R>(kargs<R>(), L, u, v, dk[0], dk[1]);
+            have_ray = true;
+            if (bounce(kind, hit, tmax, std::true_type{}) == 1) {  // miss or depth limit
+              finish_sample();
+              if (STATS) st.prim_idle++;
+            } else {
+              shading = true;
+            }
+          }
+          // RTW_PRIMARY_ROUND2 = n > 0 (A/B builds): a second primary round when at least n lanes ended
+          // their sample above and still hold a unit (n = 8, 16: +0.2-0.3 %, within the run-to-run spread;
+          // profiles/r11/README.md).
+          if (RTW_PRIMARY_ROUND2 == 0 || round == 1u) break;
+          if (popc64(wballot(have_unit && !have_ray)) < (uint32_t)RTW_PRIMARY_ROUND2) break;
+        }
+        RTW_STAMP(9)
+        constexpr bool PRE = (VAR & kVarPreDraw) != 0;
+        const uint32_t dim = shading ? (kind <= 2u ? 3u : (PRE ? 1u : 0u)) : 0u;
+        R pt[3] = {(R)0, (R)0, (R)0}, raw = (R)0;
+        if (__any(dim != 0u)) coop_reject_mixed<R>(dim, L.rs, pt, raw, slots, lid);
+        RTW_STAMP(7)
+        if (shading) {
+          if (scatter_hit<R, F32, VAR, PRE>(T, L, hit, tmax, kind, pt, raw)) finish_sample();  // absorbed
+        }
+        RTW_STAMP(8)
+        shading = false;
+        hit = -1;
+        tmax = kInf;
+        bool ended = false;
+        if (have_ray) {
+          const int b = bounce(kind, hit, tmax, std::false_type{});
+          ended = b == 1;
+          shading = b == 2;
+        }
+        RTW_STAMP(3)
+        if (ended) finish_sample();
+      }
+    }
+  }
+  if (primary_ran) {
+  } else if constexpr ((VAR & kVarMergedStart) != 0) {
     // Rotated loop: [take units] -> [u, v of new samples] -> ONE coop pass:
     // lens-disk points (new samples) + unit-ball points (the Lambertian /
     // Metal hits of the previous step) -> [scatter; camera rays] -> [closest
@@ -369,7 +548,7 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
       tmax = kInf;
       bool ended = false;
       if (have_ray) {
-        const int b = bounce(kind, hit, tmax);
+        const int b = bounce(kind, hit, tmax, std::false_type{});
         ended = b == 1;
         shading = b == 2;
       }
@@ -428,7 +607,7 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
     int hit = -1;
     R tmax = kInf;
     if (have_ray) {
-      const int b = bounce(kind, hit, tmax);
+      const int b = bounce(kind, hit, tmax, std::false_type{});
       ended = b == 1;
       shading = b == 2;
     }
@@ -477,6 +656,11 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
     atomicAdd(A.stats + 8, st.cull_iters);
     atomicAdd(A.stats + 11, st.cl_tests);
     atomicAdd(A.stats + 12, st.cl_skips);
+    if constexpr (PF) {
+      atomicAdd(A.stats + 14, st.prim_rounds);
+      atomicAdd(A.stats + 15, st.prim_idle);
+      atomicAdd(A.stats + 16, st.mask_pop);
+    }
   }
   if constexpr (MODE == 2) {
     RTW_STAMP(4)

@@ -38,7 +38,9 @@ WORLD_TRAVERSAL = {"auto": 0, "union": 1, "lane": 2}  # rtw_world_traversal
 STATS_WORDS = 16  # rtw_hip.h RTW_STATS_WORDS
 STAT_NAMES = ["samples", "segments", "f32_skips", "cand_wave_iters", "cand_lanes", "disc_ge0_lanes",
               "sphere_loop_wave_iters", "cull_survivor_lanes", "cull_exact_wave_iters", "drain_segments",
-              "drain_samples", "cluster_wave_tests", "cluster_wave_skips", "drain_wave_iters"]  # RTW_STAT_*
+              "drain_samples", "cluster_wave_tests", "cluster_wave_skips", "drain_wave_iters", "primary_rounds",
+              "primary_idle_lanes"]  # RTW_STAT_*
+STAT_NAMES_EX = STAT_NAMES + ["primary_mask_popcount"]  # rtw_render_stats_ex: word 16 on
 DEFAULT_CHUNK = 20
 COVER_BACKGROUND = (0.70, 0.80, 1.00)
 
@@ -146,6 +148,9 @@ def lib() -> C.CDLL:
                                        C.c_uint64 * 6]
     L.rtw_render_stats.argtypes = [C.c_void_p, P(Camera), P(Params), C.c_void_p, C.c_size_t,
                                    C.c_uint64 * STATS_WORDS]
+    if hasattr(L, "rtw_render_stats_ex"):  # (an older A/B build has none)
+        L.rtw_render_stats_ex.argtypes = [C.c_void_p, P(Camera), P(Params), C.c_void_p, C.c_size_t,
+                                          P(C.c_uint64), C.c_uint32]
     if not hasattr(L, "rtw_accum_create"):  # (A/B timing may load an older build without the accumulator)
         _lib = L
         return L
@@ -356,6 +361,13 @@ class DeviceScene:
 
     def stats(self, cam: Camera, params: Params, workspace_ptr: int, workspace_bytes_: int) -> dict:
         """The counting pass's raw statistics words (rtw_render_stats, RTW_STAT_*)."""
+        if hasattr(lib(), "rtw_render_stats_ex"):
+            n = len(STAT_NAMES_EX) + STATS_WORDS - len(STAT_NAMES)  # (words 14-15 of the 16 are named since round 11)
+            out = (C.c_uint64 * n)()
+            _check(lib().rtw_render_stats_ex(self.h, C.byref(cam), C.byref(params), C.c_void_p(workspace_ptr),
+                                             workspace_bytes_, out, n))
+            names = STAT_NAMES + [None] * (STATS_WORDS - len(STAT_NAMES)) + STAT_NAMES_EX[len(STAT_NAMES):]
+            return {k: int(out[i]) for i, k in enumerate(names) if k}
         out = (C.c_uint64 * STATS_WORDS)()
         _check(lib().rtw_render_stats(self.h, C.byref(cam), C.byref(params), C.c_void_p(workspace_ptr),
                                       workspace_bytes_, out))
