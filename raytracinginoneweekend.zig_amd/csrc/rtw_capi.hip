@@ -62,7 +62,7 @@ uint64_t splitmix_first(uint64_t seed) {  // SplitMix64.init(seed).next()
 
 struct DevInfo {
   int cus = 0;
-  std::map<std::pair<int, int>, std::pair<size_t, int>> bpc;  // (precision, var) -> (lds, blocks per CU)
+  std::map<std::pair<int, bool>, std::pair<size_t, int>> bpc;  // (precision, masked) -> (lds, blocks per CU)
 };
 std::mutex g_dev_mu;
 std::map<int, DevInfo> g_dev;
@@ -77,21 +77,12 @@ int device_cus(int dev) {
   }
   return d.cus;
 }
-int blocks_per_cu(int dev, int prec, size_t lds, int var) {
+int blocks_per_cu(int dev, int prec, size_t lds, bool masked) {
   std::lock_guard<std::mutex> lk(g_dev_mu);
   auto& d = g_dev[dev];
-  auto& e = d.bpc[{prec, var}];
-  if (e.second == 0 || e.first != lds) e = {lds, rtwk::trace_blocks_per_cu(prec, lds, var)};
+  auto& e = d.bpc[{prec, masked}];
+  if (e.second == 0 || e.first != lds) e = {lds, rtwk::trace_blocks_per_cu(prec, lds, masked)};
   return e.second;
-}
-// Kernel tuning variant (rtw_trace.hip VAR bits): the product library holds
-// one per precision (rtw_internal.hpp kDefaultVarF64 / kDefaultVarF32).
-// RTW_VARIANT selects another one of a -DRTW_MEASURE build (tools/); a value
-// that was not compiled in is refused by launch_all.
-int kernel_variant(uint32_t precision) {
-  const char* v = dev_knob("RTW_VARIANT");
-  if (v && *v) return atoi(v);
-  return precision == RTW_PRECISION_F32 ? rtwk::kDefaultVarF32 : rtwk::kDefaultVarF64;
 }
 
 }  // namespace
@@ -276,8 +267,8 @@ void fill_args(rtwk::TraceArgs<R>& a, const rtwk::SceneView<R>& v, const rtw_cam
 }
 
 // n_clusters: clusters whose slot -> position table (cpos) is staged, 0 unless
-// the launched kernel runs the clustered pretest (f64 megakernel with
-// kVarCluster and clusters_usable): other paths neither read nor stage it.
+// the launched kernel runs the clustered pretest (f64 and clusters_usable):
+// other paths neither read nor stage it.
 size_t lds_bytes(const rtw_scene_s* sc, int prec, uint32_t n_clusters) {
   const size_t r = prec == 1 ? 4 : 8;
   return rtwk::kCoopLdsBytes + r * (8 * ((size_t)sc->n + 1) + (size_t)sc->n + 8 * (size_t)sc->nm + 4 * (size_t)sc->ng) +
@@ -300,16 +291,16 @@ uint32_t clusters_usable(const rtw_scene_s* sc, const rtw_camera* cam) {
 template <typename R>
 int launch_engine(const rtwk::SceneView<R>& view, const rtw_camera* cam, const rtw_params* p, unsigned char* ws,
                   const WsLayout& L, uint64_t seed_adv, const RtwPassMap& map, uint32_t cl_on, int dev, size_t lds,
-                  uint32_t grid_cap, hipStream_t stream, int mode, int var) {
+                  uint32_t grid_cap, hipStream_t stream, int mode, bool masked) {
   rtwk::TraceArgs<R> a;
   fill_args(a, view, cam, p, ws, L, seed_adv);
   map.apply(a);
   a.sc.cluster_on = cl_on;
   if (!cl_on) a.sc.n_clusters = 0u;  // nothing to stage (lds_bytes)
-  // The primary-first loop (kVarPrimaryFirst): the megakernel with the clusters on and every clustered slot in
+  // The primary-first loop: the megakernel's f64 frame kernel with the clusters on and every clustered slot in
   // one 64-slot block (a lane's tile mask is two words); else the kernel runs the rotated loop.
-  a.primary_on = (p->engine == RTW_ENGINE_MEGAKERNEL && (var & rtwk::kVarPrimaryFirstBit) != 0 && cl_on &&
-                  a.sc.n_clusters * rtwk::kClusterSlots <= 64u)
+  a.primary_on = (p->engine == RTW_ENGINE_MEGAKERNEL && rtwk::trace_primary_first((int)p->precision, masked) &&
+                  cl_on && a.sc.n_clusters * rtwk::kClusterSlots <= 64u)
                      ? 1u
                      : 0u;
   if (p->engine == RTW_ENGINE_WAVEFRONT) {
@@ -319,9 +310,9 @@ int launch_engine(const rtwk::SceneView<R>& view, const rtw_camera* cam, const r
   const uint32_t grid = std::max(1u, std::min(grid_cap, (a.total_units + 255) / 256));
   hipError_t e;
   if constexpr (sizeof(R) == 8)
-    e = rtwk::launch_trace_f64(a, grid, lds, stream, mode, var);
+    e = rtwk::launch_trace_f64(a, grid, lds, stream, mode, masked);
   else
-    e = rtwk::launch_trace_f32(a, grid, lds, stream, mode, var);
+    e = rtwk::launch_trace_f32(a, grid, lds, stream, mode, masked);
   if (e != hipSuccess) return rtw_fail(RTW_EHIP, "trace kernel launch: %s", hipGetErrorString(e));
   return RTW_OK;
 }
@@ -342,30 +333,20 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
                                    &map, &launch);
   if (st0 != RTW_OK || !launch) return st0;
   auto* ws = static_cast<unsigned char*>(workspace);
-  const int var = (map.list && p->engine == RTW_ENGINE_MEGAKERNEL)
-                      ? (p->precision == RTW_PRECISION_F32 ? rtwk::kMaskedVarF32 : rtwk::kMaskedVarF64)
-                      : kernel_variant(p->precision);
-  if (p->engine != RTW_ENGINE_WAVEFRONT && !rtwk::trace_variant_built((int)p->precision, var))
-    return rtw_fail(RTW_EINVAL, "RTW_VARIANT=%d: trace kernel variant not built into this library", var);
-  // The clustered pretest runs only in the f64 megakernel variants with
-  // kVarCluster (or the wavefront kernels built with it: kWfCluster), and only
-  // when the shutter lies in every time group.
-  const uint32_t cl_on = (p->precision == RTW_PRECISION_F64 &&
-                          (p->engine == RTW_ENGINE_MEGAKERNEL ? (var & rtwk::kVarClusterBit) != 0 : rtwk::kWfCluster))
-                             ? clusters_usable(sc, cam)
-                             : 0u;
+  const bool masked = map.list && p->engine == RTW_ENGINE_MEGAKERNEL;  // the megakernel's masked configuration
+  // The clustered pretest runs only in f64 (both engines), and only when the
+  // shutter lies in every time group.
+  const uint32_t cl_on = p->precision == RTW_PRECISION_F64 ? clusters_usable(sc, cam) : 0u;
   size_t lds = lds_bytes(sc, (int)p->precision, cl_on ? sc->v64.n_clusters : 0u);
-  if (p->engine == RTW_ENGINE_MEGAKERNEL && (var & rtwk::kVarHomeLdsBit) != 0)
-    lds += 8 + (rtwk::kHomeLdsBytesPerWave + ((var & rtwk::kVarPathLdsBit) ? rtwk::kPathLdsBytesPerWave : 0) +
-                ((var & rtwk::kVarUnitBaseBit) ? rtwk::kUnitBaseLdsBytesPerWave : 0) +
-                ((var & rtwk::kVarPrimaryFirstBit) ? rtwk::kPrimaryLdsBytesPerWave : 0)) *
-                   (rtwk::kTraceBlock / 64);  // (8: alignment of the home block)
+  if (p->engine == RTW_ENGINE_MEGAKERNEL) lds += rtwk::trace_home_lds_bytes((int)p->precision, masked);
   if (lds > 64 * 1024) return rtw_fail(RTW_UNSUPPORTED, "scene tables need %zu B of LDS", lds);
-  const uint32_t grid_cap = (uint32_t)(device_cus(dev) * blocks_per_cu(dev, (int)p->precision, lds, var));
+  const uint32_t grid_cap = (uint32_t)(device_cus(dev) * blocks_per_cu(dev, (int)p->precision, lds, masked));
   if (timer) HIP_TRY(hipEventRecord(timer->start, stream));
   const int st = p->precision == RTW_PRECISION_F32
-                     ? launch_engine(sc->v32, cam, p, ws, L, seed_adv, map, cl_on, dev, lds, grid_cap, stream, mode, var)
-                     : launch_engine(sc->v64, cam, p, ws, L, seed_adv, map, cl_on, dev, lds, grid_cap, stream, mode, var);
+                     ? launch_engine(sc->v32, cam, p, ws, L, seed_adv, map, cl_on, dev, lds, grid_cap, stream, mode,
+                                     masked)
+                     : launch_engine(sc->v64, cam, p, ws, L, seed_adv, map, cl_on, dev, lds, grid_cap, stream, mode,
+                                     masked);
   if (st != RTW_OK) return st;
   if (timer) {
     HIP_TRY(hipEventRecord(timer->stop, stream));

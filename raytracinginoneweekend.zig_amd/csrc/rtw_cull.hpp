@@ -75,7 +75,7 @@ RTWC_HD float cull_x(float ox, float oy, float oz, float dx, float dy, float dz,
 }
 
 // Bounding sphere of a cluster of n (possibly moving) narrow spheres for the
-// clustered pretest (trace VAR kVarCluster; host only).  Member i: centre
+// clustered pretest (rtw_device.hpp closest_hit, f64; host only).  Member i: centre
 // c0_i + f * dc_i for f in [0, 1] (the shutter inside its time group),
 // radius |r_i|.  Centre cf = f32 of the centre of the members' swept box;
 // radius R = max_i max(|c0_i - cf|, |c0_i + dc_i - cf|) + |r_i|, widened by

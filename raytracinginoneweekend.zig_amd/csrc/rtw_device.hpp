@@ -66,65 +66,11 @@ __device__ __forceinline__ V3<R> ld3(const __attribute__((address_space(4))) R* 
   return mk(p[0], p[1], p[2]);
 }
 
-// sqrt of the hot path: rtwm::sqrt_rn (same bits as sqrt, fewer instructions)
-// for f64 when VAR has kVarFastSqrt.
-constexpr int kVarFastSqrt = 32768;
-// Dielectric: Schlick's r0^2 for both ratios precomputed in the material
-// record (rtw_scene_pack.cpp: doubles 0, 1 of a dielectric; its albedo is unused).
-constexpr int kVarR0Table = 131072;
-// Pretest: pairs flagged y-only (rtw_scene_pack.cpp cull_tg bit 16) skip the x/z
-// centre updates.
-constexpr int kVarYOnly = 65536;
-// Trace loop rotated so that the lens-disk points of new samples and the
-// unit-ball points of Lambertian / Metal hits come from ONE coop_reject_mixed
-// pass per iteration (rtw_trace.hip).
-constexpr int kVarMergedStart = 262144;
-// With kVarMergedStart: the sample's time draw and the dielectric's draw are
-// made inside the same cooperative pass (coop_reject_mixed `raw`).
-constexpr int kVarPreDraw = 524288;
-// Unit refill: each 64-unit batch's (tile, chunk) decoded once per batch.
-constexpr int kVarBatchDecode = 1048576;
-// kVarPathLds (with kVarHomeLds and kVarMergedStart): the lane's attenuation T and
-// RNG state live in its LDS home block between the phases that use them
-// (sampler, scatter, sample start, miss), so neither is held in VGPRs across
-// the closest hit (measurement: within noise).
-constexpr int kVarPathLds = 33554432;
-// kVarUnitBase (with kVarHomeLds): the unit's RNG block base
-// seed_base + (pixel << 40) * gamma and its f64 pixel column / reference row
-// are made once per unit (home block); a sample's state is then
-// base + s * (gamma << 16) — the same value as (((pixel << 24) | s) << 16) *
-// gamma + seed_base mod 2^64, since s < 2^24 (rtw_validate_params) makes the
-// | an addition — and u, v add the stored f64 coordinates (measurement:
-// within noise).
-constexpr int kVarUnitBase = 67108864;
-// kVarLaneDisk (with kVarMergedStart): new samples' lens-disk points from each
-// lane's own rejection loop after the cooperative pass, not inside it
-// (measurement: 4.8 % slower in the rotated loop, profiles/r06/mk_var_ab.txt;
-// with kVarPrimaryFirst, where the disk point is needed before the pass, it
-// is 0.6 % faster than a disk-only pass and the default).
-constexpr int kVarLaneDisk = 134217728;
-// kVarMasked: a masked accumulator pass — the take maps the dealt tile through
-// TraceArgs::tile_list and skips the units of inactive pixels (tile_mask).
-constexpr int kVarMasked = 268435456;
-// f64 pretest over spatial clusters of narrow spheres (SceneView ccull...):
-// a wave skips a cluster's member pretests when every lane's line provably
-// misses the cluster's bounding sphere.
-constexpr int kVarCluster = 2097152;
-// kVarPrimaryFirst (with kVarMergedStart, kVarCluster, kVarHomeLds; f64): a lane
-// that starts a sample resolves its camera ray itself, before the cooperative
-// pass — wide spheres, then the exact per-lane survivor loop over the mask of
-// its unit batch's tile (rtw_beam.hpp) — and shades that hit in the same
-// iteration (rtw_trace.hip).  Runs when TraceArgs::primary_on is set.
-constexpr int kVarPrimaryFirst = kVarPrimaryFirstBit;
-// Measurement only (phase duplication): the clustered path's survivor
-// loop runs twice, the first pass's result discarded (same image).
-constexpr int kVarDupSurvivors = 8388608;
-// Megakernel: the lane's unit fields (pixel, chunk, sample end) and f64
-// chunk sum live in LDS instead of VGPRs (rtw_trace.hip HomeLds).
-constexpr int kVarHomeLds = kVarHomeLdsBit;
-template <typename R, int VAR>
+// sqrt of the hot path: for f64 rtwm::sqrt_rn (same bits as sqrt, fewer
+// instructions); EXACT: the library's sqrt (the wavefront drain kernels).
+template <typename R, bool EXACT = false>
 __device__ __forceinline__ R sqrt_k(R x) {
-  if constexpr ((VAR & kVarFastSqrt) != 0 && sizeof(R) == 8)
+  if constexpr (!EXACT && sizeof(R) == 8)
     return rtwm::sqrt_rn(x);
   else
     return sqrt(x);
@@ -154,35 +100,6 @@ __device__ __forceinline__ uint32_t dealt_unit(uint32_t raw, const A& a) {
 // W + (k + 1) * gamma and any lane can evaluate any draw (coop_reject).
 constexpr uint64_t kGamma = 0x9e3779b97f4a7c15ULL;
 constexpr uint64_t kExt = 0x5851F42D4C957F2DULL;
-// z * c mod 2^64 on 32-bit lanes as three chained v_mad_u64_u32: the low
-// product lo*c_lo, then the high word accumulated as lo32(hi*c_lo + ph) and
-// lo32(lo*c_hi + that) (the laundering keeps each mad 64-bit, which the
-// optimiser would otherwise narrow back to v_mul_lo_u32 + v_add3_u32: four
-// instructions per product).  Same bits as the C multiply.
-template <uint64_t C>
-__device__ __forceinline__ uint64_t mul64c(uint64_t z) {
-  const uint32_t lo = (uint32_t)z, hi = (uint32_t)(z >> 32);
-  const uint64_t p = (uint64_t)lo * (uint32_t)C;
-  uint64_t q = (uint64_t)hi * (uint32_t)C + (p >> 32);
-  asm("" : "+v"(q));
-  // q's high word is don't-care: only the low word of r is used, so q goes
-  // in whole as the third product's addend (no zero-extension move)
-  uint64_t r = (uint64_t)lo * (uint32_t)(C >> 32) + q;
-  asm("" : "+v"(r));
-  return (r << 32) | (uint32_t)p;
-}
-// z ^ (z >> k): one v_lshrrev_b64 + two v_xor_b32 (from 32-bit v_alignbit /
-// shift / xor instead: 1.3 % slower, profiles/r04/xsh32_scalar_decide_ab.txt)
-template <int K>
-__device__ __forceinline__ uint64_t xsh(uint64_t z) {
-  return z ^ (z >> K);
-}
-#ifndef RTW_RNG_MIX
-#define RTW_RNG_MIX 10
-#endif
-#if RTW_RNG_MIX != 10 && !defined(RTW_MEASURE)
-#error "RTW_RNG_MIX other than 10 (the Tier-B contract) exists only in the -DRTW_MEASURE build (A/B timing)"
-#endif
 // One Feistel half-round on the state's 32-bit words: t = x * M as ONE
 // v_mad_u64_u32 (the full 64-bit product), the other word ^= hi(t), x = lo(t).
 template <uint32_t M>
@@ -191,31 +108,17 @@ __device__ __forceinline__ void feistel(uint32_t& x, uint32_t& y) {
   y ^= (uint32_t)(t >> 32);
   x = (uint32_t)t;
 }
-// The Tier-B mixer of a Weyl state (oracle/rtw_oracle.c ro_tb_mix).
-//  10 (the contract since round 5): four Feistel half-rounds, the first on the
-//     high word — 4 v_mad_u64_u32 + 4 v_xor_b32 (tests/native/rng_stats.c
-//     mixer 10: passes the battery over 2^32 draws of the render's layout);
-//   0: Zig's SplitMix64 (rounds 1-4): 2 x (3 v_mad_u64_u32) + 3 x 64-bit
-//     xorshift;  1: its 32-bit-fold form (MurmurHash3 fmix64 with >> 32).
+// The Tier-B mixer of a Weyl state (oracle/rtw_oracle.c ro_tb_mix; the
+// contract since round 5): four Feistel half-rounds, the first on the high
+// word — 4 v_mad_u64_u32 + 4 v_xor_b32 (tests/native/rng_stats.c mixer 10:
+// passes the battery over 2^32 draws of the render's layout).
 __device__ __forceinline__ uint64_t sm_mix(uint64_t z) {
-#if RTW_RNG_MIX == 10
   uint32_t a = (uint32_t)(z >> 32), b = (uint32_t)z;
   feistel<0xD2511F53u>(a, b);
   feistel<0xCD9E8D57u>(b, a);
   feistel<0x9E3779B1u>(a, b);
   feistel<0x85EBCA6Bu>(b, a);
   return ((uint64_t)a << 32) | b;
-#elif RTW_RNG_MIX == 1
-  z = mul64c<0xff51afd7ed558ccdULL>(xsh<32>(z));
-  z = mul64c<0xc4ceb9fe1a85ec53ULL>(xsh<32>(z));
-  return xsh<32>(z);
-#elif RTW_RNG_MIX == 2  // (measurement only: fails the battery's neighbour-pixel tests)
-  return xsh<32>(mul64c<0xd6e8feb86659fd93ULL>(xsh<32>(z)));
-#else
-  z = mul64c<0xbf58476d1ce4e5b9ULL>(xsh<30>(z));
-  z = mul64c<0x94d049bb133111ebULL>(xsh<27>(z));
-  return xsh<31>(z);
-#endif
 }
 __device__ __forceinline__ uint64_t sm_next(uint64_t& st) {
   st += kGamma;
@@ -553,18 +456,8 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <typename R, int D, bool COOP>
+template <typename R, int D>
 __device__ __forceinline__ void coop_reject(bool need, uint64_t& st, R (&x)[D], CoopSlots* slots, uint32_t lid) {
-  if constexpr (!COOP) {  // the literal per-lane loop (tuning variant 16)
-    if (need) {
-      for (;;) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) x[i] = rrange_m11<R>(st);
-        if (in_unit_ball<R, D>(x)) break;
-      }
-    }
-    return;
-  }
   bool pending = false;
   if (need) {  // round 0: every lane its own first candidate
 #pragma unroll
@@ -709,9 +602,9 @@ __device__ __forceinline__ void coop_reject_mixed(uint32_t dim, uint64_t& st, R 
 }
 
 // v / |v| with the three divisions done against RN(1/|v|) (rtw_math.hpp div_rn).
-template <typename R, int VAR = 0>
+template <typename R>
 __device__ __forceinline__ V3<R> normalized_rn(V3<R> v) {  // vec.zig:32-39
-  const R n = sqrt_k<R, VAR>(norm2(v));
+  const R n = sqrt_k<R>(norm2(v));
   if (n == (R)0) return v;
   const R y = (R)1 / n;
   return mk(rtwm::div_rn(v.x, n, y), rtwm::div_rn(v.y, n, y), rtwm::div_rn(v.z, n, y));
@@ -728,15 +621,6 @@ __device__ __forceinline__ void start_sample_uv(const RTW_CONST TraceArgs<R>* Ap
   L.rs = A.seed_base + ((((pixel << 24) | (uint64_t)L.s)) << 16) * kGamma;
   u = rtwm::div_rn((R)L.px + rnd<R>(L.rs), (R)A.W - (R)1, A.inv_w1);
   v = rtwm::div_rn((R)j + rnd<R>(L.rs), (R)A.H - (R)1, A.inv_h1);
-}
-// start_sample_uv with the unit's precomputed base and coordinates (kVarUnitBase)
-template <typename R>
-__device__ __forceinline__ void start_sample_uv_base(const RTW_CONST TraceArgs<R>* Ap, Lane<R>& L, uint64_t base,
-                                                     R px, R j, R& u, R& v) {
-  const RTW_CONST TraceArgs<R>& A = *opaque(Ap);
-  L.rs = base + (uint64_t)L.s * (kGamma << 16);
-  u = rtwm::div_rn(px + rnd<R>(L.rs), (R)A.W - (R)1, A.inv_w1);
-  v = rtwm::div_rn(j + rnd<R>(L.rs), (R)A.H - (R)1, A.inv_h1);
 }
 // Part 2, after the lens-disk point (rand.zig:30-36, coop_reject<R, 2>).
 // PRE: the time draw was made by coop_reject_mixed (`traw`, the draw at
@@ -885,7 +769,7 @@ struct KStats {
   unsigned long long candwave = 0, candlane = 0, disc = 0, wave_iters = 0;
   unsigned long long cull_lanes = 0, cull_iters = 0;
   unsigned long long cl_tests = 0, cl_skips = 0;  // clustered pretest: (wave, cluster) pairs, skipped ones
-  // kVarPrimaryFirst: wave-iterations with a primary phase, lanes whose sample ended in it (idle for the rest
+  // primary-first loop: wave-iterations with a primary phase, lanes whose sample ended in it (idle for the rest
   // of the iteration), the batches' mask popcounts summed
   unsigned long long prim_rounds = 0, prim_idle = 0, mask_pop = 0;
   uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -907,21 +791,21 @@ struct KStats {
 // of the winner in `hit` (-1: miss) and its root in `tmax`.  `tmax` must be
 // +inf and `hit` -1 on entry.  Wave-converged control is NOT required, but the
 // wide-sphere and pretest loops are wave-uniform (scalar-loaded records).
-// VAR: rtw_trace.hip trace_kernel tuning bits (1, 2, 64 are read here).
+// FLAT (the wavefront drain kernels): the library's sqrt and, in f64, the flat
+// pretest over 64-sphere blocks; else sqrt_k's fast f64 form and the clustered
+// pretest where the scene has clusters (f64, S.cluster_on).
 // SV: SceneView<R> (a copy in registers) or `const RTW_CONST SceneView<R>`
 // (the kernel argument itself, re-read with scalar loads where used: keeps
 // the scene fields out of the SGPR budget of the rest of the loop).
-// PRIMARY (kVarPrimaryFirst; f64, clusters on, one 64-slot block): a camera
+// PRIMARY (the primary-first loop; f64, clusters on, one 64-slot block): a camera
 // ray — the wide spheres exactly, then the per-lane exact tests of the slots
 // in (pm0, pm1), the mask of the lane's tile, in place of the pretest.
-template <typename R, bool F32, int MODE, int VAR, bool PRIMARY = false, typename SV>
+template <typename R, bool F32, int MODE, bool PRIMARY = false, bool FLAT = false, typename SV>
 __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, const Lane<R>& L, R tmin,
                                             R pre_k, uint32_t lid, KStats& st, int& hit, R& tmax, uint32_t pm0 = 0u,
                                             uint32_t pm1 = 0u) {
   static_assert(!PRIMARY || !F32, "the primary form is f64 only (clustered tables)");
   constexpr bool STATS = MODE == 1;
-  constexpr bool CULL = !(VAR & 64);  // packed-f32 pretest for narrow spheres
-  constexpr int kSphUnroll = (VAR & 2) ? 2 : 1;
   const R a = norm2(L.d);
   const R inv_a = (R)1 / a;          // RN(1/a): roots via div_rn
   const R pre_lim = pre_k * a;     // "both roots behind" prefilter bound
@@ -970,7 +854,7 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
         st.disc += 1;
       }
       if (cand) {
-        const R sq = sqrt_k<R, VAR>(disc);
+        const R sq = sqrt_k<R, FLAT>(disc);
         R root = rtwm::div_rn(-hb - sq, a, inv_a);
         if (root < tmin) root = rtwm::div_rn(-hb + sq, a, inv_a);
         accept(root, (int)k, (int)(meta >> 20));
@@ -979,17 +863,10 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
   };
   auto rec_at = [&](uint32_t k) {
     Rec<R> r;
-    if constexpr (VAR & 1) {
-      const R* sp = T.sph + 8 * k;
-      r.meta = T.meta[k];
-      r.c[0] = sp[0], r.c[1] = sp[1], r.c[2] = sp[2], r.dc[0] = sp[3], r.dc[1] = sp[4], r.dc[2] = sp[5];
-      r.r2 = sp[6];
-    } else {
-      const RTW_CONST R* sp = c_sph + 8 * k;
-      r.meta = c_meta[k];
-      r.c[0] = sp[0], r.c[1] = sp[1], r.c[2] = sp[2], r.dc[0] = sp[3], r.dc[1] = sp[4], r.dc[2] = sp[5];
-      r.r2 = sp[6];
-    }
+    const RTW_CONST R* sp = c_sph + 8 * k;
+    r.meta = c_meta[k];
+    r.c[0] = sp[0], r.c[1] = sp[1], r.c[2] = sp[2], r.dc[0] = sp[3], r.dc[1] = sp[4], r.dc[2] = sp[5];
+    r.r2 = sp[6];
     return r;
   };
   // f32 mode: wide spheres (radius >= 100), solved in f64.
@@ -1009,7 +886,7 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
   auto static_range = [&](uint32_t b, uint32_t e) {
     if (b < e) {
       Rec<R> cur = rec_at(b);
-#pragma unroll kSphUnroll
+#pragma unroll 1  // (unrolled by 2: within noise, DESIGN.md §6's table)
       for (uint32_t k = b; k < e; ++k) {
         const Rec<R> nxt = rec_at(k + 1);
         test(k, cur.meta, cur.c[0], cur.c[1], cur.c[2], cur.r2);
@@ -1021,7 +898,7 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
   auto moving_range = [&](uint32_t b, uint32_t e) {
     if (b < e) {
       Rec<R> cur = rec_at(b);
-#pragma unroll kSphUnroll
+#pragma unroll 1
       for (uint32_t k = b; k < e; ++k) {
         const Rec<R> nxt = rec_at(k + 1);
         const int g = (int)((cur.meta >> 2) & 63u);
@@ -1080,7 +957,7 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
     moving_range(S.g_static, S.g_moving_wide);
     const RTW_CONST uint32_t* cval = cptr(S.cvalid);
     run_survivors(pm0 & cval[0], pm1 & cval[1], 0u, true);
-  } else if (!CULL || !S.cull_on) {
+  } else if (!S.cull_on) {
     static_range(F32 ? S.g_static_wide : 0u, S.g_static);
     moving_range(F32 ? S.g_moving_wide : S.g_static, S.n);
   } else {
@@ -1094,20 +971,8 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
     const float af = (float)a;
     const rtwc::LaneCull lc = rtwc::lane_cull((float)L.o.x, (float)L.o.y, (float)L.o.z, af, S.cull_cmax);
     const rtwc::LaneConst lk = rtwc::lane_const(af, lc.alpha, S.cull_rho);
-#ifndef RTW_CULL_BC  // (the bc() pair form: -DRTW_CULL_BC, measurement builds)
     const CullPairs cp = cull_pairs((float)L.o.x, (float)L.o.y, (float)L.o.z, (float)L.d.x, (float)L.d.y, (float)L.d.z,
                                     lk.na, lk.k);
-#define RTW_CULL_OC(rec) const CullOc oc_ = cull_oc(rec, cp)
-#define RTW_CULL(M, rec, fr) cull_pair_sel<M>(rec, oc_, cp, cp.nk, fr)
-#define RTW_CULL_K(M, rec, kp, fr) cull_pair_sel<M, 0>(rec, cull_oc(rec, cp), cp, kp, fr)
-#else
-    const f2 ox = bc((float)L.o.x), oy = bc((float)L.o.y), oz = bc((float)L.o.z);
-    const f2 dx = bc((float)L.d.x), dy = bc((float)L.d.y), dz = bc((float)L.d.z);
-    const f2 na = bc(lk.na), alpha = bc(lk.k);
-#define RTW_CULL_OC(rec) (void)0
-#define RTW_CULL(M, rec, fr) cull_pair<M>(rec, ox, oy, oz, dx, dy, dz, na, alpha, fr)
-#define RTW_CULL_K(M, rec, kp, fr) cull_pair<M>(rec, ox, oy, oz, dx, dy, dz, na, kp, fr)
-#endif
     const RTW_CONST f2* ct = reinterpret_cast<const RTW_CONST f2*>(cptr(S.cull));
     const RTW_CONST uint32_t* ctg = cptr(S.cull_tg);
     const RTW_CONST float* ctf = cptr(S.tg_f);
@@ -1131,19 +996,16 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
             const uint32_t tgp = tgp_nxt;
             tgp_nxt = ctg[p + 1];
             f2 x;
-            RTW_CULL_OC(cur);
+            const CullOc oc = cull_oc(cur, cp);
             if (p < np_static) {
-              x = RTW_CULL(0, cur, fr2);
+              x = cull_pair_sel<0>(cur, oc, cp, cp.nk, fr2);
             } else {
               if ((tgp & 0xFFFFu) != tgp_cur) {  // wave-uniform
                 tgp_cur = tgp & 0xFFFFu;
                 const uint32_t g0 = tgp & 0xFFu, g1 = (tgp >> 8) & 0xFFu;
                 fr2 = f2{(tf - ctf[4 * g0]) * ctf[4 * g0 + 2], (tf - ctf[4 * g1]) * ctf[4 * g1 + 2]};
               }
-              if ((VAR & kVarYOnly) != 0 && (tgp >> 16) != 0u)
-                x = RTW_CULL(2, cur, fr2);
-              else
-                x = RTW_CULL(1, cur, fr2);
+              x = cull_pair_sel<1>(cur, oc, cp, cp.nk, fr2);
             }
             sk[h] = __builtin_amdgcn_alignbit(sk[h], __float_as_uint(x.x), 31);
             sk[h] = __builtin_amdgcn_alignbit(sk[h], __float_as_uint(x.y), 31);
@@ -1156,7 +1018,7 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
       }
     };
     bool clustered_done = false;
-    if constexpr ((VAR & kVarCluster) != 0 && !F32) {
+    if constexpr (!FLAT && !F32) {
       if (S.cluster_on) {  // kernel argument: wave-uniform
         clustered_done = true;
         const f2 kcl = bc(lc.alpha * S.cull_rho_cl);
@@ -1170,7 +1032,8 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
           // cluster pretest (bounding spheres as static pair records): bit c = proven miss
           uint32_t cmiss = 0u;
           for (uint32_t q = 0; 2u * q < nb; ++q) {
-            const f2 x = RTW_CULL_K(0, ld_pair(ccl, (cb >> 1) + q), kcl, bc(0.0f));
+            const PairRec crec = ld_pair(ccl, (cb >> 1) + q);
+            const f2 x = cull_pair_sel<0, 0>(crec, cull_oc(crec, cp), cp, kcl, bc(0.0f));
             cmiss |= ((__float_as_uint(x.x) >> 31) << (2u * q)) | ((__float_as_uint(x.y) >> 31) << (2u * q + 1u));
           }
           if (!lc.ok) cmiss = 0u;
@@ -1197,16 +1060,17 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
                 const PairRec rec = ld_pair(cct, p);
                 const uint32_t tgp = cctg[p];
                 f2 x;
-                RTW_CULL_OC(rec);
+                const CullOc oc = cull_oc(rec, cp);
                 if (tgp & (1u << 17)) {
-                  x = RTW_CULL(0, rec, fr2);
+                  x = cull_pair_sel<0>(rec, oc, cp, cp.nk, fr2);
                 } else {
                   if ((tgp & 0xFFFFu) != tgp_cur) {  // wave-uniform
                     tgp_cur = tgp & 0xFFFFu;
                     const uint32_t g0 = tgp & 0xFFu, g1 = (tgp >> 8) & 0xFFu;
                     fr2 = f2{(tf - ctf[4 * g0]) * ctf[4 * g0 + 2], (tf - ctf[4 * g1]) * ctf[4 * g1 + 2]};
                   }
-                  x = (tgp & (1u << 16)) ? RTW_CULL(2, rec, fr2) : RTW_CULL(1, rec, fr2);
+                  x = (tgp & (1u << 16)) ? cull_pair_sel<2>(rec, oc, cp, cp.nk, fr2)   // (moving along y only)
+                                         : cull_pair_sel<1>(rec, oc, cp, cp.nk, fr2);
                 }
                 b8 = __builtin_amdgcn_alignbit(b8, __float_as_uint(x.x), 31);
                 b8 = __builtin_amdgcn_alignbit(b8, __float_as_uint(x.y), 31);
@@ -1224,15 +1088,6 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
           }
           if constexpr (STATS) st.cull_lanes += __popc(m0) + __popc(m1);
           RTW_STAMP(2)
-          if constexpr ((VAR & kVarDupSurvivors) != 0) {  // measurement: the survivors' exact tests twice
-            int h2 = hit, o2 = hit_orig;
-            R t2 = tmax;
-            bool n2 = nan_seen;
-            uint32_t q0 = m0, q1 = m1;
-            asm volatile("" : "+v"(q0), "+v"(q1));
-            run_survivors(q0, q1, cb * CS, true);
-            hit = h2, hit_orig = o2, tmax = t2, nan_seen = n2;
-          }
           run_survivors(m0, m1, cb * CS, true);
           RTW_STAMP(6)
         }
@@ -1242,13 +1097,6 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
     for (uint32_t base = 0; base < S.nn; base += 64) {
       uint32_t sk[2];
       pretest_block(base, sk);
-      if constexpr ((VAR & 2048) != 0) {  // measurement: the block twice (same image; round 1's phase costs)
-        uint32_t base2 = base;
-        asm volatile("" : "+s"(base2));
-        uint32_t sk2[2];
-        pretest_block(base2, sk2);
-        asm volatile("" ::"v"(sk2[0]), "v"(sk2[1]));
-      }
       const uint32_t rem = S.nn - base;  // real spheres in this block
       const uint32_t v0 = rem >= 32u ? ~0u : ~(~0u >> rem);
       const uint32_t v1 = rem >= 64u ? ~0u : (rem <= 32u ? 0u : ~(~0u >> (rem - 32u)));
@@ -1281,7 +1129,7 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
 // at state L.rs + gamma); it is consumed only when the reference draws it.
 // POINT: L.o already holds the hit point p = o + tmax * d (the wavefront's
 // path form, made with these operations where the hit was found), tmax unused.
-template <typename R, bool F32, int VAR = 0, bool PRE = false, bool POINT = false>
+template <typename R, bool F32, bool PRE = false, bool POINT = false>
 __device__ __forceinline__ bool scatter_hit(const LdsTables<R>& T, Lane<R>& L, int hit, R tmax, uint32_t kind,
                                             const R (&b3)[3], R draw = (R)0) {
   // Hit record of the winner (hittable.zig:118-128, :189-198).
@@ -1305,7 +1153,7 @@ __device__ __forceinline__ bool scatter_hit(const LdsTables<R>& T, Lane<R>& L, i
   // One normalisation per lane: the unit-ball point (Lambertian) or the
   // ray direction (Metal, Dielectric).
   const V3<R> rs = mk(b3[0], b3[1], b3[2]);
-  const V3<R> nv = normalized_rn<R, VAR>(kind <= 1u ? rs : L.d);
+  const V3<R> nv = normalized_rn<R>(kind <= 1u ? rs : L.d);
   const V3<R> ud = nv;
   // Metal and Dielectric share reflect(ud, normal) (material.zig:112-114) and
   // its dot product (the wave runs both branches): the Dielectric's
@@ -1329,16 +1177,12 @@ __device__ __forceinline__ bool scatter_hit(const LdsTables<R>& T, Lane<R>& L, i
     const R ir = mp[7];
     const R ratio = front ? mp[6] : ir;
     const R cos_t = fmin(-dun, (R)1);
-    const R sin_t = sqrt_k<R, VAR>((R)1 - cos_t * cos_t);
+    const R sin_t = sqrt_k<R>((R)1 - cos_t * cos_t);
     bool refr = false;
     if (ratio * sin_t <= (R)1) {
-      R r1;
-      if constexpr ((VAR & kVarR0Table) != 0) {
-        r1 = front ? mp[0] : mp[1];  // host: RN(RN((1-ratio)/(1+ratio))^2) per ratio
-      } else {
-        const R r0 = ((R)1 - ratio) / ((R)1 + ratio);
-        r1 = r0 * r0;
-      }
+      // Schlick's r0^2 for both ratios from the material record (rtw_scene_pack.cpp: doubles 0, 1 of a
+      // dielectric; its albedo is unused): host RN(RN((1-ratio)/(1+ratio))^2) per ratio
+      const R r1 = front ? mp[0] : mp[1];
       const R x = (R)1 - cos_t;
       const R x2 = x * x;
       const R refl_p = r1 + ((R)1 - r1) * (x * (x2 * x2));  // Zig pow(x, 5.0)
@@ -1351,7 +1195,7 @@ __device__ __forceinline__ bool scatter_hit(const LdsTables<R>& T, Lane<R>& L, i
     }
     if (refr) {  // refract (material.zig:116-121); its cos_theta is cos_t
       const V3<R> perp = mul(add(ud, mul(normal, cos_t)), ratio);
-      const V3<R> par = mul(normal, -sqrt_k<R, VAR>(fabs((R)1 - norm2(perp))));
+      const V3<R> par = mul(normal, -sqrt_k<R>(fabs((R)1 - norm2(perp))));
       ndir = add(perp, par);
     } else {
       ndir = refl;

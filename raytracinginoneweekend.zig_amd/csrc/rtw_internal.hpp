@@ -48,7 +48,7 @@ struct SceneView {
   uint32_t cull_on;           // pretest usable for this scene (rtw_cull.hpp limits)
   float cull_cmax;            // max |c0|_inf + |c1 - c0|_inf over narrow spheres (rounded up)
   float cull_rho;             // max 2 r^2 + 1 over narrow spheres (rounded up)
-  // Clustered pretest (trace VAR kVarCluster, f64): the narrow spheres in
+  // Clustered pretest (f64): the narrow spheres in
   // spatial clusters of <= 8 slots (cluster c = slots 8c..8c+7, padded with
   // dummy slots); a bounding sphere per cluster, pretested first, lets a wave
   // skip every member's pretest when no lane's ray line can meet it.
@@ -76,7 +76,7 @@ struct TraceArgs {
   uint32_t total_units;
   uint32_t upt_m, upt_sh, tx_m, tx_sh;  // rtwm::udiv magic of units per tile (64 * n_chunks) and tiles_x
   uint32_t unit_order;            // rtw_device.hpp dealt_unit: 0 image order, 1 last-first
-  uint32_t primary_on;            // kVarPrimaryFirst: the primary-first loop runs (clusters on, one 64-slot block)
+  uint32_t primary_on;            // the primary-first loop runs (f64 unmasked; clusters on, one 64-slot block)
   uint64_t seed_base;             // SplitMix64(seed).next()
   double* partial;                // [n_chunks][row_count*W][3] chunk sums
   uint32_t* counter;              // work-queue head (zeroed before launch)
@@ -99,69 +99,24 @@ struct FinalizeArgs {
 
 // Launchers (rtw_trace.hip).  Return hipError_t of the launch.
 // mode: 0 = product, 1 = counts (segments/samples), 2 = diagnostic phase stamps
-// var: tuning variant (rtw_trace.hip trace_kernel VAR bits)
-hipError_t launch_trace_f64(const TraceArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, int mode, int var);
-hipError_t launch_trace_f32(const TraceArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, int mode, int var);
+// masked: a masked accumulator pass (TraceArgs::tile_list / tile_mask set; product mode only).
+// The kernel has one configuration per (precision, masked): rtw_trace.hip TraceCfg.
+hipError_t launch_trace_f64(const TraceArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, int mode,
+                            bool masked);
+hipError_t launch_trace_f32(const TraceArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, int mode,
+                            bool masked);
 hipError_t launch_finalize(const FinalizeArgs& a, hipStream_t s);
-// Resident workgroups per CU for the trace kernel (occupancy query); 0 when
-// `var` is not compiled into this library.
-int trace_blocks_per_cu(int precision, size_t lds, int var);
-// The trace_kernel variant of each precision in the product library (VAR bits
-// of rtw_device.hpp / rtw_trace.hip, chosen by the in-process A/B on MI355X,
-// profiles/r01/ab_defaults.txt): scalar sphere records + 512 (scene fields from
-// the kernel argument) + kVarR0Table + kVarMergedStart + kVarPreDraw; f64 also
-// 4 waves/SIMD (4) + kVarFastSqrt + kVarCluster (round 2, +5.4 %,
-// profiles/r02/cluster_ab.txt) + 1024 (the loop's argument fields re-read from
-// the kernel argument too: +0.6 %, profiles/r02/var1024_ab.txt) + kVarHomeLds
-// (round 3, +0.6 %, profiles/r03/home_lds_ab.txt), f32 5 waves/SIMD (8) +
-// kVarHomeLds (+1.3 %, profiles/r03/home_lds_f32_ab.txt).
-// f64 since round 11: kVarPrimaryFirst (camera rays per lane from a per-tile sphere mask, rtw_beam.hpp)
-// with kVarLaneDisk (the lens-disk point of a new sample from the lane's own loop, before its camera ray).
-// Every other variant exists only in the -DRTW_MEASURE build.
-#ifndef RTW_DEFAULT_VAR_F64  // (A/B builds override it; 19826180: the round-6 default)
-#define RTW_DEFAULT_VAR_F64 \
-  (4 + 512 + 1024 + 32768 + 131072 + 262144 + 524288 + 2097152 + 16777216 + 4194304 + 134217728)  // 158238212
-#endif
-constexpr int kDefaultVarF64 = RTW_DEFAULT_VAR_F64;
-constexpr int kVarClusterBit = 2097152;  // rtw_device.hpp kVarCluster (clustered pretest, f64)
-// The wavefront engine's closest-hit variant bits beyond kVarFastSqrt (f64;
-// rtw_wavefront.hip kWfExtendVar): with kVarClusterBit its kernels run the
-// clustered pretest and the host stages the cluster tables for them.  Round 6
-// default: -3.0 % per configs[1] frame (profiles/r06/wf_step_ab.txt; round 2
-// measured it 12 % slower when it spilled in wf_step, which no longer spills).
-#ifndef RTW_WF_VAR_EXTRA  // (A/B builds override it; 0: the flat pretest)
-#define RTW_WF_VAR_EXTRA kVarClusterBit
-#endif
-constexpr bool kWfCluster = (RTW_WF_VAR_EXTRA & kVarClusterBit) != 0;
-// rtw_device.hpp kVarHomeLds: the lane's unit fields and f64 chunk sum in LDS
-// (megakernel), kHomeLdsBytesPerWave per wave after the scene tables.
-constexpr int kVarHomeLdsBit = 16777216;
+// Resident workgroups per CU for the trace kernel (occupancy query).
+int trace_blocks_per_cu(int precision, size_t lds, bool masked);
+// Whether that configuration has the primary-first loop (TraceArgs::primary_on may be set for it).
+bool trace_primary_first(int precision, bool masked);
+// The megakernel's LDS after the scene tables (lds_bytes): per wave, the lanes' home block — unit fields and
+// f64 chunk sum, kHomeLdsBytesPerWave — and, with the primary-first loop, the mask of the lane's unit batch:
+// which clustered slots its tile's camera rays may hit (two words per lane, bit order of SceneView::cvalid),
+// then the wave's current batch's (a copy per lane), kPrimaryLdsBytesPerWave.  (8: alignment of the home block)
 constexpr size_t kHomeLdsBytesPerWave = 2560;
-// + (kVarPathLds) the lane's path attenuation T (3 x 8 B) and RNG state (8 B) after it
-constexpr int kVarPathLdsBit = 33554432;
-constexpr size_t kPathLdsBytesPerWave = 4 * 64 * 8;
-// + (kVarUnitBase) the unit's RNG base and f64 pixel column / reference row
-constexpr int kVarUnitBaseBit = 67108864;
-constexpr size_t kUnitBaseLdsBytesPerWave = 3 * 64 * 8;
-// + (kVarPrimaryFirst) the mask of the lane's unit batch: which clustered slots its tile's camera rays may
-// hit (two words per lane, bit order of SceneView::cvalid), then the wave's current batch's (a copy per lane);
-// right after the kHomeLdsBytesPerWave block
-constexpr int kVarPrimaryFirstBit = 4194304;
 constexpr size_t kPrimaryLdsBytesPerWave = 4 * 64 * 4;
-#ifndef RTW_DEFAULT_VAR_F32  // (A/B builds override it)
-#define RTW_DEFAULT_VAR_F32 (8 + 512 + 131072 + 262144 + 524288 + 16777216)  // 17695240
-#endif
-constexpr int kDefaultVarF32 = RTW_DEFAULT_VAR_F32;
-// rtw_device.hpp kVarMasked: the take reads TraceArgs::tile_list / tile_mask (a masked accumulator pass).
-// Built for the default variant of each precision, product mode only; launched only with both pointers set.
-constexpr int kVarMaskedBit = 268435456;
-// The masked instantiation of each precision.  f32 is built for 4 waves per SIMD (VAR bit 2, 128 VGPRs) where
-// the unmasked kernel has 5 (bit 3, 96): at 96 the map's two loads spilled (32 B of scratch against the unmasked
-// kernel's 16; decoding per batch, kVarBatchDecode, spilled 64).
-// (f64: without kVarPrimaryFirst and its kVarLaneDisk, 134217728 — the masked pass keeps the round-6 loop)
-constexpr int kMaskedVarF64 = (kDefaultVarF64 & ~(kVarPrimaryFirstBit | 134217728)) | kVarMaskedBit;
-constexpr int kMaskedVarF32 = ((kDefaultVarF32 & ~8) | 4) | kVarMaskedBit;
-bool trace_variant_built(int precision, int var);
+size_t trace_home_lds_bytes(int precision, bool masked);
 constexpr int kTraceBlock = 256;
 
 // ---------------------------------------------------------- accumulator --

@@ -180,7 +180,7 @@ int pack_scene(const rtw_sphere* spheres, uint32_t n, const rtw_material* mats, 
   const float cmax = std::nextafter((float)(cmax_c + cmax_d), INFINITY);
   const float rho = std::nextafter((float)rho_max, INFINITY);
   const uint32_t cull_on = (nn > 0 && cmax <= rtwc::kCmaxLimit) ? 1u : 0u;
-  // Clustered pretest tables (SceneView ccull..., trace VAR kVarCluster).
+  // Clustered pretest tables (SceneView ccull...; rtw_device.hpp closest_hit, f64).
   // kd-split of the narrow spheres (by the centre of their swept box over
   // the shutter) into clusters of <= 8; members static first, so pairs are
   // static-static where possible.  Bounding sphere of cluster c: centre

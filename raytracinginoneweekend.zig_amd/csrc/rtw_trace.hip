@@ -13,10 +13,10 @@
 //  * Per lane, one loop iteration = [take a unit] -> [start a sample: the
 //    sample's counter-RNG block, camera ray] -> [one bounce segment].  Paths
 //    of different length share the wave without padding to the longest.  The
-//    default variant rotates the iteration so that the lens-disk points of the
-//    new samples and the unit-ball points of the hits come from ONE
-//    cooperative rejection pass (kVarMergedStart, below).  The f64 default
-//    goes one step further (kVarPrimaryFirst, the primary-first loop below):
+//    loop rotates the iteration so that the lens-disk points of the new
+//    samples and the unit-ball points of the hits come from ONE cooperative
+//    rejection pass (the rotated loop below).  The f64 kernel of a full frame
+//    goes one step further (TraceCfg::kPrimaryFirst, the primary-first loop):
 //    a lane that starts a sample resolves its camera ray itself — the wide
 //    spheres, then the exact tests of the few spheres in the mask of its
 //    tile (rtw_beam.hpp, made once per 64-unit batch in take_units) — and
@@ -47,29 +47,39 @@
 // lane ops, 2 -> 1 scratch pairs; -1.4 % per configs[1] frame
 // (profiles/r04/trace_lane_flags_ab.txt).
 
-#ifndef RTW_PRIMARY_ROUND2  // (the primary-first loop's second primary round: lane threshold, 0 = none)
-#define RTW_PRIMARY_ROUND2 0
-#endif
-
 namespace rtwk {
 
-// VAR (tuning variants, selected at launch): bit0 = sphere records from LDS
-// instead of scalar loads; bit1 = unroll the sphere loop by 2; bit2 = ask for
-// 4 waves per SIMD (VGPR budget 128); bit3 = 5 waves per SIMD (budget 96);
-// bit4 = per-lane rejection loops instead of coop_reject; bit5 = coop_reject
-// for the lens disk too; bit6 = no narrow-sphere pretest (every lane tests
-// every sphere exactly); bit9 (512) = scene fields re-read from the kernel
-// argument; bit10 (1024) = the loop's other argument fields too; bits 11-14 =
-// phase-duplication measurement builds (RTW_MEASURE); rtw_device.hpp: 32768
-// kVarFastSqrt, 65536 kVarYOnly, 131072 kVarR0Table, 262144 kVarMergedStart,
-// 524288 kVarPreDraw, 1048576 kVarBatchDecode, 4194304 kVarPrimaryFirst,
-// 134217728 kVarLaneDisk.  Defaults: rtw_capi.hip kernel_variant; A/B tables:
-// profiles/r01/ab_*.txt, profiles/r11/README.md.
-template <typename R, bool F32, int MODE, int VAR>
-__global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 1)) trace_kernel(TraceArgs<R> A) {
+// The kernel's configurations: one per precision and kind of launch (MASKED: a masked accumulator pass,
+// DESIGN.md §13; else a frame or an unmasked pass).  Each line names the measurement that decided it; the
+// arms that lost are DESIGN.md §6's table of retired variants.  In every configuration:
+//  - the closest hit reads the scene fields from the kernel argument (SGPR budget; +0.8 % f64, +1.0 % f32,
+//    profiles/r01/ab_defaults.txt);
+//  - the rotated loop (+5.3 % f64, +4.1 % f32) with the sample's time draw and the dielectric's draw made in
+//    its cooperative pass (+1.2 % f64; both profiles/r01/ab_defaults.txt);
+//  - Schlick's r0^2 from the material table and, in f64, the fast exact sqrt (+0.4 % f64 together,
+//    profiles/r01/ab_defaults.txt) and the clustered pretest (+5.4 %, profiles/r02/cluster_ab.txt);
+//  - the lane's unit fields and f64 chunk sum in the wave's LDS home block (+0.6 % f64, +1.3 % f32,
+//    profiles/r03/home_lds_ab.txt, home_lds_f32_ab.txt).
+template <bool F32, bool MASKED>
+struct TraceCfg {
+  // Waves per SIMD the register allocator is asked for: 4 (128 VGPRs) in f64, 5 (96) in f32
+  // (profiles/r01/ab_defaults.txt); the masked f32 pass 4, since at 96 the map's two loads spilled 32 B of
+  // scratch against the unmasked kernel's 16.
+  static constexpr int kWavesPerSimd = (F32 && !MASKED) ? 5 : 4;
+  // The loop's argument fields re-read from the kernel argument where used, not held in SGPRs for the whole
+  // kernel: f64 only (+0.6 %, profiles/r02/var1024_ab.txt).
+  static constexpr bool kLoopArgsFromKernarg = !F32;
+  // The primary-first loop, its new samples' lens-disk points from each lane's own rejection loop: f64 frames
+  // (profiles/r11/README.md, bench_ab.txt); a masked pass keeps the rotated loop with the cooperative disk.
+  static constexpr bool kPrimaryFirst = !F32 && !MASKED;
+  // Bytes per wave after the scene tables (rtw_internal.hpp): the home block, then the primary masks.
+  static constexpr size_t kHomeStride = kHomeLdsBytesPerWave + (kPrimaryFirst ? kPrimaryLdsBytesPerWave : 0);
+};
+
+template <typename R, bool F32, int MODE, bool MASKED>
+__global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPerSimd)) trace_kernel(TraceArgs<R> A) {
+  using Cfg = TraceCfg<F32, MASKED>;
   constexpr bool STATS = MODE == 1;
-  constexpr bool COOP = !(VAR & 16);               // unit-ball point (scatter)
-  constexpr bool COOP_DISK = COOP && (VAR & 32);  // lens-disk point (camera ray)
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const SceneView<R> S = A.sc;
   // LDS: per-wave coop_reject slots, then copies of the per-lane lookup
@@ -78,51 +88,30 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
   CoopSlots* slots = T.slots;
 
   const uint32_t lid = lane_id();
-  // VAR kVarHomeLds: the lane's unit fields (pixel, chunk, sample end) and its
-  // f64 chunk sum live in this wave's LDS home block (SoA, one entry per
-  // lane) instead of 10 VGPRs held across the closest hit; they are touched
-  // only when a unit starts or ends, a sample starts, or a path misses.
-  constexpr bool HOME = (VAR & kVarHomeLds) != 0;
+  // The lane's unit fields (pixel, chunk, sample end) and its f64 chunk sum
+  // live in this wave's LDS home block (SoA, one entry per lane) instead of
+  // 10 VGPRs held across the closest hit; they are touched only when a unit
+  // starts or ends, a sample starts, or a path misses.
+  // (Declared, then set: with the pointers initialised in place the counts kernel of f32 is allocated
+  // otherwise, 5 instructions apart; profiles/r12/isa_identity.txt.)
   double* h_sum = nullptr;    // [3][64]
   uint32_t* h_u32 = nullptr;  // px[64], ly[64], c[64], s_end[64]
-  R* h_t = nullptr;           // kVarPathLds: T [3][64] (8-B slots)
-  uint64_t* h_base = nullptr; // kVarUnitBase: the unit's RNG block base [64]
-  R* h_pxj = nullptr;         // kVarUnitBase: its f64 pixel column and reference row [2][64] (8-B slots)
-  uint64_t* h_rs = nullptr;   // kVarPathLds: RNG state [64]
-  if constexpr (HOME) {
+  {
     const size_t off = (size_t)(reinterpret_cast<unsigned char*>(T.cpos + kClusterSlots * S.n_clusters) - lds_raw);
-    constexpr size_t kPathB = (VAR & kVarPathLds) ? kPathLdsBytesPerWave : 0;
-    constexpr size_t kPrimB = (VAR & kVarPrimaryFirst) ? kPrimaryLdsBytesPerWave : 0;
-    constexpr size_t kHomeStride =
-        kHomeLdsBytesPerWave + kPathB + ((VAR & kVarUnitBase) ? kUnitBaseLdsBytesPerWave : 0) + kPrimB;
-    unsigned char* hb = lds_raw + ((off + 7) & ~(size_t)7) + (threadIdx.x >> 6) * kHomeStride;
+    unsigned char* hb = lds_raw + ((off + 7) & ~(size_t)7) + (threadIdx.x >> 6) * Cfg::kHomeStride;
     h_sum = reinterpret_cast<double*>(hb);
     h_u32 = reinterpret_cast<uint32_t*>(hb + 3 * 64 * 8);
-    // (the masks are h_u32[256 ...]: right after it, the same address register with other offsets)
-    constexpr size_t kHome0 = kHomeLdsBytesPerWave + kPrimB;
-    h_t = reinterpret_cast<R*>(hb + kHome0);
-    h_rs = reinterpret_cast<uint64_t*>(hb + kHome0 + 3 * 64 * 8);
-    h_base = reinterpret_cast<uint64_t*>(hb + kHome0 + kPathB);
-    h_pxj = reinterpret_cast<R*>(hb + kHome0 + kPathB + 64 * 8);
+    // (the primary masks are h_u32[256 ...]: right after it, the same address register with other offsets)
   }
-  constexpr bool UBASE = HOME && (VAR & kVarUnitBase) != 0;
-  constexpr bool PLDS = HOME && (VAR & kVarPathLds) != 0 && (VAR & kVarMergedStart) != 0;
-  constexpr uint32_t TS = 8 / sizeof(R);  // (8-B slots: T component k of lane l at h_t[(k * 64 + l) * TS])
-  auto t_load = [&]() -> V3<R> { return mk(h_t[lid * TS], h_t[(64 + lid) * TS], h_t[(128 + lid) * TS]); };
-  auto t_store = [&](const V3<R>& v) {
-    h_t[lid * TS] = v.x, h_t[(64 + lid) * TS] = v.y, h_t[(128 + lid) * TS] = v.z;
-  };
-  // VAR bit 10: the loop's kernel-argument fields are re-read where used
-  // (scalar loads through a laundered kernarg pointer) instead of living in
-  // SGPRs for the whole kernel: the SGPR budget is the limit (spills become
-  // v_readlane/v_writelane VALU instructions).
-#define RTW_KA(f) ((VAR & 1024) ? opaque(kargs<R>())->f : A.f)
-  const R tmin = A.tmin;
+  // Cfg::kLoopArgsFromKernarg: the loop's kernel-argument fields are re-read
+  // where used (scalar loads through a laundered kernarg pointer) instead of
+  // living in SGPRs for the whole kernel: the SGPR budget is the limit (spills
+  // become v_readlane/v_writelane VALU instructions).
+#define RTW_KA(f) (Cfg::kLoopArgsFromKernarg ? opaque(kargs<R>())->f : A.f)
   const R kInf = (R)__builtin_huge_val();
 
   Lane<R> L;
-  L.px = L.ly = L.c = L.s = L.s_end = L.depth = 0;
-  L.sx = L.sy = L.sz = 0.0;
+  L.px = L.ly = L.s = L.depth = 0;
   L.rs = 0;
   L.skip = -1;
   uint32_t lane_flags = 0u;  // (rtw_device.hpp LaneFlag)
@@ -133,40 +122,28 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
   KStats st;
   if constexpr (MODE == 2) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st.t_last)::"memory");
 
-  // (tile x, tile y, chunk) of the wave's current unit batch and of a newly
-  // fetched one (VAR kVarBatchDecode; wave-uniform).
-  uint32_t cur_tx = 0, cur_ty = 0, cur_c = 0, nb_tx = 0, nb_ty = 0, nb_c = 0;
-  // VAR kVarMasked: a masked accumulator pass.  The dealt tile index counts the
-  // active tiles only, tile_list gives the frame's tile, and a unit whose
-  // pixel's bit of the tile's mask is clear is skipped as a padding unit is.
-  // The two instantiations that are built (kMaskedVarF64 / kMaskedVarF32) take
-  // the per-lane decode below.  The kVarBatchDecode form of the map
-  // (decode_batch, cur_mask / nb_mask) is written out for an A/B build that
-  // combines the two bits; no library builds it and no test runs it (an f32
-  // build of it spilled 64 B of scratch: rtw_internal.hpp).
-  constexpr bool MASKED = (VAR & kVarMasked) != 0;
-  uint64_t cur_mask = 0, nb_mask = 0;  // (kVarBatchDecode: the batch's tile mask, wave-uniform)
-  // VAR kVarPrimaryFirst: the sphere mask of a unit batch's tile (wave-uniform; bit order of
+  // MASKED: the dealt tile index counts the active tiles only, tile_list gives
+  // the frame's tile, and a unit whose pixel's bit of the tile's mask is clear
+  // is skipped as a padding unit is.
+  // Cfg::kPrimaryFirst: the sphere mask of a unit batch's tile (wave-uniform; bit order of
   // SceneView::cvalid), in LDS, not in registers held across the loop: h_u32[kPm + 64 h + lid] = word h
   // of the mask of the lane's own batch, h_u32[kBm + 64 h + lid] = of the wave's current batch (a copy
   // per lane: every LDS address of the take is the lane's h_u32 address plus a constant).
   constexpr uint32_t kPm = 4 * 64, kBm = 6 * 64;
   uint32_t* const h_me = h_u32 + lid;
-  constexpr bool PF = (VAR & kVarPrimaryFirst) != 0;
-  static_assert(!PF || (HOME && !F32 && (VAR & kVarMergedStart) && (VAR & kVarCluster) &&
-                        !(VAR & (kVarPathLds | kVarMasked))),
-                "kVarPrimaryFirst: the f64 rotated loop with clusters and the home block");
-  auto decode_batch = [&](uint32_t base, uint32_t& tx, uint32_t& ty, uint32_t& c, uint64_t& tmask) {
+  constexpr bool PF = Cfg::kPrimaryFirst;
+  // Cfg::kPrimaryFirst: (tile x, tile y, chunk) of a newly fetched unit batch (wave-uniform).  A batch is 64
+  // aligned units = one (tile, chunk): decoded once, for the tile's beam.
+  // (nb_pad is never written.  The kernels were measured with a 64-bit word in this place; without it the
+  // compiler numbers three VGPRs of the f64 kernels otherwise — the same instructions — and the library
+  // would not be the one profiles/r11 measured: profiles/r12/isa_identity.txt.)
+  uint32_t nb_tx = 0, nb_ty = 0, nb_c = 0;
+  uint64_t nb_pad = 0;
+  auto decode_batch = [&](uint32_t base, uint32_t& tx, uint32_t& ty, uint32_t& c, uint64_t& pad) {
     const uint32_t b64 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 6));
     const uint32_t nc = RTW_KA(n_chunks), txs = RTW_KA(tiles_x);
-    uint32_t tile = b64 / nc;
+    const uint32_t tile = b64 / nc;
     c = b64 - tile * nc;
-    if constexpr (MASKED) {  // (a batch past the queue's end names no tile: its units are refused below)
-      const bool in_q = (b64 << 6) < RTW_KA(total_units);
-      const auto* ka = opaque(kargs<R>());
-      tile = in_q ? ka->tile_list[tile] : 0u;
-      tmask = in_q ? ka->tile_mask[tile] : 0ull;
-    }
     ty = tile / txs;
     tx = tile - ty * txs;
   };
@@ -187,14 +164,10 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
         else
           base2 = __shfl(b, 0);
       }
-      if constexpr ((VAR & kVarBatchDecode) != 0 || PF) {
-        // A batch is 64 aligned units = one (tile, chunk): decoded once per
-        // batch (wave-uniform) instead of two integer divisions per refill.
-        if (n > rem)  // (a dealt batch is a 64-aligned batch in every order)
-          decode_batch(dealt_unit(base2, *opaque(kargs<R>())) & ~63u, nb_tx, nb_ty, nb_c, nb_mask);
-      }
       uint32_t nb_bm0 = 0u, nb_bm1 = 0u;
       if constexpr (PF) {
+        if (n > rem)  // (a dealt batch is a 64-aligned batch in every order)
+          decode_batch(dealt_unit(base2, *opaque(kargs<R>())) & ~63u, nb_tx, nb_ty, nb_c, nb_pad);
         // The new batch's mask: which clustered slots can a camera ray of its
         // tile hit (rtw_beam.hpp)?  Lane j answers for slot j; every lane of
         // the wave is here (wave-uniform branch at the loop's top).  A batch
@@ -238,65 +211,40 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
         if (unit >= RTW_KA(total_units)) {
           done = true;
         } else {
-          uint32_t tx, ty, c;
           const uint32_t du = dealt_unit(unit, *opaque(kargs<R>()));
           const uint32_t l = du & 63u;
-          bool active = true;  // (kVarMasked)
-          if constexpr ((VAR & kVarBatchDecode) != 0) {
-            const bool in_cur = rank < rem;
-            tx = in_cur ? cur_tx : nb_tx;
-            ty = in_cur ? cur_ty : nb_ty;
-            c = in_cur ? cur_c : nb_c;
-            if constexpr (MASKED) active = (((in_cur ? cur_mask : nb_mask) >> l) & 1ull) != 0;
-          } else {
-            const uint32_t units_per_tile = kTileW * kTileH * RTW_KA(n_chunks);
-            uint32_t tile = rtwm::udiv(du, RTW_KA(upt_m), RTW_KA(upt_sh));  // du / units_per_tile
-            const uint32_t r = du - tile * units_per_tile;
-            c = r >> 6;
-            if constexpr (MASKED) {  // (unit < total_units: tile < the list's length)
-              // Both pointers are read from the kernel argument here, whatever VAR bit 1024 says: held in
-              // SGPRs for the whole kernel they cost the f32 variant spills.  The frame has < 2^24 tiles
-              // (validate: <= 2^24 pixels), so the masked indices let the loads take a 32-bit offset.
-              const auto* ka = opaque(kargs<R>());
-              tile = ka->tile_list[tile & 0xFFFFFFu] & 0xFFFFFFu;
-              // (the 32-bit half of the mask that holds bit l: one register less than the u64)
-              const uint32_t half = reinterpret_cast<const uint32_t*>(ka->tile_mask)[2u * tile + (l >> 5)];
-              active = ((half >> (l & 31u)) & 1u) != 0;
-            }
-            ty = rtwm::udiv(tile, RTW_KA(tx_m), RTW_KA(tx_sh));  // tile / tiles_x
-            tx = tile - ty * RTW_KA(tiles_x);
+          bool active = true;  // (MASKED)
+          const uint32_t units_per_tile = kTileW * kTileH * RTW_KA(n_chunks);
+          uint32_t tile = rtwm::udiv(du, RTW_KA(upt_m), RTW_KA(upt_sh));  // du / units_per_tile
+          const uint32_t r = du - tile * units_per_tile;
+          const uint32_t c = r >> 6;
+          if constexpr (MASKED) {  // (unit < total_units: tile < the list's length)
+            // Both pointers are read from the kernel argument here, in f32 too: held in SGPRs for the
+            // whole kernel they cost the f32 kernel spills.  The frame has < 2^24 tiles (validate: <= 2^24
+            // pixels), so the masked indices let the loads take a 32-bit offset.
+            const auto* ka = opaque(kargs<R>());
+            tile = ka->tile_list[tile & 0xFFFFFFu] & 0xFFFFFFu;
+            // (the 32-bit half of the mask that holds bit l: one register less than the u64)
+            const uint32_t half = reinterpret_cast<const uint32_t*>(ka->tile_mask)[2u * tile + (l >> 5)];
+            active = ((half >> (l & 31u)) & 1u) != 0;
           }
+          const uint32_t ty = rtwm::udiv(tile, RTW_KA(tx_m), RTW_KA(tx_sh));  // tile / tiles_x
+          const uint32_t tx = tile - ty * RTW_KA(tiles_x);
           const uint32_t px = tx * kTileW + (l & 7u);
           const uint32_t ly = ty * kTileH + (l >> 3);
           if (px < RTW_KA(W) && ly < RTW_KA(row_count) && active) {  // else: padding or inactive unit, take another
             have_unit = true;
             L.s = c * RTW_KA(chunk);
-            if constexpr (HOME) {
-              double z = 0.0;  // (laundered: a hoisted constant would hold registers)
-              asm volatile("" : "+v"(z));
-              h_u32[lid] = px;
-              h_u32[64 + lid] = ly;
-              h_u32[128 + lid] = c;
-              h_u32[192 + lid] = min(L.s + RTW_KA(chunk), RTW_KA(spp));
-              h_sum[lid] = h_sum[64 + lid] = h_sum[128 + lid] = z;
-              if constexpr (PF) {  // the mask of the lane's own batch, current or new
-                h_me[kPm] = rank < rem ? h_me[kBm] : nb_bm0;
-                h_me[kPm + 64] = rank < rem ? h_me[kBm + 64] : nb_bm1;
-              }
-              if constexpr (UBASE) {  // start_sample_uv's per-pixel part, once per unit
-                const uint32_t y = RTW_KA(row_begin) + ly * RTW_KA(row_stride);
-                const uint64_t pixel = (uint64_t)y * RTW_KA(W) + px;
-                h_base[lid] = RTW_KA(seed_base) + (pixel << 40) * kGamma;
-                constexpr uint32_t TS = 8 / sizeof(R);
-                h_pxj[lid * TS] = (R)px;
-                h_pxj[(64 + lid) * TS] = (R)(RTW_KA(H) - 1 - y);
-              }
-            } else {
-              L.px = px;
-              L.ly = ly;
-              L.c = c;
-              L.s_end = min(L.s + RTW_KA(chunk), RTW_KA(spp));
-              L.sx = L.sy = L.sz = 0.0;
+            double z = 0.0;  // (laundered: a hoisted constant would hold registers)
+            asm volatile("" : "+v"(z));
+            h_u32[lid] = px;
+            h_u32[64 + lid] = ly;
+            h_u32[128 + lid] = c;
+            h_u32[192 + lid] = min(L.s + RTW_KA(chunk), RTW_KA(spp));
+            h_sum[lid] = h_sum[64 + lid] = h_sum[128 + lid] = z;
+            if constexpr (PF) {  // the mask of the lane's own batch, current or new
+              h_me[kPm] = rank < rem ? h_me[kBm] : nb_bm0;
+              h_me[kPm + 64] = rank < rem ? h_me[kBm + 64] : nb_bm1;
             }
           }
         }
@@ -304,7 +252,6 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
       if (n > rem) {
         qnext = base2 + (n - rem);
         qend = base2 + kBatch;
-        if constexpr ((VAR & kVarBatchDecode) != 0) cur_tx = nb_tx, cur_ty = nb_ty, cur_c = nb_c, cur_mask = nb_mask;
         if constexpr (PF) {  // after the takes above read the old one
           h_me[kBm] = nb_bm0, h_me[kBm + 64] = nb_bm1;
         }
@@ -320,22 +267,13 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
     L.s++;
     have_ray = false;
     if (STATS) st.samples++;
-    if constexpr (HOME) {
-      if (L.s == h_u32[192 + lid]) {
-        const uint32_t npix = RTW_KA(row_count) * RTW_KA(W);
-        double* dst = RTW_KA(partial) +
-                      ((size_t)h_u32[128 + lid] * npix + (size_t)h_u32[64 + lid] * RTW_KA(W) + h_u32[lid]) * 3;
-        dst[0] = h_sum[lid];
-        dst[1] = h_sum[64 + lid];
-        dst[2] = h_sum[128 + lid];
-        have_unit = false;
-      }
-    } else if (L.s == L.s_end) {
+    if (L.s == h_u32[192 + lid]) {
       const uint32_t npix = RTW_KA(row_count) * RTW_KA(W);
-      double* dst = RTW_KA(partial) + ((size_t)L.c * npix + (size_t)L.ly * RTW_KA(W) + L.px) * 3;
-      dst[0] = L.sx;
-      dst[1] = L.sy;
-      dst[2] = L.sz;
+      double* dst = RTW_KA(partial) +
+                    ((size_t)h_u32[128 + lid] * npix + (size_t)h_u32[64 + lid] * RTW_KA(W) + h_u32[lid]) * 3;
+      dst[0] = h_sum[lid];
+      dst[1] = h_sum[64 + lid];
+      dst[2] = h_sum[128 + lid];
       have_unit = false;
     }
   };
@@ -344,7 +282,7 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
   // to be shaded.  (A result code, not two bool& outputs: the optimiser merged
   // their stores through a selected pointer, which put both flags in scratch
   // memory — a store + load per iteration on the critical path.)
-  // prim (kVarPrimaryFirst): the lane's camera ray, from the mask of its tile
+  // prim (the primary-first loop): the lane's camera ray, from the mask of its tile
   // (closest_hit's PRIMARY form) instead of the wave's pretest.
   auto bounce = [&](uint32_t& kind, int& hit, R& tmax, auto prim) -> int {
     constexpr bool PRIM = decltype(prim)::value;
@@ -357,24 +295,14 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
     }
     uint32_t pm0 = 0u, pm1 = 0u;
     if constexpr (PRIM) pm0 = h_me[kPm], pm1 = h_me[kPm + 64];
-    if constexpr (VAR & 512)  // scene fields re-read from the kernel argument (SGPR budget)
-      closest_hit<R, F32, MODE, VAR, PRIM>(opaque(kargs<R>())->sc, T, L, RTW_KA(tmin), RTW_KA(pre_k), lid, st, hit,
-                                           tmax, pm0, pm1);
-    else
-      closest_hit<R, F32, MODE, VAR, PRIM>(S, T, L, tmin, A.pre_k, lid, st, hit, tmax, pm0, pm1);
+    // (scene fields re-read from the kernel argument: SGPR budget)
+    closest_hit<R, F32, MODE, PRIM>(opaque(kargs<R>())->sc, T, L, RTW_KA(tmin), RTW_KA(pre_k), lid, st, hit, tmax,
+                                    pm0, pm1);
     if (hit < 0) {  // miss: background (main.zig:109-112)
-      V3<R> tt = L.T;
-      if constexpr (PLDS) tt = t_load();
-      const V3<R> col = mulv(tt, ld3(opaque(kargs<R>())->bg));
-      if constexpr (HOME) {
-        h_sum[lid] += (double)col.x;
-        h_sum[64 + lid] += (double)col.y;
-        h_sum[128 + lid] += (double)col.z;
-      } else {
-        L.sx += (double)col.x;
-        L.sy += (double)col.y;
-        L.sz += (double)col.z;
-      }
+      const V3<R> col = mulv(L.T, ld3(opaque(kargs<R>())->bg));
+      h_sum[lid] += (double)col.x;
+      h_sum[64 + lid] += (double)col.y;
+      h_sum[128 + lid] += (double)col.z;
       return 1;
     }
     kind = T.kind[(T.meta[hit] >> 8) & 0xFFFu];
@@ -384,7 +312,7 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
   bool primary_ran = false;
   if constexpr (PF) {
     if (A.primary_on) {
-      // Primary-first loop (kVarPrimaryFirst; TraceArgs::primary_on): [take
+      // Primary-first loop (Cfg::kPrimaryFirst; TraceArgs::primary_on): [take
       // units] -> [new samples, per lane: u, v, the lens-disk point from the
       // lane's own loop, the camera ray and ITS closest hit — the wide spheres,
       // then the exact tests of the spheres in the mask of the lane's tile; a
@@ -409,59 +337,34 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
         }
         RTW_STAMP(0)
         // (at the loop's top a lane has a ray exactly when it is shading)
-        // kVarLaneDisk (the default): the lens-disk point from the lane's own loop; without it, from a
-        // disk-only cooperative pass before the camera rays (0.6 % slower, profiles/r11/README.md).
-        constexpr bool LDISK = (VAR & kVarLaneDisk) != 0;
-        for (uint32_t round = 0;; ++round) {
-          const bool ns = have_unit && !have_ray;
+        // (the lens-disk point from the lane's own loop: 0.6 % faster than a disk-only cooperative pass
+        // before the camera rays, profiles/r11/README.md)
+        if (have_unit && !have_ray) {
           R u = (R)0, v = (R)0, dk[2] = {(R)0, (R)0};
-          auto uv = [&]() {
-            if constexpr (UBASE) {
-              start_sample_uv_base<R>(kargs<R>(), L, h_base[lid], h_pxj[lid * TS], h_pxj[(64 + lid) * TS], u, v);
-            } else {
-              L.px = h_u32[lid];
-              L.ly = h_u32[64 + lid];
-              start_sample_uv<R>(kargs<R>(), L, u, v);
-            }
-          };
-          if constexpr (!LDISK) {
-            if (__any(ns)) {  // wave-uniform: coop_reject runs converged
-              if (ns) uv();
-              coop_reject<R, 2, true>(ns, L.rs, dk, slots, lid);
-            }
+          L.px = h_u32[lid];
+          L.ly = h_u32[64 + lid];
+          start_sample_uv<R>(kargs<R>(), L, u, v);
+          for (;;) {  // randomPointInUnitDisk (rand.zig:30-36)
+            dk[0] = rrange_m11<R>(L.rs);
+            dk[1] = rrange_m11<R>(L.rs);
+            if (in_unit_ball<R, 2>(dk)) break;
           }
-          if (ns) {
-            if constexpr (LDISK) {
-              uv();
-              for (;;) {  // randomPointInUnitDisk (rand.zig:30-36)
-                dk[0] = rrange_m11<R>(L.rs);
-                dk[1] = rrange_m11<R>(L.rs);
-                if (in_unit_ball<R, 2>(dk)) break;
-              }
-            }
-            start_sample_ray<R>(kargs<R>(), L, u, v, dk[0], dk[1]);
-            have_ray = true;
-            if (bounce(kind, hit, tmax, std::true_type{}) == 1) {  // miss or depth limit
-              finish_sample();
-              if (STATS) st.prim_idle++;
-            } else {
-              shading = true;
-            }
+          start_sample_ray<R>(kargs<R>(), L, u, v, dk[0], dk[1]);
+          have_ray = true;
+          if (bounce(kind, hit, tmax, std::true_type{}) == 1) {  // miss or depth limit
+            finish_sample();
+            if (STATS) st.prim_idle++;
+          } else {
+            shading = true;
           }
-          // RTW_PRIMARY_ROUND2 = n > 0 (A/B builds): a second primary round when at least n lanes ended
-          // their sample above and still hold a unit (n = 8, 16: +0.2-0.3 %, within the run-to-run spread;
-          // profiles/r11/README.md).
-          if (RTW_PRIMARY_ROUND2 == 0 || round == 1u) break;
-          if (popc64(wballot(have_unit && !have_ray)) < (uint32_t)RTW_PRIMARY_ROUND2) break;
         }
         RTW_STAMP(9)
-        constexpr bool PRE = (VAR & kVarPreDraw) != 0;
-        const uint32_t dim = shading ? (kind <= 2u ? 3u : (PRE ? 1u : 0u)) : 0u;
+        const uint32_t dim = shading ? (kind <= 2u ? 3u : 1u) : 0u;  // (as in the rotated loop below)
         R pt[3] = {(R)0, (R)0, (R)0}, raw = (R)0;
         if (__any(dim != 0u)) coop_reject_mixed<R>(dim, L.rs, pt, raw, slots, lid);
         RTW_STAMP(7)
         if (shading) {
-          if (scatter_hit<R, F32, VAR, PRE>(T, L, hit, tmax, kind, pt, raw)) finish_sample();  // absorbed
+          if (scatter_hit<R, F32, true>(T, L, hit, tmax, kind, pt, raw)) finish_sample();  // absorbed
         }
         RTW_STAMP(8)
         shading = false;
@@ -478,14 +381,15 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
       }
     }
   }
-  if (primary_ran) {
-  } else if constexpr ((VAR & kVarMergedStart) != 0) {
+  if (!primary_ran) {
     // Rotated loop: [take units] -> [u, v of new samples] -> ONE coop pass:
     // lens-disk points (new samples) + unit-ball points (the Lambertian /
     // Metal hits of the previous step) -> [scatter; camera rays] -> [closest
     // hit].  A lane whose path missed starts its next sample in the next
-    // iteration before that iteration's closest hit, as in the default loop;
-    // each sample's draws are in the reference's order.
+    // iteration before that iteration's closest hit, as in the textbook order;
+    // each sample's draws are in the reference's order.  The sample's time draw
+    // and the dielectric's draw are made inside the same cooperative pass
+    // (coop_reject_mixed `raw`).
     LaneFlag<8u> shading{lane_flags};
     uint32_t kind = 0;
     int hit = -1;
@@ -499,30 +403,24 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
       }
       RTW_STAMP(0)
       const bool ns = have_unit && !have_ray;
-      if constexpr (PLDS) L.rs = h_rs[lid];
       R u = (R)0, v = (R)0;
       if (ns) {
-        if constexpr (UBASE) {
-          start_sample_uv_base<R>(kargs<R>(), L, h_base[lid], h_pxj[lid * TS], h_pxj[(64 + lid) * TS], u, v);
-        } else {
-          if constexpr (HOME) {
-            L.px = h_u32[lid];
-            L.ly = h_u32[64 + lid];
-          }
-          start_sample_uv<R>(kargs<R>(), L, u, v);
-        }
+        L.px = h_u32[lid];
+        L.ly = h_u32[64 + lid];
+        start_sample_uv<R>(kargs<R>(), L, u, v);
       }
       RTW_STAMP(1)
       // dim: 3 unit ball (Lambertian, Metal), 1 the dielectric's draw, 2 lens disk (+ time)
-      constexpr bool PRE = (VAR & kVarPreDraw) != 0;
-      constexpr bool LDISK = (VAR & kVarLaneDisk) != 0;  // new samples' disk points from each lane's own loop
-      const uint32_t dim = shading ? (kind <= 2u ? 3u : (PRE ? 1u : 0u)) : (ns && !LDISK ? 2u : 0u);
+      // LDISK: the primary-first kernel running this loop (primary_on clear) keeps its new samples' disk
+      // points in each lane's own loop, as that kernel was measured (in this loop alone 4.8 % slower than
+      // the cooperative disk: profiles/r06/mk_var_ab.txt).
+      constexpr bool LDISK = PF;
+      const uint32_t dim = shading ? (kind <= 2u ? 3u : 1u) : (ns && !LDISK ? 2u : 0u);
       R pt[3] = {(R)0, (R)0, (R)0}, raw = (R)0;
       if (__any(dim != 0u)) coop_reject_mixed<R>(dim, L.rs, pt, raw, slots, lid);
       RTW_STAMP(7)
       if (shading) {
-        if constexpr (PLDS) L.T = t_load();
-        if (scatter_hit<R, F32, VAR, PRE>(T, L, hit, tmax, kind, pt, raw)) finish_sample();  // absorbed
+        if (scatter_hit<R, F32, true>(T, L, hit, tmax, kind, pt, raw)) finish_sample();  // absorbed
       }
       if (ns) {
         if constexpr (LDISK) {
@@ -534,13 +432,9 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
           }
           start_sample_ray<R>(kargs<R>(), L, u, v, dk[0], dk[1]);
         } else {
-          start_sample_ray<R, PRE>(kargs<R>(), L, u, v, pt[0], pt[1], raw);
+          start_sample_ray<R, true>(kargs<R>(), L, u, v, pt[0], pt[1], raw);
         }
         have_ray = true;
-      }
-      if constexpr (PLDS) {
-        if (shading || ns) t_store(L.T);
-        h_rs[lid] = L.rs;
       }
       RTW_STAMP(8)
       shading = false;
@@ -555,95 +449,7 @@ __global__ void __launch_bounds__(kTraceBlock, (VAR & 8) ? 5 : ((VAR & 4) ? 4 : 
       RTW_STAMP(3)
       if (ended) finish_sample();
     }
-  } else {
-  for (;;) {
-    RTW_STAMP(5)
-    take_units();
-    if (!__any(have_unit)) {
-      if (__all(done)) break;
-      continue;
-    }
-    RTW_STAMP(0)
-
-    // ---- 2. new samples: per-sample RNG block + camera ray ----
-    {
-      const bool ns = have_unit && !have_ray;
-      if constexpr (COOP_DISK) {
-        if (__any(ns)) {  // wave-uniform: coop_reject runs converged
-          R u = (R)0, v = (R)0, dk[2];
-          if (ns) start_sample_uv<R>(kargs<R>(), L, u, v);
-          coop_reject<R, 2, true>(ns, L.rs, dk, slots, lid);
-          if (ns) {
-            start_sample_ray<R>(kargs<R>(), L, u, v, dk[0], dk[1]);
-            have_ray = true;
-          }
-        }
-      } else if (ns) {
-        if constexpr ((VAR & 8192) != 0) {  // measurement: sample start twice (same image)
-          Lane<R> L2 = L;
-          asm volatile("" : "+v"(L2.px));
-          R u2, v2, dk2[2];
-          start_sample_uv<R>(kargs<R>(), L2, u2, v2);
-          coop_reject<R, 2, false>(true, L2.rs, dk2, slots, lid);
-          start_sample_ray<R>(kargs<R>(), L2, u2, v2, dk2[0], dk2[1]);
-          asm volatile("" ::"v"(L2.d.x), "v"(L2.d.y), "v"(L2.d.z), "v"(L2.o.x), "v"(L2.o.y), "v"(L2.o.z),
-                       "v"(L2.time), "v"(L2.rs));
-        }
-        R u, v, dk[2];
-        start_sample_uv<R>(kargs<R>(), L, u, v);
-        coop_reject<R, 2, false>(true, L.rs, dk, slots, lid);
-        start_sample_ray<R>(kargs<R>(), L, u, v, dk[0], dk[1]);
-        have_ray = true;
-      }
-    }
-    RTW_STAMP(1)
-
-    // ---- 3. one bounce segment ----
-    // 3a. closest hit (lanes with a live ray); 3b. the unit-ball point for
-    // diffuse/metal lanes (converged); 3c. hit record + scatter.  Only the
-    // winner, its distance and its material cross 3b (register pressure).
-    bool ended = false, shading = false;
-    uint32_t kind = 0;
-    int hit = -1;
-    R tmax = kInf;
-    if (have_ray) {
-      const int b = bounce(kind, hit, tmax, std::false_type{});
-      ended = b == 1;
-      shading = b == 2;
-    }
-    RTW_STAMP(3)
-    {
-      // randomPointInUnitSphere (rand.zig:22-28) for Lambertian and Metal.
-      const bool nb = shading && kind <= 2u;
-      R b3[3] = {(R)0, (R)0, (R)0};
-      if constexpr ((VAR & 4096) != 0) {  // measurement: the unit-ball sampler twice (same image)
-        if (__any(nb)) {
-          uint64_t rs2 = L.rs;
-          asm volatile("" : "+v"(rs2));
-          R c3[3];
-          coop_reject<R, 3, COOP>(nb, rs2, c3, slots, lid);
-          asm volatile("" ::"v"(c3[0]), "v"(c3[1]), "v"(c3[2]), "v"(rs2));
-        }
-      }
-      if (__any(nb)) coop_reject<R, 3, COOP>(nb, L.rs, b3, slots, lid);
-      RTW_STAMP(7)
-      if constexpr ((VAR & 16384) != 0) {  // measurement: hit record + scatter twice (same image)
-        if (shading) {
-          Lane<R> L2 = L;
-          asm volatile("" : "+v"(L2.o.x));
-          const int e2 = scatter_hit<R, F32, VAR>(T, L2, hit, tmax, kind, b3) ? 1 : 0;
-          asm volatile("" ::"v"(L2.d.x), "v"(L2.d.y), "v"(L2.d.z), "v"(L2.T.x), "v"(L2.T.y), "v"(L2.T.z),
-                       "v"(L2.o.x), "v"(L2.o.y), "v"(L2.o.z), "v"(e2), "v"(L2.rs));
-        }
-      }
-      if (shading) {
-        if (scatter_hit<R, F32, VAR>(T, L, hit, tmax, kind, b3)) ended = true;
-      }
-    }
-    RTW_STAMP(8)
-    if (ended) finish_sample();
   }
-  }  // default loop
   if (STATS) {
     atomicAdd(A.stats + 0, st.samples);
     atomicAdd(A.stats + 1, st.segments);
@@ -689,81 +495,31 @@ __global__ void __launch_bounds__(256) finalize_kernel(FinalizeArgs F) {
   }
 }
 
-template <typename R, bool F32, int VAR>
-static void launch_var(const TraceArgs<R>& a, uint32_t grid, size_t lds, hipStream_t s, int mode) {
-  if (mode == 1)
-    hipLaunchKernelGGL((trace_kernel<R, F32, 1, VAR>), dim3(grid), dim3(kTraceBlock), lds, s, a);
-#ifdef RTW_MEASURE  // per-phase s_memtime stamps (diagnostic)
-  else if (mode == 2)
-    hipLaunchKernelGGL((trace_kernel<R, F32, 2, VAR>), dim3(grid), dim3(kTraceBlock), lds, s, a);
-#endif
-  else
-    hipLaunchKernelGGL((trace_kernel<R, F32, 0, VAR>), dim3(grid), dim3(kTraceBlock), lds, s, a);
-}
-
-// The product library holds ONE variant per precision (kDefaultVarF64 /
-// kDefaultVarF32, rtw_internal.hpp).  The A/B variants of round 1
-// (profiles/r01/ab_*.txt) are compiled only into the measurement build
-// (-DRTW_MEASURE, tools/); any other value is refused (trace_variant_built).
-#ifdef RTW_MEASURE
-#define RTW_AB_VARIANTS(X)                                                                                     \
-  X(0) X(1) X(5) X(9) X(16) X(24) X(32) X(36) X(20) X(68) X(72) X(40) X(4) X(8) X(516) X(1540) X(520) X(1544)  \
-  X(33284) X(66052) X(131588) X(229892) X(197128) X(164356) X(131592) X(426500) X(393736) X(1999364)         \
-  X(1966600) X(950792) X(1016324) X(2064900) X(918020) X(2564) X(4612) X(8708) X(16900)                    \
-  X(950788) X(3047940) X(3048964) X(918024) /* round-1 f64 default (the r02 A/B baseline), round-2 default  \
-                                     before bit 1024, round-2 f64 / f32 defaults (before kVarHomeLds) */
-#endif
-
-template <bool F32>
-constexpr int default_var() {
-  return F32 ? kDefaultVarF32 : kDefaultVarF64;
-}
-
-bool trace_variant_built(int precision, int var) {
-  if (var == (precision == 1 ? kDefaultVarF32 : kDefaultVarF64)) return true;
-  if (var == (precision == 1 ? kMaskedVarF32 : kMaskedVarF64)) return true;
-#ifdef RTW_MEASURE
-  switch (var) {
-#define RTW_CASE(v) case v:
-    RTW_AB_VARIANTS(RTW_CASE)
-#undef RTW_CASE
-    return true;
-  }
-#endif
-  return false;
-}
-
 template <typename R, bool F32>
 static hipError_t launch_trace(const TraceArgs<R>& a, uint32_t grid, size_t lds, hipStream_t s, int mode,
-                               int var) {
-  if (var == default_var<F32>()) {
-    launch_var<R, F32, default_var<F32>()>(a, grid, lds, s, mode);
-    return hipGetLastError();
-  }
-  constexpr int kMaskedVar = F32 ? kMaskedVarF32 : kMaskedVarF64;
-  if (var == kMaskedVar) {  // a masked accumulator pass (product mode only)
+                               bool masked) {
+  if (masked) {  // a masked accumulator pass (product mode only)
     if (mode != 0 || !a.tile_list || !a.tile_mask) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((trace_kernel<R, F32, 0, kMaskedVar>), dim3(grid), dim3(kTraceBlock), lds, s, a);
-    return hipGetLastError();
-  }
-#ifdef RTW_MEASURE
-  switch (var) {
-#define RTW_CASE(v) \
-  case v: launch_var<R, F32, v>(a, grid, lds, s, mode); return hipGetLastError();
-    RTW_AB_VARIANTS(RTW_CASE)
-#undef RTW_CASE
-  }
+    hipLaunchKernelGGL((trace_kernel<R, F32, 0, true>), dim3(grid), dim3(kTraceBlock), lds, s, a);
+  } else if (mode == 1) {
+    hipLaunchKernelGGL((trace_kernel<R, F32, 1, false>), dim3(grid), dim3(kTraceBlock), lds, s, a);
+#ifdef RTW_MEASURE  // per-phase s_memtime stamps (diagnostic)
+  } else if (mode == 2) {
+    hipLaunchKernelGGL((trace_kernel<R, F32, 2, false>), dim3(grid), dim3(kTraceBlock), lds, s, a);
 #endif
-  return hipErrorInvalidValue;  // not built (rtw_capi.hip checks trace_variant_built first)
+  } else {
+    hipLaunchKernelGGL((trace_kernel<R, F32, 0, false>), dim3(grid), dim3(kTraceBlock), lds, s, a);
+  }
+  return hipGetLastError();
 }
 
 hipError_t launch_trace_f64(const TraceArgs<double>& a, uint32_t grid, size_t lds, hipStream_t s, int mode,
-                            int var) {
-  return launch_trace<double, false>(a, grid, lds, s, mode, var);
+                            bool masked) {
+  return launch_trace<double, false>(a, grid, lds, s, mode, masked);
 }
 hipError_t launch_trace_f32(const TraceArgs<float>& a, uint32_t grid, size_t lds, hipStream_t s, int mode,
-                            int var) {
-  return launch_trace<float, true>(a, grid, lds, s, mode, var);
+                            bool masked) {
+  return launch_trace<float, true>(a, grid, lds, s, mode, masked);
 }
 hipError_t launch_finalize(const FinalizeArgs& a, hipStream_t s) {
   const uint32_t grid = min((a.npix + 255u) / 256u, 4096u);
@@ -771,30 +527,29 @@ hipError_t launch_finalize(const FinalizeArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <typename R, bool F32, int VAR>
-static int occ(size_t lds) {
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<R, F32, 0, VAR>, kTraceBlock, lds) != hipSuccess)
-    nb = 0;
-  return nb;
+// f(std::bool_constant<F32>, std::bool_constant<MASKED>) for a launch's (precision, masked)
+template <typename F>
+static auto with_cfg(int precision, bool masked, F f) {
+  if (precision == 1) return masked ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  return masked ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
 }
-// Resident workgroups per CU of a built variant; 0 for a variant not built.
-int trace_blocks_per_cu(int precision, size_t lds, int var) {
-  if (!trace_variant_built(precision, var)) return 0;
-  int nb = 0;
-  if (precision == 1 && var == kDefaultVarF32) nb = occ<float, true, kDefaultVarF32>(lds);
-  else if (precision != 1 && var == kDefaultVarF64) nb = occ<double, false, kDefaultVarF64>(lds);
-  else if (precision == 1 && var == kMaskedVarF32) nb = occ<float, true, kMaskedVarF32>(lds);
-  else if (precision != 1 && var == kMaskedVarF64) nb = occ<double, false, kMaskedVarF64>(lds);
-#ifdef RTW_MEASURE
-  else switch (var) {
-#define RTW_CASE(v) \
-  case v: nb = precision == 1 ? occ<float, true, v>(lds) : occ<double, false, v>(lds); break;
-    RTW_AB_VARIANTS(RTW_CASE)
-#undef RTW_CASE
-  }
-#endif
+int trace_blocks_per_cu(int precision, size_t lds, bool masked) {
+  const int nb = with_cfg(precision, masked, [&](auto f32, auto m) {
+    using R = std::conditional_t<f32.value, float, double>;
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_kernel<R, f32.value, 0, m.value>, kTraceBlock, lds) !=
+        hipSuccess)
+      n = 0;
+    return n;
+  });
   return nb > 0 ? nb : 1;
+}
+bool trace_primary_first(int precision, bool masked) {
+  return with_cfg(precision, masked, [](auto f32, auto m) { return TraceCfg<f32.value, m.value>::kPrimaryFirst; });
+}
+size_t trace_home_lds_bytes(int precision, bool masked) {
+  return 8 + (kTraceBlock / 64) *
+                 with_cfg(precision, masked, [](auto f32, auto m) { return TraceCfg<f32.value, m.value>::kHomeStride; });
 }
 
 }  // namespace rtwk

@@ -134,7 +134,7 @@ __device__ __forceinline__ bool take_unit(const TraceArgs<R>& A, uint32_t batch,
 
 // Start sample s of `unit` in lane L (start_sample_uv / lens disk /
 // start_sample_ray: main.zig:390-391, :91-100).  Per-lane disk rejection
-// (the megakernel's default; every variant gives the same bits).
+// (as the megakernel's primary-first loop; a cooperative pass gives the same bits).
 template <typename R>
 __device__ __forceinline__ void start_path(const TraceArgs<R>& A, uint32_t unit, uint32_t s, Lane<R>& L) {
   uint32_t px, ly, c;
@@ -252,14 +252,9 @@ __device__ __forceinline__ bool group_has_work(const WfArgs<R>& A) {
 // whether the lane holds a live path afterwards.  STATS: count finished
 // samples and shaded segments (rtw_render_counts); FIN: also as the
 // in-register drain's own counts (stats 9, 10: rtw_render_counts_ex).
-// scatter_hit's variant bits: the megakernel's exact fast f64 sqrt and the
-// host's Schlick r0^2 table (both bit-identical forms); -0.9 % per frame on top
-// of the clustered pretest (profiles/r06/wf_step_ab.txt).
-#ifndef RTW_WF_SCATTER_VAR  // (A/B builds override it; 0: the plain forms)
-#define RTW_WF_SCATTER_VAR (kVarFastSqrt | kVarR0Table)
-#endif
-template <typename R>
-constexpr int kWfScatterVar = RTW_WF_SCATTER_VAR;
+// (scatter_hit is the megakernel's: the exact fast f64 sqrt and the host's
+// Schlick r0^2 table, both bit-identical forms; -0.9 % per frame on top of the
+// clustered pretest, profiles/r06/wf_step_ab.txt.)
 #ifndef RTW_WF_PREDRAW
 #define RTW_WF_PREDRAW 0  // A/B builds: the dielectric's draw inside the bounce's cooperative pass (neutral;
                           // profiles/r06/wf_step_ab.txt item 6)
@@ -310,10 +305,10 @@ __device__ __forceinline__ void bounce(const WfArgs<R>& A, const LdsTables<R>& T
       }
   } else {
     const bool nb = shading && kind <= 2u;
-    if (__any(nb)) coop_reject<R, 3, true>(nb, L.rs, b3, T.slots, lid);
+    if (__any(nb)) coop_reject<R, 3>(nb, L.rs, b3, T.slots, lid);
   }
   if (shading) {
-    if (scatter_hit<R, F32, kWfScatterVar<R>, kWfPreDraw, true>(T, L, hit, tmax, kind, b3, raw))
+    if (scatter_hit<R, F32, kWfPreDraw, true>(T, L, hit, tmax, kind, b3, raw))
       ended = true;  // absorbed: emitted == 0 (material.zig:31-38)
     else if (L.depth == A.t.max_depth)
       ended = true;  // rayColor(depth == 0) is black (main.zig:105-108)
@@ -396,9 +391,8 @@ __device__ __forceinline__ bool shade_step(const WfArgs<R>& A, const LdsTables<R
 constexpr int kWfExtendOcc = RTW_WF_EXT_OCC;
 // (The clustered pretest, +5 % in the megakernel, made the fused engine 12 % slower
 // in round 2: profiles/r02/wf_cluster_ab.txt — its extra registers spilled in
-// wf_step.  Without spills since round 6 it is the default: RTW_WF_VAR_EXTRA.)
-template <typename R>
-constexpr int kWfExtendVar = sizeof(R) == 8 ? (kVarFastSqrt | RTW_WF_VAR_EXTRA) : 0;
+// wf_step.  Without spills since round 6 the extend, generate and step kernels
+// run it: -3.0 % per configs[1] frame, profiles/r06/wf_step_ab.txt.)
 
 // ---------------------------------------------------------------- generate --
 // Every slot of the wave's segments takes a unit and starts its first sample.
@@ -432,7 +426,7 @@ __global__ void __launch_bounds__(kTraceBlock) wf_generate(WfArgs<R> A) {
         int hit = -1;
         R tmax = (R)__builtin_huge_val();
         if (got) {
-          closest_hit<R, F32, 0, kWfExtendVar<R>>(opaque(kargs<R>())->sc, T, L, A.t.tmin, A.t.pre_k, lid, st, hit, tmax);
+          closest_hit<R, F32, 0>(opaque(kargs<R>())->sc, T, L, A.t.tmin, A.t.pre_k, lid, st, hit, tmax);
           to_hit_point(L, hit, tmax);
         }
         push_path_hit(A.out, base, out_n, got, L, slot, hit);
@@ -450,9 +444,9 @@ __global__ void __launch_bounds__(kTraceBlock) wf_generate(WfArgs<R> A) {
 
 // ------------------------------------------------------------------ extend --
 // The megakernel's closest-hit instantiation: scene fields re-read from the
-// kernel argument inside closest_hit (trace VAR bit 512: the SceneView copy
-// would sit in SGPRs for the whole kernel, at the 100-SGPR limit), the exact
-// fast f64 sqrt (kVarFastSqrt), and a waves-per-SIMD target for the register
+// kernel argument inside closest_hit (the SceneView copy would sit in SGPRs
+// for the whole kernel, at the 100-SGPR limit), the exact fast f64 sqrt,
+// and a waves-per-SIMD target for the register
 // allocator (kWfExtendOcc, chosen by A/B on MI355X).
 template <typename R, bool F32>
 __global__ void __launch_bounds__(kTraceBlock, kWfExtendOcc) wf_extend(WfArgs<R> A) {
@@ -486,7 +480,7 @@ __global__ void __launch_bounds__(kTraceBlock, kWfExtendOcc) wf_extend(WfArgs<R>
     if (cur_ok) {
       int hit = -1;
       R tmax = (R)__builtin_huge_val();
-      closest_hit<R, F32, 0, kWfExtendVar<R>>(opaque(kargs<R>())->sc, T, cur, tmin, pre_k, lid, st, hit, tmax);
+      closest_hit<R, F32, 0>(opaque(kargs<R>())->sc, T, cur, tmin, pre_k, lid, st, hit, tmax);
       const uint32_t i = seg * kSegCap + lid;
       A.hit_t[i] = tmax;
       A.hit_k[i] = hit;
@@ -660,7 +654,7 @@ __global__ void __launch_bounds__(kTraceBlock, RTW_WF_STEP_OCC) wf_step([[maybe_
       nh = -1;
       nt = (R)__builtin_huge_val();
       if (live) {
-        closest_hit<R, F32, 0, kWfExtendVar<R>>(opaque(kargs<R>())->sc, T, L, A.t.tmin, A.t.pre_k, lid, st, nh, nt);
+        closest_hit<R, F32, 0>(opaque(kargs<R>())->sc, T, L, A.t.tmin, A.t.pre_k, lid, st, nh, nt);
         to_hit_point(L, nh, nt);
       }
       if (!wany(live)) break;
@@ -733,7 +727,7 @@ __global__ void __launch_bounds__(kTraceBlock) wf_finish(WfArgs<R> A) {
       if (stored) {
         hit = hit0;
       } else if (live) {
-        closest_hit<R, F32, 0, 0>(S, T, L, tmin, pre_k, lid, st, hit, tmax);
+        closest_hit<R, F32, 0, /*PRIMARY*/ false, /*FLAT*/ true>(S, T, L, tmin, pre_k, lid, st, hit, tmax);
         to_hit_point(L, hit, tmax);
       }
       stored = false;
@@ -862,7 +856,7 @@ __global__ void __launch_bounds__(kTraceBlock) wf_drain([[maybe_unused]] WfArgs<
           hit = stored;
           stored = -2;
         } else {
-          closest_hit<R, F32, 0, 0>(S, T, L, tmin, pre_k, lid, st, hit, tmax);
+          closest_hit<R, F32, 0, /*PRIMARY*/ false, /*FLAT*/ true>(S, T, L, tmin, pre_k, lid, st, hit, tmax);
           to_hit_point(L, hit, tmax);
         }
       }

@@ -884,11 +884,11 @@ __global__ void __launch_bounds__(kWorldBlock, OCC) world_kernel(WorldArgs A) {
   // (scalar loads through a laundered kernarg pointer) instead of living in
   // SGPRs for the whole kernel: at the 100-SGPR limit they spill to VGPR
   // lanes (v_writelane / v_readlane in the traversal loop).  As the
-  // megakernel's scene fields (rtw_trace.hip VAR bit 512); +1.4 % on the
+  // megakernel's scene fields (rtw_trace.hip bounce); +1.4 % on the
   // globe and Cornell (profiles/r02/world_karg_ab.txt).
   const RTW_CONST WorldView& W =
       opaque((const RTW_CONST WorldArgs*)__builtin_amdgcn_kernarg_segment_ptr())->w;
-  // The loop's other argument fields too (as the megakernel's VAR bit 1024):
+  // The loop's other argument fields too (as the megakernel's TraceCfg::kLoopArgsFromKernarg):
   // read where used, through the same laundered pointer.
 #define WKA(f) (opaque((const RTW_CONST WorldArgs*)__builtin_amdgcn_kernarg_segment_ptr())->f)
   const uint32_t* order = W.order;

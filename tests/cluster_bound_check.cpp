@@ -1,6 +1,6 @@
 // cluster_bound_check.cpp — adversarial check of the clustered pretest
 // (raytracinginoneweekend.zig_amd/csrc/rtw_cull.hpp cluster_sphere + cull_x;
-// trace VAR kVarCluster).  For random clusters of <= 8 static / moving
+// rtw_device.hpp closest_hit, f64).  For random clusters of <= 8 static / moving
 // spheres and rays grazing the cluster's bounding sphere, x < 0 for the
 // cluster record must imply that every member's exact f64 discriminant
 // (hittable.zig:96-101, the kernel's operation order) is negative at any

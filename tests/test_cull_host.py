@@ -56,7 +56,7 @@ CLSRC = os.path.join(REPO, "tests", "cluster_bound_check.cpp")
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 def test_cluster_pretest_never_skips_a_member_that_can_be_hit(tmp_path):
-    """Clustered pretest (trace VAR kVarCluster, rtw_cull.hpp cluster_sphere):
+    """Clustered pretest (rtw_device.hpp closest_hit in f64, rtw_cull.hpp cluster_sphere):
     a cluster proven missed has every member's exact f64 discriminant negative
     (at every shutter time); with the bound radius shrunk by 2 % the check
     finds violations (it has teeth)."""

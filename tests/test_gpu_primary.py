@@ -1,4 +1,4 @@
-"""The megakernel's primary-first loop (kVarPrimaryFirst): a lane
+"""The megakernel's primary-first loop (TraceCfg::kPrimaryFirst): a lane
 resolves its camera ray itself from the mask of its tile (csrc/rtw_beam.hpp)
 and shades that hit in the same iteration.  Every case is bit-identical
 (max|d| = 0) to oracle Tier B, as the rotated loop is, and the counts pass

@@ -156,8 +156,8 @@ def test_wavefront_custom_scene(rtw, oracle, precision):
 @pytest.mark.parametrize("time1", [1.0, 1.2])
 def test_wavefront_clustered_pretest(rtw, oracle, time1):
     """The bounce kernels run the megakernel's clustered pretest since round 6
-    (rtw_internal.hpp RTW_WF_VAR_EXTRA): three time groups mixed in clusters,
-    odd cluster sizes, with a shutter inside every group (clusters on) and one
+    (rtw_device.hpp closest_hit, every f64 kernel but the drains): three time
+    groups mixed in clusters, odd cluster sizes, with a shutter inside every group (clusters on) and one
     outside a group (clusters off, the flat pretest) — the megakernel's image
     bit for bit and the oracle's."""
     sph, mats = clustered_scene(rtw)

@@ -1,11 +1,11 @@
 """Static attribution of one trace_kernel instantiation's hot-loop VALU / SALU
 instructions to source lines and instruction classes, from an ISA dump built
-with -gline-tables-only (tools/isa_quick.sh -gline-tables-only, or make isa).
+with -gline-tables-only (make isa EXTRA=-gline-tables-only).
 The classes follow the VALU mix of profiles/rNN/valu_issue.json: f64, f32 (and
 packed f32), integer, conversion, and "other" (moves, selects, compares, bit and
 lane operations: what the SQ counters do not split apart).
 
-  python tools/isa_attrib.py build/quick_g.s d 19826180 [top] [loop-header]
+  python tools/isa_attrib.py build/rtw_trace-gfx950.s d 0 [top] [loop-header]      (d|f, masked 0|1)
 
 The loop is the one with the most VALU instructions in its own blocks (nested
 loops excluded, as tools/isa_loops.py) unless a header label is given."""
@@ -13,14 +13,14 @@ import collections
 import re
 import sys
 
-path, prec, var = sys.argv[1], sys.argv[2], sys.argv[3]
+path, prec, masked = sys.argv[1], sys.argv[2], sys.argv[3]
 top = int(sys.argv[4]) if len(sys.argv) > 4 else 25
 want_hdr = sys.argv[5] if len(sys.argv) > 5 else None
 s = open(path).read()
 files = {}
 for m in re.finditer(r'^\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', s, re.M):
     files[m.group(1)] = (m.group(3) or m.group(2)).split('/')[-1]
-m = re.search(rf'^(_ZN4rtwk12trace_kernelI{prec}Lb\dELi0ELi{var}E\S*):', s, re.M)
+m = re.search(rf'^(_ZN4rtwk12trace_kernelI{prec}Lb\dELi0ELb{masked}E\S*):', s, re.M)
 body = s[m.end():s.find('.Lfunc_end', m.end())].split('\n')
 
 
@@ -84,7 +84,7 @@ for lp, ins in blocks:
         if c == 'other':
             ops_other[op.split('_e32')[0].split('_e64')[0]] += 1
 tot = sum(cls.values())
-print(f"trace_kernel<{prec}> var {var}: hot loop {hdr}: {tot} VALU, {salu} SALU (static, own blocks)")
+print(f"trace_kernel<{prec}> masked {masked}: hot loop {hdr}: {tot} VALU, {salu} SALU (static, own blocks)")
 print("classes:", ", ".join(f"{k} {v} ({100 * v / tot:.1f} %)" for k, v in cls.most_common()))
 print("\"other\" by opcode:", ", ".join(f"{k} {v}" for k, v in ops_other.most_common(14)))
 print(f"\ntop {top} source lines by \"other\" VALU (file:line  other / all VALU):")

@@ -1,17 +1,17 @@
 """Static per-source-line counts of chosen instructions in one trace_kernel
 instantiation of an ISA dump built with -gline-tables-only.
-Usage: isa_lines.py file.s <prec d|f> <var> <regex> [top]"""
+Usage: isa_lines.py file.s <prec d|f> <masked 0|1> <regex> [top]"""
 import collections
 import re
 import sys
 
 s = open(sys.argv[1]).read()
-prec, var, pat = sys.argv[2], sys.argv[3], re.compile(sys.argv[4])
+prec, masked, pat = sys.argv[2], sys.argv[3], re.compile(sys.argv[4])
 top = int(sys.argv[5]) if len(sys.argv) > 5 else 30
 files = {}
 for m in re.finditer(r'^\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', s, re.M):
     files[m.group(1)] = (m.group(3) or m.group(2)).split('/')[-1]
-m = re.search(rf'^(_ZN4rtwk12trace_kernelI{prec}Lb\dELi0ELi{var}E\S*):', s, re.M)
+m = re.search(rf'^(_ZN4rtwk12trace_kernelI{prec}Lb\dELi0ELb{masked}E\S*):', s, re.M)
 body = s[m.end():s.find('.Lfunc_end', m.end())].split('\n')
 cur, cnt = None, collections.Counter()
 for l in body:

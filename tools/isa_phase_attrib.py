@@ -1,5 +1,5 @@
-"""Static attribution of the megakernel's rotated loop (rtw_trace.hip, variant
-with kVarMergedStart) to its PHASES: every VALU instruction of the loop and
+"""Static attribution of the megakernel's rotated loop (rtw_trace.hip; the loop
+of the f64 masked kernel, MASKED = 1) to its PHASES: every VALU instruction of the loop and
 of the loops nested in it is charged to the loop-body line of rtw_trace.hip
 its inlined call chain starts from (the outermost `rtw_trace.hip:N` of the
 instruction's .loc chain in a -gline-tables-only ISA dump), and the lines map
@@ -8,23 +8,23 @@ cooperative sampler, scatter, camera ray, closest hit (bounce), finish.
 Classes as tools/isa_attrib.py (f64, f32, int, cvt, "other").  Static counts:
 an instruction of a nested loop counts once, whatever its trip count.
 
-  python tools/isa_phase_attrib.py build/tqg.s 19826180"""
+  python tools/isa_phase_attrib.py build/rtw_trace-gfx950.s 1        (masked 0|1)"""
 import collections
 import re
 import sys
 
 sys.path.insert(0, __import__("os").path.dirname(__file__))
-path, var = sys.argv[1], sys.argv[2]
+path, masked = sys.argv[1], sys.argv[2]
 s = open(path).read()
 src = open(__import__("os").path.join(__import__("os").path.dirname(__file__), "..", "raytracinginoneweekend.zig_amd",
                                       "csrc", "rtw_trace.hip")).read().split("\n")
 # phase boundaries from the source: the rotated loop's statements
 marks = {"take_units();": "take units", "start_sample_uv<R>(kargs<R>(), L, u, v);": "sample start (u, v)",
-         "coop_reject_mixed<R>(dim": "cooperative sampler", "scatter_hit<R, F32, VAR, PRE>": "scatter",
-         "start_sample_ray<R, PRE>": "camera ray", "const int b = bounce(kind, hit, tmax);": "closest hit (bounce)",
+         "coop_reject_mixed<R>(dim": "cooperative sampler", "scatter_hit<R, F32, true>": "scatter",
+         "start_sample_ray<R, true>": "camera ray", "const int b = bounce(kind, hit, tmax, std::false_type{});": "closest hit (bounce)",
          "if (ended) finish_sample();": "finish sample"}
-loop0 = next(i for i, l in enumerate(src) if "if constexpr ((VAR & kVarMergedStart) != 0) {" in l) + 1
-loop1 = next(i for i, l in enumerate(src) if i > loop0 and l.strip() == "} else {") + 1
+loop0 = next(i for i, l in enumerate(src) if "if (!primary_ran) {" in l) + 1
+loop1 = next(i for i, l in enumerate(src) if i > loop0 and l.startswith("  if (STATS) {")) + 1
 bounds = []
 for i in range(loop0, loop1):
     for k, name in marks.items():
@@ -43,7 +43,7 @@ def phase_of(line):
     return name
 
 
-m = re.search(rf'^(_ZN4rtwk12trace_kernelIdLb\dELi0ELi{var}E\S*):', s, re.M)
+m = re.search(rf'^(_ZN4rtwk12trace_kernelIdLb\dELi0ELb{masked}E\S*):', s, re.M)
 body = s[m.end():s.find('.Lfunc_end', m.end())].split('\n')
 
 
@@ -99,7 +99,7 @@ for l in body:
 order = ["take units", "sample start (u, v)", "cooperative sampler", "scatter", "camera ray", "closest hit (bounce)",
          "finish sample", "loop control", "other loop code"]
 tot = collections.Counter()
-print(f"trace_kernel<d> var {var}: rotated loop {hot} and its nested loops, static VALU by phase and class")
+print(f"trace_kernel<d> masked {masked}: rotated loop {hot} and its nested loops, static VALU by phase and class")
 print(f"{'phase':24s} {'all':>5s} {'f64':>5s} {'f32':>5s} {'int':>5s} {'cvt':>5s} {'other':>6s}")
 for ph in order:
     c = cnt.get(ph)

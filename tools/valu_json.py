@@ -14,8 +14,8 @@ import sys
 
 SIMDS = 256 * 4
 SEGMENTS = 922534227  # segments of one configs[1] launch (bench.py counts pass; seed 42)
-# Phase costs from the phase-duplication builds (RTW_MEASURE, tools/gpu_measure.sh,
-# variant 516): delta SQ_INSTS_VALU per wave-iteration when the phase runs twice.
+# Phase costs from round 1's phase-duplication builds of the textbook-order loop (retired: DESIGN.md's
+# table of retired variants; profiles/r01): delta SQ_INSTS_VALU per wave-iteration when the phase runs twice.
 PHASES = {"narrow_sphere_pretest": 371, "unit_ball_sampler_coop_reject": 347,
           "sample_start_uv_disk_camera_ray": 336, "hit_record_and_scatter": 236}
 
@@ -24,9 +24,9 @@ def counters(d):
     vals, var, ms = {}, None, None
     for f in glob.glob(f"{d}/*counter_collection.csv"):
         for r in csv.DictReader(open(f)):
-            m = re.search(r"trace_kernel<double, false, 0, (\d+)>", r["Kernel_Name"])
+            m = re.search(r"trace_kernel<double, false, 0, (true|false)>", r["Kernel_Name"])
             if m:
-                var = int(m.group(1))
+                var = "f64 masked" if m.group(1) == "true" else "f64 unmasked"
                 vals[r["Counter_Name"]] = vals.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
     for f in glob.glob(f"{d}/*kernel_trace.csv"):
         for r in csv.DictReader(open(f)):
