@@ -21,6 +21,78 @@ def to_oracle_camera(oracle, cam):
     return oc
 
 
+# ------------------------------------------- the tile-beam bound on the host ----
+# tests/native/beam_bound_check.cpp evaluates csrc/rtw_beam.hpp with the host compiler
+# (tests/test_beam_host.py); its `masks` mode gives the GPU tests the popcount the
+# megakernel's primary-first loop must report (RTW_STAT primary_mask_popcount).
+CAMERA_VECTORS = ("origin", "horizontal", "vertical", "lower_left_corner", "u", "v")
+
+
+def build_beam_check(out_dir, header_dir=None, name="beamchk"):
+    """Compile beam_bound_check against the rtw_beam.hpp in header_dir (default: csrc)."""
+    import os
+    import subprocess
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header_dir = header_dir or os.path.join(repo, "raytracinginoneweekend.zig_amd", "csrc")
+    exe = os.path.join(str(out_dir), name)
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-I", str(header_dir),
+                    os.path.join(repo, "tests", "native", "beam_bound_check.cpp"), "-o", exe], check=True)
+    return exe
+
+
+_beam_exe = None
+
+
+def beam_check_exe():
+    """The checker built once per process, in a temporary directory."""
+    global _beam_exe
+    if _beam_exe is None:
+        import atexit
+        import shutil
+        import tempfile
+        d = tempfile.mkdtemp(prefix="beamchk")
+        atexit.register(shutil.rmtree, d, ignore_errors=True)
+        _beam_exe = build_beam_check(d)
+    return _beam_exe
+
+
+def write_beam_scene(path, spheres):
+    """spheres: (c0, c1, radius, t0, t1, moving) tuples -> the checker's scene file."""
+    with open(path, "w") as f:
+        f.write(f"{len(spheres)}\n")
+        for c0, c1, r, t0, t1, mv in spheres:
+            f.write(" ".join(repr(float(x)) for x in (*c0, *c1, r, t0, t1)) + f" {int(mv)}\n")
+    return str(path)
+
+
+def write_beam_cases(path, cases):
+    """cases: (camera, (W, H, row_begin, row_stride, row_count)); a camera is anything with the rtw_camera
+    fields (a ctypes Camera, a namespace of sequences) -> the checker's case file."""
+    with open(path, "w") as f:
+        f.write(f"{len(cases)}\n")
+        for cam, frame in cases:
+            vals = [x for n in CAMERA_VECTORS for x in getattr(cam, n)] + [cam.lens_radius, cam.time0, cam.time1]
+            f.write(" ".join(repr(float(x)) for x in vals) + " " + " ".join(str(int(x)) for x in frame) + "\n")
+    return str(path)
+
+
+def host_masks(spheres, cam, params):
+    """The host evaluation of the tile masks of one render (rtw Sphere array, Camera, Params): a dict of
+    popcount (summed over the tiles; one batch = one (tile, chunk) adds its tile's), tiles, full, guarded
+    (tiles the wide-cone guard answers for) and narrow (spheres of radius < 100)."""
+    import re
+    import subprocess
+    import tempfile
+    with tempfile.TemporaryDirectory(prefix="beamcase") as d:
+        sc = write_beam_scene(d + "/scene.txt", [(list(s.c0), list(s.c1), s.radius, s.t0, s.t1, s.moving) for s in spheres])
+        cs = write_beam_cases(d + "/cases.txt", [(cam, (params.width, params.height, params.row_begin, params.row_stride,
+                                                        params.row_count))])
+        p = subprocess.run([beam_check_exe(), sc, "masks", cs], capture_output=True, text=True)
+    m = re.search(r"case 0 popcount (\d+) tiles (\d+) full (\d+) guarded (\d+) narrow (\d+)", p.stdout)
+    assert m and p.returncode == 0, p.stdout + p.stderr
+    return dict(zip(("popcount", "tiles", "full", "guarded", "narrow"), map(int, m.groups())))
+
+
 def diff_stats(a, b):
     d = a.astype(np.int32) - b.astype(np.int32)
     return {

@@ -6,9 +6,32 @@
 // MovingSphere.hit, hittable.zig:95-131, :165-201) against every sphere; a
 // sphere with a root >= tmin must be in the tile's mask.
 //   beam_bound_check <scene.txt> [popcount]
+//   beam_bound_check <scene.txt> cases <cases.txt> [quick]
+//   beam_bound_check <scene.txt> masks <cases.txt>
 // scene.txt: n, then per sphere "c0.xyz c1.xyz radius t0 t1 moving".
 // `popcount`: also print the mean mask popcount of the narrow spheres over the
 // 1200x675 frame's tiles with the cover camera.
+// cases.txt: n, then per case the raw rtw_camera fields "origin.xyz
+// horizontal.xyz vertical.xyz lower_left_corner.xyz u.xyz v.xyz lens_radius
+// time0 time1" (any struct: it need not come from Camera.init) and the frame
+// "W H row_begin row_stride row_count" (the kernel's tiles are cut from
+// row_count rows, which may be fewer than the frame holds).
+// `cases`: the rays above for every case instead of the built-in cameras, and
+// for every (tile, sphere) pair the mask EXCLUDES rays aimed at that sphere:
+// from the lens centre and 16 rim points, at both shutter ends and the middle,
+// through the point of the tile's part of the focus plane nearest to the line
+// lens point -> sphere centre (a sphere behind the lens: the point mirrored
+// through the tile's centre); any hit is a violation.  Also prints "pairs P
+// in_mask M tiles T full_tiles F neg_tiles G narrow_hits N aimed A": the narrow
+// (tile, sphere) pairs and those in their mask, the tiles, those whose mask
+// holds every narrow sphere / a narrow sphere of negative radius, the hits on
+// narrow spheres, the aimed rays.  `quick`: stop after the first case with a
+// violation.
+// `masks`: no rays; per case "case i popcount P tiles T full F guarded G narrow
+// N": the sum over tiles of the narrow spheres in the mask (what the
+// megakernel counts per fetched batch, RTW_STAT primary_mask_popcount), the
+// tiles whose mask is full, and those the wide-cone guard answers for.
+// Narrow: radius < 100 (rtw_layout.hpp kWideRadius; a negative radius is narrow).
 // Prints "rays R hits H violations V"; exit status 1 when V > 0.
 #include <cmath>
 #include <cstdint>
@@ -81,12 +104,25 @@ bool exact_hit(const Sph& s, V o, V d, double time) {
 
 struct Totals {
   unsigned long long rays = 0, hits = 0, viol = 0, pop = 0, tiles = 0;
+  unsigned long long pairs = 0, full = 0, neg = 0, guarded = 0, narrow_hits = 0, aimed = 0;
 };
 
-// One frame: every tile's mask; with `rays`, the exact solves against it.
-void run_frame(const std::vector<Sph>& S, const Cam& c, uint32_t W, uint32_t H, uint32_t rb, uint32_t rs, bool rays,
-               Totals& T) {
-  const uint32_t rc = (H - rb + rs - 1) / rs;
+bool narrow(const Sph& s) { return !(s.r >= 100.0); }  // rtw_scene_pack.cpp: radius >= kWideRadius is wide
+
+// x of M x = r (columns m0, m1, m2), Cramer's rule; false: singular.
+bool solve3(V m0, V m1, V m2, V r, double x[3]) {
+  const double det = dot(m0, cross(m1, m2));
+  if (!(std::fabs(det) > 1e-300)) return false;
+  x[0] = dot(r, cross(m1, m2)) / det;
+  x[1] = dot(m0, cross(r, m2)) / det;
+  x[2] = dot(m0, cross(m1, r)) / det;
+  return std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]);
+}
+
+// One frame: every tile's mask; with `rays`, the exact solves against it; with `aimed`, also the rays aimed
+// at the spheres a mask excludes.  rc: the rows rendered (row_count).
+void run_frame(const std::vector<Sph>& S, const Cam& c, uint32_t W, uint32_t H, uint32_t rb, uint32_t rs, uint32_t rc,
+               bool rays, bool aimed, Totals& T) {
   const double O[3] = {c.origin.x, c.origin.y, c.origin.z}, L[3] = {c.llc.x, c.llc.y, c.llc.z};
   const double Hh[3] = {c.hor.x, c.hor.y, c.hor.z}, Vv[3] = {c.ver.x, c.ver.y, c.ver.z};
   const double U[3] = {c.u.x, c.u.y, c.u.z}, Vu[3] = {c.v.x, c.v.y, c.v.z};
@@ -101,10 +137,68 @@ void run_frame(const std::vector<Sph>& S, const Cam& c, uint32_t W, uint32_t H, 
       for (size_t i = 0; i < S.size(); ++i) {
         const double dc[3] = {S[i].c1[0] - S[i].c0[0], S[i].c1[1] - S[i].c0[1], S[i].c1[2] - S[i].c0[2]};
         mask[i] = rtwb::beam_may_hit(b, S[i].c0, dc, S[i].r, S[i].moving != 0, S[i].t0, S[i].t1, c.time0, c.time1);
-        if (std::fabs(S[i].r) < 100.0) T.pop += mask[i] ? 1 : 0;
+      }
+      {
+        unsigned nn = 0, in = 0, neg = 0;
+        for (size_t i = 0; i < S.size(); ++i)
+          if (narrow(S[i])) nn++, in += mask[i] ? 1 : 0, neg += (mask[i] && S[i].r < 0.0) ? 1 : 0;
+        T.pop += in, T.pairs += nn, T.full += (nn > 0 && in == nn) ? 1 : 0, T.neg += neg ? 1 : 0;
+        // the wide-cone guard answers for the tile: a speck far behind the lens is in its mask
+        const double far[3] = {b.O[0] - 1e3 * b.D[0], b.O[1] - 1e3 * b.D[1], b.O[2] - 1e3 * b.D[2]}, z3[3] = {0, 0, 0};
+        T.guarded += rtwb::beam_may_hit(b, far, z3, 1e-6, false, 0.0, 1.0, c.time0, c.time1) ? 1 : 0;
       }
       T.tiles++;
       if (!rays) continue;
+      if (aimed) {
+        const double w1 = (double)W - 1.0, h1 = (double)H - 1.0;
+        const double sc = 0.5 * ((double)px0 + (double)px1 + 1.0) / w1;
+        const double tc = 0.5 * ((double)(H - 1 - y1) + (double)(H - y0)) / h1;
+        for (size_t i = 0; i < S.size(); ++i) {
+          if (mask[i]) continue;
+          for (int li = 0; li < 17; ++li) {
+            const double ang = (li - 1) * (M_PI / 8.0);
+            const double dx = li ? std::cos(ang) : 0.0, dy = li ? std::sin(ang) : 0.0;
+            const V off = c.u * (dx * c.lens_radius) + c.v * (dy * c.lens_radius);
+            const V o = c.origin + off;
+            for (int ti = 0; ti < 3; ++ti) {
+              const double time = ti == 0 ? c.time0 : (ti == 1 ? c.time1 : 0.5 * (c.time0 + c.time1));
+              V cen = {S[i].c0[0], S[i].c0[1], S[i].c0[2]};
+              if (S[i].moving)
+                cen = cen + V{S[i].c1[0] - S[i].c0[0], S[i].c1[1] - S[i].c0[1], S[i].c1[2] - S[i].c0[2]} *
+                                ((time - S[i].t0) / (S[i].t1 - S[i].t0));
+              // llc + s hor + t ver = o + lam (cen - o)
+              double x[3];
+              if (!solve3(c.hor, c.ver, (cen - o) * -1.0, o - c.llc, x)) continue;
+              double s = x[0], t = x[1];
+              if (x[2] < 0.0) s = 2.0 * sc - s, t = 2.0 * tc - t;  // behind the lens: the far side of the tile
+              // the tile's nearest pixel column and row, and the jitter in it
+              const double sx = s * w1, jx = t * h1;
+              uint32_t px = px0;
+              if (sx > (double)px0) px = sx >= (double)px1 ? px1 : (uint32_t)sx;
+              const double ju = std::fmin(std::fmax(sx - (double)px, 0.0), one_m);
+              uint32_t jbest = H - 1 - (rb + ly0 * rs);
+              double dbest = INFINITY;
+              for (uint32_t ly = ly0; ly <= ly1; ++ly) {
+                const uint32_t j = H - 1 - (rb + ly * rs);
+                const double dist = jx < (double)j ? (double)j - jx : (jx > (double)j + 1.0 ? jx - ((double)j + 1.0) : 0.0);
+                if (dist < dbest) dbest = dist, jbest = j;
+              }
+              const double jv = std::fmin(std::fmax(jx - (double)jbest, 0.0), one_m);
+              const double u = ((double)px + ju) / w1, v = ((double)jbest + jv) / h1;
+              const V d = c.llc + c.hor * u + c.ver * v - c.origin - off;
+              T.aimed++;
+              if (exact_hit(S[i], o, d, time)) {
+                T.hits++;
+                if (narrow(S[i])) T.narrow_hits++;
+                if (T.viol < 5)
+                  fprintf(stderr, "violation (aimed): %ux%u rows %u:%u:%u tile (%u, %u) pixel (%u, %u) sphere %zu\n", W, H,
+                          rb, rs, rc, tx, ty, px, H - 1 - jbest, i);
+                T.viol++;
+              }
+            }
+          }
+        }
+      }
       for (uint32_t ly = ly0; ly <= ly1; ++ly)
         for (uint32_t px = px0; px <= px1; ++px) {
           const uint32_t y = rb + ly * rs, j = H - 1 - y;
@@ -130,6 +224,7 @@ void run_frame(const std::vector<Sph>& S, const Cam& c, uint32_t W, uint32_t H, 
                 for (size_t i = 0; i < S.size(); ++i)
                   if (exact_hit(S[i], o, d, time)) {
                     T.hits++;
+                    if (narrow(S[i])) T.narrow_hits++;
                     if (!mask[i]) {
                       if (T.viol < 5)
                         fprintf(stderr, "violation: %ux%u rows %u::%u tile (%u, %u) pixel (%u, %u) sphere %zu\n", W, H,
@@ -158,6 +253,39 @@ int main(int argc, char** argv) {
                &s.r, &s.t0, &s.t1, &s.moving) != 10)
       return 2;
   fclose(f);
+  if (argc > 3 && (std::strcmp(argv[2], "cases") == 0 || std::strcmp(argv[2], "masks") == 0)) {
+    const bool rays = std::strcmp(argv[2], "cases") == 0, quick = argc > 4 && std::strcmp(argv[4], "quick") == 0;
+    FILE* cf = fopen(argv[3], "r");
+    int nc = 0;
+    if (!cf || fscanf(cf, "%d", &nc) != 1 || nc <= 0) return 2;
+    Totals T;
+    for (int i = 0; i < nc; ++i) {
+      Cam c;
+      V* const vs[6] = {&c.origin, &c.hor, &c.ver, &c.llc, &c.u, &c.v};
+      for (V* v : vs)
+        if (fscanf(cf, "%lf %lf %lf", &v->x, &v->y, &v->z) != 3) return 2;
+      uint32_t W, H, rb, rs, rc;
+      if (fscanf(cf, "%lf %lf %lf %u %u %u %u %u", &c.lens_radius, &c.time0, &c.time1, &W, &H, &rb, &rs, &rc) != 8)
+        return 2;
+      if (W < 2 || H < 2 || rs == 0 || rc == 0 || (uint64_t)rb + (uint64_t)(rc - 1) * rs >= H) return 2;
+      if (rays) {
+        run_frame(S, c, W, H, rb, rs, rc, true, true, T);
+        if (quick && T.viol) break;
+      } else {
+        Totals P;
+        run_frame(S, c, W, H, rb, rs, rc, false, false, P);
+        printf("case %d popcount %llu tiles %llu full %llu guarded %llu narrow %llu\n", i, P.pop, P.tiles, P.full,
+               P.guarded, P.tiles ? P.pairs / P.tiles : 0ull);
+      }
+    }
+    fclose(cf);
+    if (rays) {
+      printf("rays %llu hits %llu violations %llu\n", T.rays, T.hits, T.viol);
+      printf("pairs %llu in_mask %llu tiles %llu full_tiles %llu neg_tiles %llu narrow_hits %llu aimed %llu\n", T.pairs,
+             T.pop, T.tiles, T.full, T.neg, T.narrow_hits, T.aimed);
+    }
+    return T.viol ? 1 : 0;
+  }
   const double asp = 16.0 / 9.0;
   const Cam cams[4] = {
       cam_init({13, 2, 3}, {0, 0, 0}, {0, 1, 0}, 20.0, asp, 0.1, 10.0, 0.0, 1.0),   // the cover camera
@@ -168,14 +296,14 @@ int main(int argc, char** argv) {
   Totals T;
   for (const Cam& c : cams)
     for (const auto& fr : frames)
-      for (const auto& sp : splits) run_frame(S, c, fr[0], fr[1], sp[0], sp[1], true, T);
+      for (const auto& sp : splits)
+        run_frame(S, c, fr[0], fr[1], sp[0], sp[1], (fr[1] - sp[0] + sp[1] - 1) / sp[1], true, false, T);
   printf("rays %llu hits %llu violations %llu\n", T.rays, T.hits, T.viol);
   if (argc > 2 && std::strcmp(argv[2], "popcount") == 0) {
     Totals P;
-    run_frame(S, cams[0], 1200, 675, 0, 1, false, P);
-    int narrow = 0;
-    for (const auto& s : S) narrow += std::fabs(s.r) < 100.0;
-    printf("mean_popcount %.3f of %d narrow spheres over %llu tiles\n", (double)P.pop / (double)P.tiles, narrow, P.tiles);
+    run_frame(S, cams[0], 1200, 675, 0, 1, 675, false, false, P);
+    printf("mean_popcount %.3f of %llu narrow spheres over %llu tiles\n", (double)P.pop / (double)P.tiles,
+           P.pairs / P.tiles, P.tiles);
   }
   return T.viol ? 1 : 0;
 }

@@ -2,11 +2,13 @@
 resolves its camera ray itself from the mask of its tile (csrc/rtw_beam.hpp)
 and shades that hit in the same iteration.  Every case is bit-identical
 (max|d| = 0) to oracle Tier B, as the rotated loop is, and the counts pass
-proves which loop ran (primary_rounds)."""
+proves which loop ran (primary_rounds) and that the device's tile masks are
+the host's (primary_mask_popcount == the host evaluation of rtw_beam.hpp).
+tests/test_gpu_primary_fuzz.py has the cameras and scenes away from the cover's."""
 import numpy as np
 import pytest
 
-from helpers import diff_stats, to_oracle_camera, to_oracle_scene
+from helpers import diff_stats, host_masks, to_oracle_camera, to_oracle_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -20,12 +22,17 @@ def cover(rtw, oracle):
 
 
 def check(rtw, oracle, sph, mats, osc, cam, what, primary=True, **kw):
-    """GPU f64 megakernel == oracle Tier B on every channel; the loop that ran."""
+    """GPU f64 megakernel == oracle Tier B on every channel; the loop that ran; and, when it was the
+    primary-first loop, the kernel's mask popcount (one per fetched batch = (tile, chunk)) == the host
+    evaluation of rtw_beam.hpp over the tiles, times the chunks."""
     from rtw_amd.device import TorchRenderer
-    g = rtw.render(cam, sph, mats, rtw.make_params(**kw))
+    params = rtw.make_params(**kw)
+    g = rtw.render(cam, sph, mats, params)
     okw = dict(kw)
     w, h, spp = okw.pop("width"), okw.pop("height"), okw.pop("spp")
     depth = okw.pop("max_depth", 50)
+    if "background" in okw:
+        okw["bg"] = okw.pop("background")
     o, _ = oracle.render_tier_b(osc, to_oracle_camera(oracle, cam), w, h, spp, depth=depth, **okw)
     d = diff_stats(g, o)
     print(what, d)
@@ -37,7 +44,12 @@ def check(rtw, oracle, sph, mats, osc, cam, what, primary=True, **kw):
         # every sample's camera ray went through the primary phase; the ones that missed ended there
         assert st["primary_rounds"] > 0 and st["primary_idle_lanes"] < st["samples"], st
         assert st["primary_mask_popcount"] > 0, st  # some tile's camera rays can hit a narrow sphere
-    elif not primary:
+    if primary:
+        chunk =min(params.chunk or rtw.DEFAULT_CHUNK, spp)
+        hm = host_masks(sph, cam, params)
+        print(what, hm)
+        assert st["primary_mask_popcount"] == -(-spp // chunk) * hm["popcount"], (st, hm)
+    else:
         assert st["primary_rounds"] == 0 and st["primary_idle_lanes"] == 0 and st["primary_mask_popcount"] == 0, st
     return g, st
 
