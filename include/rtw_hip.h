@@ -660,6 +660,89 @@ int rtw_accum_denoise_device(rtw_accum a, const rtw_guide *d_guides, const rtw_d
                              void *workspace, size_t workspace_bytes, uint8_t *d_rgb, float *d_mean,
                              void *stream);
 
+/* ============================================================ ray queries ===
+ *   The closest hit, or the occlusion, of rays the CALLER
+ * supplies, over an uploaded world or scene: picking the primitive under a
+ * pixel, visibility and shadow tests, ambient occlusion, an integrator of the
+ * caller's own.  New symbols only: a render without these calls is untouched.
+ *
+ * Closest hit.  The answer is HittableList.hit's (hittable.zig:231-244) over
+ * the flattened list: the minimal accepted root in [t_min, t_max]; a root equal
+ * to the current closest is accepted, so among equal roots the later list index
+ * wins.
+ * Hit record.  The reference's HitRecord: p, and the normal facing the ray;
+ * front = 1 if the outward normal opposes the ray; u, v = getSphereUv for a
+ * static sphere, 0, 0 for a moving sphere, (x - a0) / (a1 - a0),
+ * (y - b0) / (b1 - b0) for a rect; Translate / RotateY wrappers applied back in
+ * the reference's order; prim = list index + 1 as in rtw_guide (the sphere
+ * index + 1 for a scene).  A miss: all 80 bytes 0.
+ * Occlusion.  d_occluded[i] = 1 iff the closest-hit query of ray i would hit,
+ * else 0; the kernel stops a ray at its first accepted root (the answer does
+ * not depend on the order).
+ * Arithmetic.  f64, one IEEE operation per reference operation, as everywhere
+ * in this library; every field of a record equals the oracle's rw_hit
+ * (oracle/rtw_world.h) bit for bit.
+ * Input domain.  Components finite, dir != 0, time finite, t_min <= t_max,
+ * t_max may be +inf; direction components that are exactly 0 are in the
+ * domain, and a NaN root sends the ray through the reference's sequential loop
+ * as in a render.  (A ray whose time lies outside [0, 1] on a world whose BVH
+ * holds moving spheres takes that loop too: the boxes cover those times only.)
+ * The BVH's box tests (not the primitive tests) give a direction component that
+ * is 0, or smaller than 2^-60 of the largest, that magnitude: the slab
+ * arithmetic divides by it, and the shift stays far inside the boxes' margin.
+ * A ray that lies in a rect's plane (the reference's 0/0, whose answer depends
+ * on the list order) is guaranteed the reference's record only in worlds
+ * without a BVH: a walk meets that rect only where the ray meets its box.
+ * Outside the domain the record's contents are unspecified, but no access
+ * leaves the tables or the output buffers: the stack depth bounds every walk.
+ * Launch.  The _device entries are asynchronous on `stream`: one kernel launch,
+ * no allocation, no synchronisation, no atomics on the outputs; the same input
+ * gives the same bytes.  n == 0 returns RTW_OK and launches nothing.
+ * RTW_EINVAL for null pointers, d_rays / d_hits not 8-byte aligned, or
+ * n > 2^31.  The world or scene must live on the current device.  Capture into
+ * a graph is not tested and not promised.
+ * Traversal (opts->traversal, opts NULL = all 0): UNION and LANE are forced as
+ * in rtw_params.world_traversal; a world that cannot walk per lane (not a
+ * sphere world, or no BVH) takes the union walk or the linear loop —
+ * rtw_world_query_info says which.  AUTO: see RTW_QUERY_LANE_NODES. */
+typedef struct { double origin[3], dir[3]; double time, t_min, t_max; } rtw_ray;            /* 72 bytes */
+typedef struct { double t, p[3], normal[3], u, v; uint32_t prim, front; } rtw_hit;          /* 80 bytes */
+typedef struct {
+  uint32_t traversal;  /* rtw_world_traversal, 0 = AUTO */
+  uint32_t flags;      /* 0 */
+} rtw_query_opts;
+#define RTW_QUERY_MAX_RAYS (1ull << 31)
+/* AUTO: per lane for sphere worlds whose BVH has at least this many nodes, else
+ * the union walk — rtw_params.world_traversal's rule, which the measurement on
+ * incoherent rays (one bounce per hit of a frame's feature rays; tools/
+ * query_bench.py, profiles/r13/query.txt) confirms at both ends: the globe
+ * (9,981 nodes) 0.1723 ms per lane against 0.1930 ms union for 651,951 rays,
+ * scene 1 (23 nodes) 0.0452 ms union against 0.0645 ms per lane for 810,089. */
+#define RTW_QUERY_LANE_NODES 256u
+
+/* Host helper: the feature ray of pixel (x, image row y, top first) exactly as
+ * the guides define it ("Guides" above: s, t at the pixel centre, lens offset
+ * 0, mid-shutter time), t_min = 0.001, t_max = +inf.  RTW_EINVAL for null
+ * pointers, width or height < 2, x >= width or y >= height. */
+int rtw_pixel_ray(const rtw_camera *cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, rtw_ray *out);
+
+int rtw_world_trace_device(rtw_world w, const rtw_ray *d_rays, uint64_t n, const rtw_query_opts *opts,
+                           rtw_hit *d_hits, void *stream);
+int rtw_world_occluded_device(rtw_world w, const rtw_ray *d_rays, uint64_t n, const rtw_query_opts *opts,
+                              uint8_t *d_occluded, void *stream);
+int rtw_scene_trace_device(rtw_scene s, const rtw_ray *d_rays, uint64_t n, rtw_hit *d_hits, void *stream);
+int rtw_scene_occluded_device(rtw_scene s, const rtw_ray *d_rays, uint64_t n, uint8_t *d_occluded, void *stream);
+/* HOST buffers, synchronous (allocate, copy, trace, copy back): for one-off
+ * queries such as a pick. */
+int rtw_world_trace(rtw_world w, const rtw_ray *rays, uint64_t n, const rtw_query_opts *opts, rtw_hit *hits_out);
+int rtw_scene_trace(rtw_scene s, const rtw_ray *rays, uint64_t n, rtw_hit *hits_out);
+/* How a query would launch on this world (current device = the world's) at its
+ * largest: info_out[4] = {traversal after AUTO and the world's limits (LANE,
+ * UNION or LINEAR), kernel feature set, workgroups of a batch that fills the
+ * device (a smaller batch launches ceil(n / 256)), dynamic LDS bytes per
+ * workgroup}. */
+int rtw_world_query_info(rtw_world w, const rtw_query_opts *opts, uint32_t info_out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -463,6 +463,44 @@ int rtw_scene_guides_device(rtw_scene sc, const rtw_camera* cam, const rtw_param
   return RTW_OK;
 }
 
+// Ray queries over a scene (rtw_hip.h "ray queries"; rtw_query.hip scene_query_kernel).
+static int scene_query(const char* who, rtw_scene sc, const rtw_ray* d_rays, uint64_t n, void* d_out, bool occlusion,
+                       void* stream) {
+  std::string msg;
+  const int st = rtwq::check_batch(who, sc, d_rays, n, nullptr, d_out, occlusion ? 1u : 8u, msg);
+  if (st != RTW_OK) return rtw_fail(st, "%s", msg.c_str());
+  if (n == 0) return RTW_OK;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != sc->device) return rtw_fail(RTW_EINVAL, "%s: scene lives on device %d, current is %d", who, sc->device, dev);
+  rtwk::SceneQueryArgs a;
+  a.sc = sc->v64;
+  a.rays = reinterpret_cast<const double*>(d_rays);
+  a.out = d_out;
+  a.n = (uint32_t)n;
+  const uint32_t grid = rtwq::grid(n, (uint32_t)device_cus(dev), 8u);
+  const hipError_t e = rtwk::launch_scene_query(a, grid, occlusion, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+  return RTW_OK;
+}
+int rtw_scene_trace_device(rtw_scene sc, const rtw_ray* d_rays, uint64_t n, rtw_hit* d_hits, void* stream) {
+  return scene_query("rtw_scene_trace_device", sc, d_rays, n, d_hits, false, stream);
+}
+int rtw_scene_occluded_device(rtw_scene sc, const rtw_ray* d_rays, uint64_t n, uint8_t* d_occluded, void* stream) {
+  return scene_query("rtw_scene_occluded_device", sc, d_rays, n, d_occluded, true, stream);
+}
+int rtw_scene_trace(rtw_scene sc, const rtw_ray* rays, uint64_t n, rtw_hit* hits_out) {
+  std::string msg;
+  const int st = rtwq::check_batch("rtw_scene_trace", sc, rays, n, nullptr, hits_out, 8u, msg);
+  if (st != RTW_OK) return rtw_fail(st, "%s", msg.c_str());
+  if (n == 0) return RTW_OK;
+  RtwQueryBuffers b;
+  int rc = b.upload("rtw_scene_trace", rays, n);
+  if (rc == RTW_OK) rc = rtw_scene_trace_device(sc, b.d_rays, n, b.d_hits, nullptr);
+  if (rc == RTW_OK) rc = b.download("rtw_scene_trace", hits_out, n);
+  return rc;
+}
+
 // The statistics pass: one render in counting mode, the kernels' 32 statistics
 // words copied back (rtw_hip.h RTW_STAT_*; words 16.. are the diagnostic
 // build's phase stamps).

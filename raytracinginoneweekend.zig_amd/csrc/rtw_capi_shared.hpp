@@ -11,6 +11,7 @@
 #include "rtw_hip.h"
 #include "rtw_internal.hpp"
 #include "rtw_plan.hpp"
+#include "rtw_query_plan.hpp"
 
 struct rtw_timer_s {
   hipEvent_t start = nullptr, stop = nullptr;
@@ -125,3 +126,31 @@ int rtw_accum_pass_fold(rtw_accum a, const rtw_params* pp, unsigned char* ws, hi
 // The take's map for a pass of `a`: empty for a never-masked accumulator; else the device tile list and
 // masks and the active tile count, after waiting for the previous active-set update (one 8-byte readback).
 int rtw_accum_pass_map(rtw_accum a, RtwPassMap* map);
+
+// The device buffers of a host-form ray query (rtw_world_trace, rtw_scene_trace): the rays up, the records back
+// after waiting for the device.  The destructor frees.
+struct RtwQueryBuffers {
+  rtw_ray* d_rays = nullptr;
+  rtw_hit* d_hits = nullptr;
+  RtwQueryBuffers() = default;
+  RtwQueryBuffers(const RtwQueryBuffers&) = delete;
+  RtwQueryBuffers& operator=(const RtwQueryBuffers&) = delete;
+  ~RtwQueryBuffers() {
+    if (d_rays) (void)hipFree(d_rays);
+    if (d_hits) (void)hipFree(d_hits);
+  }
+  int upload(const char* who, const rtw_ray* rays, uint64_t n) {
+    if (hipMalloc(reinterpret_cast<void**>(&d_rays), n * sizeof(rtw_ray)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d_hits), n * sizeof(rtw_hit)) != hipSuccess)
+      return rtw_fail(RTW_ENOMEM, "%s: device buffers for %llu rays", who, (unsigned long long)n);
+    if (hipMemcpy(d_rays, rays, n * sizeof(rtw_ray), hipMemcpyHostToDevice) != hipSuccess)
+      return rtw_fail(RTW_EHIP, "%s: copy of the rays failed", who);
+    return RTW_OK;
+  }
+  int download(const char* who, rtw_hit* hits_out, uint64_t n) {
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(hits_out, d_hits, n * sizeof(rtw_hit), hipMemcpyDeviceToHost) != hipSuccess)
+      return rtw_fail(RTW_EHIP, "%s: the query failed on the device", who);
+    return RTW_OK;
+  }
+};

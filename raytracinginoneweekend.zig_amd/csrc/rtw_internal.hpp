@@ -352,4 +352,33 @@ struct WorldGuideArgs {
 hipError_t launch_scene_guides(const SceneGuideArgs& a, hipStream_t s);
 hipError_t launch_world_guides(const WorldGuideArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------ ray queries --
+// rtw_query.hip (rtw_hip.h "ray queries"): closest hit or
+// occlusion of n caller-supplied rays, one ray per lane.  rays: n x rtw_ray
+// (9 f64); out: n x rtw_hit (10 x 8 bytes) or n bytes (occlusion).
+constexpr int kQueryBlock = 256;
+struct WorldQueryArgs {
+  WorldView w;
+  const double* rays;
+  void* out;
+  uint32_t n;           // <= 2^31
+  uint32_t lane_yield;  // per-lane walk: a phase pauses once fewer lanes than this still walk (while rays remain)
+  uint32_t seq_times;   // 1: a BVH over moving spheres (its boxes cover shutter times [0, 1]): a ray of another
+                        // time takes the reference's sequential loop
+  double reach;         // max |coordinate| of the world's box: the BVH margin of a ray is bvh_margin's with
+                        // the ray's own origin (rtw_world_capi.hip)
+};
+struct SceneQueryArgs {
+  SceneView<double> sc;
+  const double* rays;
+  void* out;
+  uint32_t n;
+};
+// fs: the query kernel's feature set — kFeatAll (15) for the linear loop and the union walk, a per-lane
+// sphere set (world_feature_set with lane) for the per-lane walk.
+hipError_t launch_world_query(const WorldQueryArgs& a, uint32_t grid, int fs, bool occlusion, hipStream_t s);
+hipError_t launch_scene_query(const SceneQueryArgs& a, uint32_t grid, bool occlusion, hipStream_t s);
+size_t query_lds_bytes(int fs);
+int query_blocks_per_cu(int fs, bool occlusion);
+
 }  // namespace rtwk

@@ -8,6 +8,15 @@
 //              [--pass-spp N [--preview-dir DIR] [--max-noise X]
 //                            [--pixel-noise X [--min-spp N] [--spp-map FILE]]]
 //              [--denoise [--denoise-levels N] [--denoise-spatial]]
+//              [--pick X,Y] [--focus-at X,Y]
+// --pick X,Y traces the feature ray of pixel (X, image row Y) (rtw_pixel_ray,
+// rtw_world_trace) and prints one line,
+//   pick x=.. y=.. prim=.. t=.. p=..,..,.. front=.. material=<kind>   (or: pick x=.. y=.. miss)
+// with prim = the primitive's list index + 1, then exits without rendering.
+// --focus-at X,Y renders with the camera focused on what that pixel shows: the
+// focus distance is the depth of the pixel's hit along the view axis,
+// dot(p - look_from, unit(look_at - look_from)), printed as focus_dist=..
+// before the render; a pixel whose ray misses is an error.
 // --pass-spp N renders the frame progressively, N samples per pass (a multiple
 // of the chunk): the same --out bytes as without it.  --preview-dir DIR writes
 // the image after every pass to DIR/pass_NNNN.ppm; --max-noise X stops once the
@@ -32,6 +41,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,6 +54,17 @@ static double parse_aspect(const char* s) {
   const char* c = std::strchr(s, ':');
   if (c) return std::atof(s) / std::atof(c + 1);
   return std::atof(s);
+}
+
+static bool parse_pixel(const char* s, uint32_t xy[2]) {
+  char* e = nullptr;
+  const unsigned long x = std::strtoul(s, &e, 10);
+  if (e == s || *e != ',') return false;
+  const char* s2 = e + 1;
+  const unsigned long y = std::strtoul(s2, &e, 10);
+  if (e == s2 || *e != 0) return false;
+  xy[0] = (uint32_t)x, xy[1] = (uint32_t)y;
+  return true;
 }
 
 static uint32_t be32(const unsigned char* p) { return (uint32_t)p[0] << 24 | p[1] << 16 | p[2] << 8 | p[3]; }
@@ -132,6 +153,8 @@ int main(int argc, char** argv) {
   std::string out = "out.ppm", image_path, preview_dir, spp_map;
   bool denoise = false, denoise_spatial = false;
   uint32_t denoise_levels = 0;
+  bool pick = false, focus_at = false;
+  uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0};
   for (int i = 1; i < argc; i += 2) {
     const std::string k = argv[i];
     if (k == "--denoise" || k == "--denoise-spatial") {  // (the options without a value)
@@ -159,6 +182,14 @@ int main(int argc, char** argv) {
     else if (k == "--min-spp") min_spp = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--spp-map") spp_map = v;
     else if (k == "--denoise-levels") denoise_levels = (uint32_t)std::strtoul(v, nullptr, 10);
+    else if (k == "--pick" || k == "--focus-at") {
+      const bool is_pick = k == "--pick";
+      if (!parse_pixel(v, is_pick ? pick_xy : focus_xy)) {
+        std::fprintf(stderr, "%s needs X,Y\n", k.c_str());
+        return 2;
+      }
+      (is_pick ? pick : focus_at) = true;
+    }
     else {
       std::fprintf(stderr, "unknown option %s\n", k.c_str());
       return 2;
@@ -182,10 +213,72 @@ int main(int argc, char** argv) {
     const uint32_t W = width ? width : st.width;
     const uint32_t H = (width || aspect > 0) ? rtw::imageHeight(W, asp) : st.height;
     const uint32_t S = spp ? spp : st.spp;
-    const rtw::Camera cam = rtw::Camera::init({st.look_from[0], st.look_from[1], st.look_from[2]},
-                                              {st.look_at[0], st.look_at[1], st.look_at[2]}, {0, 1, 0}, st.vfov, asp,
-                                              st.aperture, 10.0, 0, 1);  // main.zig:366-376
-    rtw::Random rng = rtw::Random::init(seed);                           // main.zig:300-301
+    auto camera = [&](double focus_dist) {
+      return rtw::Camera::init({st.look_from[0], st.look_from[1], st.look_from[2]},
+                               {st.look_at[0], st.look_at[1], st.look_at[2]}, {0, 1, 0}, st.vfov, asp, st.aperture,
+                               focus_dist, 0, 1);  // main.zig:366-376
+    };
+    rtw::Camera cam = camera(10.0);
+    rtw::Random rng = rtw::Random::init(seed);  // main.zig:300-301
+    std::shared_ptr<rtw::Image> earth;
+    if (scene == 4 || scene == 7) {
+      if (image_path.empty()) throw rtw::Error(RTW_EINVAL, "scenes 4 and 7 need --image assets/sekaichizu.png");
+      earth = loadPNG(image_path);
+    }
+    rtw::Hittable world;
+    switch (scene) {
+      case 1: world = rtw::generateRandomScene(rng); break;
+      case 2: world = rtw::generateTwoSpheres(rng); break;
+      case 3: world = rtw::generateTwoPerlinSpheres(rng); break;
+      case 4: world = rtw::generateEarthScene(earth); break;
+      case 5: world = rtw::generateSimpleLightScene(rng); break;
+      case 6: world = rtw::generateCornellBox(); break;
+      case 7: world = rtw::generateGlobeScene(rng, earth); break;
+      default: throw rtw::Error(RTW_EINVAL, "scene must be 1..7");
+    }
+    if (pick || focus_at) {
+      // The closest hit of the pixel's feature ray (the guides' ray, rtw_hip.h) over the flattened world.
+      const rtw::FlatWorld fw = rtw::flattenWorld(world);
+      const rtw_world_desc desc = fw.desc();
+      auto trace_pixel = [&](const uint32_t xy[2], rtw_hit& h) {
+        const rtw_camera c = cam.to_c();
+        rtw_ray r;
+        if (rtw_pixel_ray(&c, W, H, xy[0], xy[1], &r) != RTW_OK)
+          throw rtw::Error(RTW_EINVAL, "pixel " + std::to_string(xy[0]) + "," + std::to_string(xy[1]) + " is outside the " +
+                                           std::to_string(W) + "x" + std::to_string(H) + " image");
+        rtw_world w = nullptr;
+        int rc = rtw_world_create(&desc, 0, &w);
+        if (rc == RTW_OK) rc = rtw_world_trace(w, &r, 1, nullptr, &h);
+        rtw_world_destroy(w);
+        if (rc != RTW_OK) throw rtw::Error(rc, rtw_last_error());
+      };
+      rtw_hit h;
+      if (pick) {
+        trace_pixel(pick_xy, h);
+        if (h.prim == 0) {
+          std::printf("pick x=%u y=%u miss\n", pick_xy[0], pick_xy[1]);
+        } else {
+          static const char* const kinds[] = {"lambert", "metal", "dielectric", "light"};
+          const uint32_t mk = desc.mats[desc.prims[h.prim - 1].mat].kind;
+          std::printf("pick x=%u y=%u prim=%u t=%.17g p=%.17g,%.17g,%.17g front=%u material=%s\n", pick_xy[0], pick_xy[1],
+                      h.prim, h.t, h.p[0], h.p[1], h.p[2], h.front, mk < 4 ? kinds[mk] : "unknown");
+        }
+        return 0;
+      }
+      trace_pixel(focus_xy, h);
+      if (h.prim == 0)
+        throw rtw::Error(RTW_EINVAL, "--focus-at " + std::to_string(focus_xy[0]) + "," + std::to_string(focus_xy[1]) +
+                                         ": the pixel's ray hits nothing to focus on");
+      double a[3], len2 = 0;
+      for (int k = 0; k < 3; ++k) a[k] = st.look_at[k] - st.look_from[k], len2 += a[k] * a[k];
+      const double len = std::sqrt(len2);
+      for (int k = 0; k < 3; ++k) a[k] = a[k] / len;
+      const double f = (h.p[0] - st.look_from[0]) * a[0] + (h.p[1] - st.look_from[1]) * a[1] +
+                       (h.p[2] - st.look_from[2]) * a[2];
+      std::printf("focus_dist=%.17g\n", f);
+      std::fflush(stdout);
+      cam = camera(f);
+    }
     std::vector<uint8_t> rgb((size_t)W * H * 3);
     uint32_t used = S;
     std::vector<uint32_t> counts;
@@ -230,31 +323,15 @@ int main(int argc, char** argv) {
     p.row_begin = 0, p.row_stride = 1, p.row_count = H, p.chunk = chunk, p.device = -1;
     if (scene == 1 && pass_spp) {
       p.precision = precision, p.engine = engine;
-      const rtw::FlatScene fs = rtw::flatten(rtw::generateRandomScene(rng));
+      const rtw::FlatScene fs = rtw::flatten(world);
       rgb = progressive(p, &fs, nullptr);
     } else if (scene == 1) {  // the cover scene: the sphere megakernel (or the wavefront engine)
       rtw::RenderSettings rs;
       rs.width = W, rs.aspect_ratio = asp, rs.samples_per_pixel = S, rs.max_depth = depth, rs.seed = seed;
       rs.precision = precision, rs.chunk = chunk, rs.engine = engine;
       rs.background = {st.background[0], st.background[1], st.background[2]};
-      const rtw::Hittable world = rtw::generateRandomScene(rng);
       rgb = rtw::render(cam, world, rs, H);  // main.zig:378-402
     } else {
-      std::shared_ptr<rtw::Image> earth;
-      if (scene == 4 || scene == 7) {
-        if (image_path.empty()) throw rtw::Error(RTW_EINVAL, "scenes 4 and 7 need --image assets/sekaichizu.png");
-        earth = loadPNG(image_path);
-      }
-      rtw::Hittable world;
-      switch (scene) {
-        case 2: world = rtw::generateTwoSpheres(rng); break;
-        case 3: world = rtw::generateTwoPerlinSpheres(rng); break;
-        case 4: world = rtw::generateEarthScene(earth); break;
-        case 5: world = rtw::generateSimpleLightScene(rng); break;
-        case 6: world = rtw::generateCornellBox(); break;
-        case 7: world = rtw::generateGlobeScene(rng, earth); break;
-        default: throw rtw::Error(RTW_EINVAL, "scene must be 1..7");
-      }
       const rtw::FlatWorld fw = rtw::flattenWorld(world);
       const rtw_world_desc desc = fw.desc();
       p.precision = RTW_PRECISION_F64, p.engine = RTW_ENGINE_MEGAKERNEL;

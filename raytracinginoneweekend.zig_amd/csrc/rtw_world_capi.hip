@@ -357,6 +357,104 @@ int rtw_world_render_counts(rtw_world w, const rtw_camera* cam, const rtw_params
   return st;
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------ ray queries --
+// (rtw_hip.h "ray queries"; kernels: rtw_query.hip; checks, AUTO rule and launch geometry: rtw_query_plan.hpp)
+namespace {
+
+struct QueryCfg {
+  uint32_t traversal;  // rtw_world_traversal: LANE, UNION or LINEAR
+  int fs;              // the query kernel's feature set
+};
+QueryCfg query_cfg(const rtw_world_s* w, const rtw_query_opts* o) {
+  // per lane: sphere worlds (image textures allowed) whose BVH fits the per-lane stack, as world_cfg
+  const bool lane_ok = (w->feat & ~2u) == 0u && w->view.n_nodes > 0 && w->info[2] <= rtwk::kLaneStack &&
+                       w->info[3] <= rtwk::kMaxLeafPrims && w->view.n_prims + 1u < (1u << rtwk::kTravPosBits);
+  QueryCfg c;
+  c.traversal = rtwq::traversal(o ? o->traversal : 0u, w->view.n_nodes, lane_ok);
+  c.fs = c.traversal == RTW_WORLD_TRAVERSAL_LANE ? rtwk::world_feature_set(w->feat, true, w->packed) : 15;
+  return c;
+}
+int query_bpc(int fs, bool occlusion) {  // resident workgroups per CU, asked once per kernel
+  static std::mutex mu;
+  static int cache[64][2] = {};
+  std::lock_guard<std::mutex> lk(mu);
+  int& e = cache[fs & 63][occlusion ? 1 : 0];
+  if (e == 0) e = rtwk::query_blocks_per_cu(fs, occlusion);
+  return e;
+}
+
+int world_query(const char* who, rtw_world w, const rtw_ray* d_rays, uint64_t n, const rtw_query_opts* opts,
+                void* d_out, bool occlusion, hipStream_t stream) {
+  std::string msg;
+  const int st = rtwq::check_batch(who, w, d_rays, n, opts, d_out, occlusion ? 1u : 8u, msg);
+  if (st != RTW_OK) return rtw_fail(st, "%s", msg.c_str());
+  if (n == 0) return RTW_OK;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != w->device) return rtw_fail(RTW_EINVAL, "%s: world lives on device %d, current is %d", who, w->device, dev);
+  const QueryCfg c = query_cfg(w, opts);
+  rtwk::WorldQueryArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.w = w->view;
+  a.rays = reinterpret_cast<const double*>(d_rays);
+  a.out = d_out;
+  a.n = (uint32_t)n;
+  a.lane_yield = kLaneYield;
+  a.seq_times = (w->has_moving && w->view.n_nodes) ? 1u : 0u;
+  for (int k = 0; k < 3; ++k) {
+    if (std::isfinite(w->bounds_lo[k])) a.reach = std::max(a.reach, std::fabs(w->bounds_lo[k]));
+    if (std::isfinite(w->bounds_hi[k])) a.reach = std::max(a.reach, std::fabs(w->bounds_hi[k]));
+  }
+  const uint32_t grid = rtwq::grid(n, (uint32_t)rtw_device_cus(dev), (uint32_t)query_bpc(c.fs, occlusion));
+  const hipError_t e = rtwk::launch_world_query(a, grid, c.fs, occlusion, stream);
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+  return RTW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rtw_world_trace_device(rtw_world w, const rtw_ray* d_rays, uint64_t n, const rtw_query_opts* opts, rtw_hit* d_hits,
+                           void* stream) {
+  return world_query("rtw_world_trace_device", w, d_rays, n, opts, d_hits, false, static_cast<hipStream_t>(stream));
+}
+
+int rtw_world_occluded_device(rtw_world w, const rtw_ray* d_rays, uint64_t n, const rtw_query_opts* opts,
+                              uint8_t* d_occluded, void* stream) {
+  return world_query("rtw_world_occluded_device", w, d_rays, n, opts, d_occluded, true,
+                     static_cast<hipStream_t>(stream));
+}
+
+int rtw_world_trace(rtw_world w, const rtw_ray* rays, uint64_t n, const rtw_query_opts* opts, rtw_hit* hits_out) {
+  std::string msg;
+  const int st = rtwq::check_batch("rtw_world_trace", w, rays, n, opts, hits_out, 8u, msg);
+  if (st != RTW_OK) return rtw_fail(st, "%s", msg.c_str());
+  if (n == 0) return RTW_OK;
+  RtwQueryBuffers b;
+  int rc = b.upload("rtw_world_trace", rays, n);
+  if (rc == RTW_OK) rc = rtw_world_trace_device(w, b.d_rays, n, opts, b.d_hits, nullptr);
+  if (rc == RTW_OK) rc = b.download("rtw_world_trace", hits_out, n);
+  return rc;
+}
+
+int rtw_world_query_info(rtw_world w, const rtw_query_opts* opts, uint32_t info_out[4]) {
+  if (!w || !info_out) return rtw_fail(RTW_EINVAL, "rtw_world_query_info: world/info is NULL");
+  if (opts && (opts->traversal > RTW_WORLD_TRAVERSAL_LANE || opts->flags != 0))
+    return rtw_fail(RTW_EINVAL, "rtw_world_query_info: opts.traversal %u / flags %u", opts->traversal, opts->flags);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev != w->device)
+    return rtw_fail(RTW_EINVAL, "rtw_world_query_info: the world's device must be current");
+  const QueryCfg c = query_cfg(w, opts);
+  info_out[0] = c.traversal;
+  info_out[1] = (uint32_t)c.fs;
+  info_out[2] = rtwq::grid(RTW_QUERY_MAX_RAYS, (uint32_t)rtw_device_cus(dev), (uint32_t)query_bpc(c.fs, false));
+  info_out[3] = (uint32_t)rtwk::query_lds_bytes(c.fs);
+  return RTW_OK;
+}
+
 int rtw_world_render(const rtw_camera* cam, const rtw_world_desc* desc, const rtw_params* p, uint8_t* rgb_out,
                      float* mean_out) {
   if (!cam || !desc || !rgb_out) return rtw_fail(RTW_EINVAL, "camera/desc/rgb_out is NULL");

@@ -89,6 +89,34 @@ VAR_UNKNOWN, VAR_EMPTY = -1.0, -2.0  # rtw_hip.h RTW_VAR_*
 DENOISE_NO_COLOR, DENOISE_DIRECT, DENOISE_SPATIAL_VAR = 1, 2, 4  # rtw_denoise_opts.flags
 
 
+class Ray(C.Structure):
+    """rtw_ray: a caller-supplied ray of a query (72 bytes)."""
+    _fields_ = [("origin", C.c_double * 3), ("dir", C.c_double * 3), ("time", C.c_double), ("t_min", C.c_double),
+                ("t_max", C.c_double)]
+
+
+class Hit(C.Structure):
+    """rtw_hit: the closest hit's record (80 bytes; a miss is all zero, prim = list index + 1)."""
+    _fields_ = [("t", C.c_double), ("p", C.c_double * 3), ("normal", C.c_double * 3), ("u", C.c_double),
+                ("v", C.c_double), ("prim", C.c_uint32), ("front", C.c_uint32)]
+
+
+class QueryOpts(C.Structure):
+    """rtw_query_opts: traversal (WORLD_TRAVERSAL, 0 = auto), flags (0)."""
+    _fields_ = [("traversal", C.c_uint32), ("flags", C.c_uint32)]
+
+
+RAY_DTYPE = np.dtype([("origin", np.float64, 3), ("dir", np.float64, 3), ("time", np.float64),
+                      ("t_min", np.float64), ("t_max", np.float64)])
+HIT_DTYPE = np.dtype([("t", np.float64), ("p", np.float64, 3), ("normal", np.float64, 3), ("u", np.float64),
+                      ("v", np.float64), ("prim", np.uint32), ("front", np.uint32)])
+QUERY_MAX_RAYS = 1 << 31  # rtw_hip.h RTW_QUERY_MAX_RAYS
+
+
+def query_opts(traversal="auto") -> QueryOpts:
+    return QueryOpts(WORLD_TRAVERSAL[traversal] if isinstance(traversal, str) else int(traversal), 0)
+
+
 class DenoiseOpts(C.Structure):
     """rtw_denoise_opts: every field 0 = its default."""
     _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_double), ("sigma_normal", C.c_double),
@@ -191,6 +219,15 @@ def lib() -> C.CDLL:
         L.rtw_accum_denoise_workspace_bytes.argtypes = [C.c_void_p, P(DenoiseOpts)]
         L.rtw_accum_denoise_device.argtypes = [C.c_void_p, C.c_void_p, P(DenoiseOpts), C.c_void_p, C.c_size_t,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "rtw_world_trace_device"):  # ray queries (an older A/B build has none)
+        L.rtw_pixel_ray.argtypes = [P(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(Ray)]
+        for f in (L.rtw_world_trace_device, L.rtw_world_occluded_device):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, P(QueryOpts), C.c_void_p, C.c_void_p]
+        for f in (L.rtw_scene_trace_device, L.rtw_scene_occluded_device):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.rtw_world_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, P(QueryOpts), C.c_void_p]
+        L.rtw_scene_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.rtw_world_query_info.argtypes = [C.c_void_p, P(QueryOpts), C.c_uint32 * 4]
     _lib = L
     return L
 
@@ -231,6 +268,16 @@ def cover_camera(aspect: float) -> Camera:
 
 def image_height(width: int, aspect: float) -> int:
     return int(lib().rtw_image_height(width, aspect))
+
+
+def pixel_ray(cam: Camera, width: int, height: int, x: int, y: int) -> Ray:
+    """The feature ray of pixel (x, image row y) as the guides define it (rtw_pixel_ray):
+    pixel centre, no lens offset, mid-shutter time, t_min 0.001, t_max inf."""
+    r = Ray()
+    st = lib().rtw_pixel_ray(C.byref(cam), width, height, x, y, C.byref(r))
+    if st != RTW_OK:
+        raise RtwError(st, f"rtw_pixel_ray: pixel ({x}, {y}) of {width}x{height}")
+    return r
 
 
 def cover_scene(seed: int = 42):
@@ -351,6 +398,24 @@ class DeviceScene:
         records (32 bytes each) into device memory, asynchronous on `stream`."""
         _check(lib().rtw_scene_guides_device(self.h, C.byref(cam), C.byref(params), C.c_void_p(guides_ptr),
                                              C.c_void_p(stream) if stream else None))
+
+    def trace(self, rays_ptr: int, n: int, hits_ptr: int, stream: int | None = None):
+        """Closest hits of n rtw_ray records in device memory into n rtw_hit records
+        (rtw_scene_trace_device), asynchronous on `stream`; prim = sphere index + 1."""
+        _check(lib().rtw_scene_trace_device(self.h, C.c_void_p(rays_ptr), n, C.c_void_p(hits_ptr),
+                                            C.c_void_p(stream) if stream else None))
+
+    def occluded(self, rays_ptr: int, n: int, out_ptr: int, stream: int | None = None):
+        """One byte per ray, 1 where trace() would hit (rtw_scene_occluded_device)."""
+        _check(lib().rtw_scene_occluded_device(self.h, C.c_void_p(rays_ptr), n, C.c_void_p(out_ptr),
+                                               C.c_void_p(stream) if stream else None))
+
+    def trace_host(self, rays) -> np.ndarray:
+        """rtw_scene_trace: rays (n,) RAY_DTYPE on the host -> hits (n,) HIT_DTYPE, synchronous."""
+        r = np.ascontiguousarray(rays, RAY_DTYPE)
+        out = np.zeros(r.shape, HIT_DTYPE)
+        _check(lib().rtw_scene_trace(self.h, r.ctypes.data, r.size, out.ctypes.data))
+        return out
 
     def counts(self, cam: Camera, params: Params, workspace_ptr: int, workspace_bytes_: int) -> dict:
         out = (C.c_uint64 * 6)()

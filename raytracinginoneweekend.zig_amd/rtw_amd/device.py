@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import torch
 
-from . import Accumulator, Camera, DeviceScene, Params, Timer, workspace_bytes
+from . import Accumulator, Camera, DeviceScene, Params, QueryOpts, Timer, workspace_bytes
 
 
 class TorchRenderer:
@@ -173,3 +173,64 @@ class TorchAccumulator:
 
     def close(self):
         self.acc.close()
+
+
+class TorchTracer:
+    """Ray queries on torch tensors (rtw_hip.h "ray queries"): closest hits and occlusion of
+    caller-supplied rays over a DeviceScene or a world.DeviceWorld of the current device,
+    launched on torch's current HIP stream.
+
+        tr = TorchTracer(world)
+        hit = tr.trace(origins, dirs)          # (N, 3) float64 device tensors
+        lit = ~tr.occluded(hit["p"], to_light, t_max=1.0)
+    """
+
+    def __init__(self, target, device: int | torch.device | None = None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("no GPU visible: the rtw query path has no CPU fallback")
+        if device is None:
+            device = torch.cuda.current_device()
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self.target = target
+        self.is_world = not isinstance(target, DeviceScene)
+
+    def pack(self, origins, dirs, time=0.5, t_min=0.001, t_max=float("inf")) -> torch.Tensor:
+        """The (N, 9) float64 ray tensor (rtw_ray records) from (N, 3) origins and directions and
+        scalars or (N,) tensors of time, t_min, t_max — torch ops on the current stream."""
+        o = torch.as_tensor(origins, dtype=torch.float64, device=self.device)
+        d = torch.as_tensor(dirs, dtype=torch.float64, device=self.device)
+        if o.dim() != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError("origins and dirs must both be (N, 3)")
+        rays = torch.empty((o.shape[0], 9), dtype=torch.float64, device=self.device)
+        rays[:, 0:3] = o
+        rays[:, 3:6] = d
+        for col, v in ((6, time), (7, t_min), (8, t_max)):
+            rays[:, col] = torch.as_tensor(v, dtype=torch.float64, device=self.device) if torch.is_tensor(v) else float(v)
+        return rays
+
+    def _launch(self, f, rays, out, opts):
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if rays.shape[0] == 0:
+            return
+        if self.is_world:
+            f(rays.data_ptr(), rays.shape[0], out.data_ptr(), opts, stream)
+        else:
+            f(rays.data_ptr(), rays.shape[0], out.data_ptr(), stream)
+
+    def trace(self, origins, dirs, time=0.5, t_min=0.001, t_max=float("inf"), opts: QueryOpts | None = None) -> dict:
+        """Closest hits: a dict of tensors viewing one (N, 10) float64 record buffer — t (N,), p (N, 3),
+        normal (N, 3), uv (N, 2) — and prim (N,) int64 (the list index, -1 for a miss), front (N,) bool."""
+        rays = self.pack(origins, dirs, time, t_min, t_max)
+        rec = torch.empty((rays.shape[0], 10), dtype=torch.float64, device=self.device)
+        self._launch(self.target.trace, rays, rec, opts)
+        words = rec.view(torch.int32)[:, 18:20]  # {prim, front}: the record's last 8 bytes
+        return {"t": rec[:, 0], "p": rec[:, 1:4], "normal": rec[:, 4:7], "uv": rec[:, 7:9],
+                "prim": words[:, 0].to(torch.int64) - 1, "front": words[:, 1] != 0, "records": rec}
+
+    def occluded(self, origins, dirs, time=0.5, t_min=0.001, t_max=float("inf"),
+                 opts: QueryOpts | None = None) -> torch.Tensor:
+        """(N,) bool: whether trace() of the same rays would hit."""
+        rays = self.pack(origins, dirs, time, t_min, t_max)
+        out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=self.device)
+        self._launch(self.target.occluded, rays, out, opts)
+        return out != 0

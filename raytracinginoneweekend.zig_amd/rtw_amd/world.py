@@ -19,7 +19,7 @@ import zlib
 
 import numpy as np
 
-from . import RTW_EINVAL, Camera, Params, RtwError, Timer, _check, camera_init, lib
+from . import HIT_DTYPE, RAY_DTYPE, RTW_EINVAL, Camera, Params, QueryOpts, RtwError, Timer, _check, camera_init, lib
 
 PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_XY_RECT, PRIM_XZ_RECT, PRIM_YZ_RECT = 0, 1, 2, 3, 4
 XF_TRANSLATE, XF_ROTATE_Y = 0, 1
@@ -318,6 +318,36 @@ class DeviceWorld:
         _check(_wlib().rtw_world_launch_info(self.h, C.byref(params), out))
         return {"traversal": TRAVERSAL_NAMES.get(int(out[0]), str(out[0])), "feature_set": int(out[1]),
                 "waves": int(out[2]), "blocks_per_cu": int(out[3]), "grid": int(out[4]), "lds_bytes": int(out[5])}
+
+    def trace(self, rays_ptr: int, n: int, hits_ptr: int, opts: QueryOpts | None = None, stream: int | None = None):
+        """Closest hits of n rtw_ray records in device memory into n rtw_hit records
+        (rtw_world_trace_device), asynchronous on `stream`; prim = list index + 1, a miss all zero."""
+        _check(_wlib().rtw_world_trace_device(self.h, C.c_void_p(rays_ptr), n,
+                                              C.byref(opts) if opts is not None else None, C.c_void_p(hits_ptr),
+                                              C.c_void_p(stream) if stream else None))
+
+    def occluded(self, rays_ptr: int, n: int, out_ptr: int, opts: QueryOpts | None = None,
+                 stream: int | None = None):
+        """One byte per ray, 1 where trace() would hit (rtw_world_occluded_device)."""
+        _check(_wlib().rtw_world_occluded_device(self.h, C.c_void_p(rays_ptr), n,
+                                                 C.byref(opts) if opts is not None else None, C.c_void_p(out_ptr),
+                                                 C.c_void_p(stream) if stream else None))
+
+    def trace_host(self, rays, opts: QueryOpts | None = None) -> np.ndarray:
+        """rtw_world_trace: rays (n,) RAY_DTYPE on the host -> hits (n,) HIT_DTYPE, synchronous."""
+        r = np.ascontiguousarray(rays, RAY_DTYPE)
+        out = np.zeros(r.shape, HIT_DTYPE)
+        _check(_wlib().rtw_world_trace(self.h, r.ctypes.data, r.size, C.byref(opts) if opts is not None else None,
+                                       out.ctypes.data))
+        return out
+
+    def query_info(self, opts: QueryOpts | None = None) -> dict:
+        """rtw_world_query_info: the walk a query runs (after AUTO and the world's limits),
+        its kernel feature set, the workgroups of a device-filling batch, LDS per workgroup."""
+        out = (C.c_uint32 * 4)()
+        _check(_wlib().rtw_world_query_info(self.h, C.byref(opts) if opts is not None else None, out))
+        return {"traversal": TRAVERSAL_NAMES.get(int(out[0]), str(out[0])), "feature_set": int(out[1]),
+                "grid": int(out[2]), "lds_bytes": int(out[3])}
 
     def counts(self, cam: Camera, params: Params, workspace_ptr: int, workspace_bytes_: int) -> dict:
         """rtw_world_render_counts_ex: the counts, the persistent kernel's wave
