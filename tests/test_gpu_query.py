@@ -18,16 +18,12 @@ import numpy as np
 import pytest
 
 import query_helpers as Q
-from helpers import MIXED_CAMERA, MIXED_SIZES, _to_desc, chain_to_world, mixed_bvh_world
+from query_helpers import _assert_records, _trace
 
 pytestmark = pytest.mark.gpu
 
 import torch  # noqa: E402  (device buffers and streams)
 
-SKY = (0.7, 0.8, 1.0)
-GEN_SEED = 5  # mixed_bvh_world's seed (as tests/test_gpu_world_general.py)
-MIXED = {"small": (*MIXED_SIZES["small"], None, False, 100), "small_swap": (*MIXED_SIZES["small"], None, True, 100),
-         "spheres_image": (0, 520, "spheres_image", False, 101)}
 # (world, traversal asked, traversal rtw_world_query_info must report)
 CASES = [("scene6", "auto", "linear"), ("scene6", "lane", "linear"), ("scene5", "auto", "linear"),
          ("scene4", "auto", "linear"), ("scene3", "auto", "linear"),
@@ -43,130 +39,11 @@ def W():
     return world
 
 
-def _pair_rays(W, tables, look_from, rng):
-    """For each coincident-pair class of a mixed world, rays aimed at the pair: from the camera origin and
-    from one unit in front of its surface.  Returns (rows, [(class, later list index, [row indices])])."""
-    prims, xf = tables[0], tables[1]
-    rows, want = [], []
-    for cls in ("pair_rect", "pair_sphere", "pair_face"):
-        idx = [i for i, p in enumerate(prims) if p["cls"] == cls]
-        if not idx:
-            continue
-        first = prims[idx[0]]
-        same = [i for i in idx if (prims[i]["kind"], list(prims[i]["a"]), prims[i]["xform"]) ==
-                (first["kind"], list(first["a"]), first["xform"])]
-        assert len(same) >= 2, cls
-        a = first["a"]
-        if first["kind"] == W.PRIM_SPHERE:
-            c, r = np.array(a[0:3]), a[6]
-            to_cam = np.array(look_from) - c
-            to_cam /= np.sqrt((to_cam * to_cam).sum())
-            centre, front = c + r * to_cam, c + (r + 1.0) * to_cam
-        else:  # an XY rect, facing +z in its object space
-            mid = np.array([(a[0] + a[1]) / 2, (a[2] + a[3]) / 2, a[4]])
-            centre, front = mid, mid + np.array([0.0, 0.0, 1.0])
-            if first["xform"] >= 0:
-                centre, front = chain_to_world(xf[first["xform"]], centre), chain_to_world(xf[first["xform"]], front)
-        mine = []
-        for o in (np.array(look_from, float), front):
-            mine.append(len(rows))
-            rows.append((o, centre - o, float(rng.random()), 0.001, np.inf))
-        want.append((cls, max(same), mine))
-    return rows, want
-
-
-class World:
-    """One world: the device's, the oracle's, the ray set and the oracle's records (computed once, read-only)."""
-
-    def __init__(self, rtw, oracle, W, name):
-        self.name = name
-        self.pairs, extra = [], []
-        if name.startswith("scene"):
-            sid = int(name[5:])
-            img = W.synthetic_world_map() if sid in (4, 7) else None
-            self.built = W.BuiltScene(sid, 42, img)
-            self.desc = self.built.desc
-            self.oracle = oracle.OracleWorld(sid, 42, img)
-            cam = self.built.camera(Q.QW / Q.QH)
-            look_from, seed = tuple(self.built.settings.look_from), 1234 + sid
-            self.moving = [i for i in range(self.desc.n_prims) if self.desc.prims[i].kind == W.PRIM_MOVING_SPHERE]
-            if sid == 6:  # direction components exactly 0, from inside the box; then the ray in the back wall's plane
-                rng = np.random.default_rng(99)
-                for o in ((278.0, 278.0, 10.0), (100.0, 400.0, 300.0), (500.0, 50.0, 540.0)):
-                    for d in ((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (1, 1, 0), (0, 1, 1)):
-                        extra.append((o, tuple(float(x) for x in d), float(rng.random()), 0.001, np.inf))
-                extra.append(((100.0, 100.0, 555.0), (1.0, 0.5, 0.0), 0.5, 0.001, np.inf))
-        else:
-            nb, ns, variant, swap, k = MIXED[name]
-            self.tables = mixed_bvh_world(W, W.earth_map(), nb, ns, GEN_SEED, swap=swap, variant=variant)
-            self.desc, self._keep = _to_desc(W, *self.tables)
-            self.oracle = oracle.TableWorld(*self.tables, background=SKY)
-            m = MIXED_CAMERA
-            cam = rtw.camera_init(m["look_from"], m["look_at"], (0, 1, 0), m["vfov"], Q.QW / Q.QH, m["aperture"],
-                                  m["focus"], 0.0, 1.0)
-            look_from, seed = m["look_from"], 1234 + k
-            self.moving = []
-            extra, self.pairs = _pair_rays(W, self.tables, look_from, np.random.default_rng(7))
-        rays, kinds = Q.ray_set(rtw, self.oracle, cam, look_from, seed)
-        self.n_main = len(rays)
-        if extra:
-            rays = np.concatenate([rays, Q.make_rays(rtw, extra)])
-            kinds = np.concatenate([kinds, np.array(["x"] * len(extra))])
-        self.rays, self.kinds = rays, kinds
-        self.ref = Q.oracle_hits(rtw, self.oracle, rays)
-        self.rays.setflags(write=False)
-        self.ref.setflags(write=False)
-        self._W, self._dev, self._d_rays = W, None, None
-
-    @property
-    def dev(self):
-        if self._dev is None:
-            self._dev = self._W.DeviceWorld(self.desc)
-        return self._dev
-
-    @property
-    def d_rays(self):
-        if self._d_rays is None:
-            self._d_rays = torch.from_numpy(np.frombuffer(self.rays.tobytes(), np.uint8).copy()).cuda()
-        return self._d_rays
-
-
 @pytest.fixture(scope="module")
 def worlds(rtw, oracle, W):
-    cache = {}
-
     def get(name):
-        if name not in cache:
-            cache[name] = World(rtw, oracle, W, name)
-        return cache[name]
+        return Q.get_world(rtw, oracle, W, name)
     return get
-
-
-def _trace(rtw, target, d_rays, n, opts=None, occluded=False, is_world=True):
-    """n rays through the pointer API into a buffer pre-filled with 0xA5, with a 256-byte guard behind
-    the last record (or byte).  Returns (records or bytes, guard)."""
-    size = n * (1 if occluded else 80)
-    buf = torch.full((size + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    f = target.occluded if occluded else target.trace
-    if is_world:
-        f(d_rays.data_ptr(), n, buf.data_ptr(), opts, stream)
-    else:
-        f(d_rays.data_ptr(), n, buf.data_ptr(), stream)
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    out = host[:size].copy()
-    return (out if occluded else out.view(rtw.HIT_DTYPE)), host[size:]
-
-
-def _assert_records(got, ref, where):
-    """Bit for bit, except a record whose oracle root is NaN (a ray in a rect's plane): prim, and t NaN on both sides."""
-    nan = np.isnan(ref["t"])
-    assert (got["prim"] == ref["prim"]).all(), where
-    assert np.isnan(got["t"][nan]).all(), where
-    gw, rw = Q.words(got)[~nan], Q.words(ref)[~nan]
-    bad = np.nonzero((gw != rw).any(axis=1))[0]
-    assert bad.size == 0, (where, bad[:5], got[~nan][bad[:2]], ref[~nan][bad[:2]])
 
 
 def test_ray_sets_cannot_pass_vacuously(worlds):
