@@ -256,7 +256,12 @@ int rtw_render_stats(rtw_scene scene, const rtw_camera *cam, const rtw_params *p
 enum {
   /* megakernel, primary-first loop: the fetched unit batches' tile masks, their popcounts summed
    * (spheres the batch's camera rays are tested against per lane) */
-  RTW_STAT_PRIMARY_MASK_POPCOUNT = 16
+  RTW_STAT_PRIMARY_MASK_POPCOUNT = 16,
+  /* megakernel, primary-first loop, after a wave's unit queue ran dry (its tail): samples a lane traced
+   * for another lane's unit; wave-iterations run in that state; lane-slots of those iterations with no
+   * sample in flight or to start, the lane's own or another lane's.  The last two are counted whether
+   * or not the launch hands samples out. */
+  RTW_STAT_TAIL_HELPED_SAMPLES = 17, RTW_STAT_TAIL_WAVE_ITERS = 18, RTW_STAT_TAIL_IDLE_LANE_ITERS = 19
 };
 int rtw_render_stats_ex(rtw_scene scene, const rtw_camera *cam, const rtw_params *params,
                         void *workspace, size_t workspace_bytes, uint64_t *stats_out, uint32_t n_words);

@@ -60,9 +60,11 @@ uint64_t splitmix_first(uint64_t seed) {  // SplitMix64.init(seed).next()
   return z ^ (z >> 31);
 }
 
+constexpr int kBpcTail = 16;
 struct DevInfo {
   int cus = 0;
-  std::map<std::pair<int, bool>, std::pair<size_t, int>> bpc;  // (precision, masked) -> (lds, blocks per CU)
+  // (precision, masked) -> (lds, blocks per CU); precision + kBpcTail: the same with the tail blocks
+  std::map<std::pair<int, bool>, std::pair<size_t, int>> bpc;
 };
 std::mutex g_dev_mu;
 std::map<int, DevInfo> g_dev;
@@ -77,10 +79,10 @@ int device_cus(int dev) {
   }
   return d.cus;
 }
-int blocks_per_cu(int dev, int prec, size_t lds, bool masked) {
+int blocks_per_cu(int dev, int prec, size_t lds, bool masked, bool tail = false) {
   std::lock_guard<std::mutex> lk(g_dev_mu);
   auto& d = g_dev[dev];
-  auto& e = d.bpc[{prec, masked}];
+  auto& e = d.bpc[{prec + (tail ? kBpcTail : 0), masked}];
   if (e.second == 0 || e.first != lds) e = {lds, rtwk::trace_blocks_per_cu(prec, lds, masked)};
   return e.second;
 }
@@ -291,7 +293,7 @@ uint32_t clusters_usable(const rtw_scene_s* sc, const rtw_camera* cam) {
 template <typename R>
 int launch_engine(const rtwk::SceneView<R>& view, const rtw_camera* cam, const rtw_params* p, unsigned char* ws,
                   const WsLayout& L, uint64_t seed_adv, const RtwPassMap& map, uint32_t cl_on, int dev, size_t lds,
-                  uint32_t grid_cap, hipStream_t stream, int mode, bool masked) {
+                  uint32_t grid_cap, hipStream_t stream, int mode, bool masked, size_t tail_lds) {
   rtwk::TraceArgs<R> a;
   fill_args(a, view, cam, p, ws, L, seed_adv);
   map.apply(a);
@@ -303,6 +305,9 @@ int launch_engine(const rtwk::SceneView<R>& view, const rtw_camera* cam, const r
                   cl_on && a.sc.n_clusters * rtwk::kClusterSlots <= 64u)
                      ? 1u
                      : 0u;
+  // Its tail dealing, where launch_all found room for the tail blocks (tail_lds, after `lds`).
+  a.tail_on = (a.primary_on && tail_lds) ? 1u : 0u;
+  if (a.tail_on) lds += tail_lds;
   if (p->engine == RTW_ENGINE_WAVEFRONT) {
     if (mode == 2) return rtw_fail(RTW_UNSUPPORTED, "phase profile runs on the megakernel engine");
     return rtw_run_wavefront<R>(a, p, ws, L, dev, lds, stream, mode == 1);
@@ -340,13 +345,21 @@ int launch_all(rtw_scene sc, const rtw_camera* cam, const rtw_params* p, void* w
   size_t lds = lds_bytes(sc, (int)p->precision, cl_on ? sc->v64.n_clusters : 0u);
   if (p->engine == RTW_ENGINE_MEGAKERNEL) lds += rtwk::trace_home_lds_bytes((int)p->precision, masked);
   if (lds > 64 * 1024) return rtw_fail(RTW_UNSUPPORTED, "scene tables need %zu B of LDS", lds);
-  const uint32_t grid_cap = (uint32_t)(device_cus(dev) * blocks_per_cu(dev, (int)p->precision, lds, masked));
+  const int bpc = blocks_per_cu(dev, (int)p->precision, lds, masked);
+  const uint32_t grid_cap = (uint32_t)(device_cus(dev) * bpc);
+  // The tail blocks of the primary-first loop (TraceArgs::tail_on) join the launch only where they cost no
+  // resident workgroup: a scene with large tables keeps the loop without the tail dealing.
+  // (RTW_TRACE_TAIL=0, -DRTW_MEASURE only: off, for the A/B.)
+  size_t tail_lds = p->engine == RTW_ENGINE_MEGAKERNEL ? rtwk::trace_tail_lds_bytes((int)p->precision, masked) : 0;
+  if (const char* tk = dev_knob("RTW_TRACE_TAIL"); tk && tk[0] == '0') tail_lds = 0;
+  if (tail_lds && (lds + tail_lds > 64 * 1024 || blocks_per_cu(dev, (int)p->precision, lds + tail_lds, masked, true) != bpc))
+    tail_lds = 0;
   if (timer) HIP_TRY(hipEventRecord(timer->start, stream));
   const int st = p->precision == RTW_PRECISION_F32
                      ? launch_engine(sc->v32, cam, p, ws, L, seed_adv, map, cl_on, dev, lds, grid_cap, stream, mode,
-                                     masked)
+                                     masked, tail_lds)
                      : launch_engine(sc->v64, cam, p, ws, L, seed_adv, map, cl_on, dev, lds, grid_cap, stream, mode,
-                                     masked);
+                                     masked, tail_lds);
   if (st != RTW_OK) return st;
   if (timer) {
     HIP_TRY(hipEventRecord(timer->stop, stream));

@@ -772,6 +772,9 @@ struct KStats {
   // primary-first loop: wave-iterations with a primary phase, lanes whose sample ended in it (idle for the rest
   // of the iteration), the batches' mask popcounts summed
   unsigned long long prim_rounds = 0, prim_idle = 0, mask_pop = 0;
+  // its tail (the wave's queue ran dry): samples traced for another lane's unit, wave-iterations, lane-slots of
+  // those with no sample in flight or to start, its own or another lane's
+  unsigned long long tail_helped = 0, tail_iters = 0, tail_idle = 0;
   uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t t_last = 0;
 };

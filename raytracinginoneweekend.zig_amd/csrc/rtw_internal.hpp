@@ -77,7 +77,9 @@ struct TraceArgs {
   uint32_t upt_m, upt_sh, tx_m, tx_sh;  // rtwm::udiv magic of units per tile (64 * n_chunks) and tiles_x
   uint32_t unit_order;            // rtw_device.hpp dealt_unit: 0 image order, 1 last-first
   uint32_t primary_on;            // the primary-first loop runs (f64 unmasked; clusters on, one 64-slot block)
-  uint64_t seed_base;             // SplitMix64(seed).next()
+  uint32_t tail_on;               // that loop deals a wave's remaining samples to its idle lanes once the queue is
+                                  // dry (the launch's LDS then holds trace_tail_lds_bytes more)
+  uint64_t seed_base;            // SplitMix64(seed).next()
   double* partial;                // [n_chunks][row_count*W][3] chunk sums
   uint32_t* counter;              // work-queue head (zeroed before launch)
   unsigned long long* stats;      // counts {samples, segments, skipped} [0..2]; phase cycles [8..13]
@@ -118,6 +120,12 @@ constexpr size_t kHomeLdsBytesPerWave = 2560;
 constexpr size_t kPrimaryLdsBytesPerWave = 4 * 64 * 4;
 size_t trace_home_lds_bytes(int precision, bool masked);
 constexpr int kTraceBlock = 256;
+// The primary-first loop's tail dealing (TraceArgs::tail_on): a block per wave after the workgroup's home
+// blocks — per lane the unit's next sample to hand out, the helper's busy word, the dealing list and the
+// unit's window of kTailWindow helper lanes (rtw_trace.hip).  0 for a configuration without that loop.
+constexpr uint32_t kTailWindow = 4;
+constexpr size_t kTailLdsBytesPerWave = (3 + kTailWindow) * 64 * 4;
+size_t trace_tail_lds_bytes(int precision, bool masked);
 
 // ---------------------------------------------------------- accumulator --
 // rtw_accum.hip: progressive rendering (rtw_hip.h rtw_accum_*).  A pass

@@ -74,6 +74,9 @@ struct TraceCfg {
   static constexpr bool kPrimaryFirst = !F32 && !MASKED;
   // Bytes per wave after the scene tables (rtw_internal.hpp): the home block, then the primary masks.
   static constexpr size_t kHomeStride = kHomeLdsBytesPerWave + (kPrimaryFirst ? kPrimaryLdsBytesPerWave : 0);
+  // Bytes per wave after those, in a launch with TraceArgs::tail_on: the tail block of the primary-first loop
+  // (profiles/r15/README.md).
+  static constexpr size_t kTailBytes = kPrimaryFirst ? kTailLdsBytesPerWave : 0;
 };
 
 template <typename R, bool F32, int MODE, bool MASKED>
@@ -98,7 +101,9 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
   uint32_t* h_u32 = nullptr;  // px[64], ly[64], c[64], s_end[64]
   {
     const size_t off = (size_t)(reinterpret_cast<unsigned char*>(T.cpos + kClusterSlots * S.n_clusters) - lds_raw);
-    unsigned char* hb = lds_raw + ((off + 7) & ~(size_t)7) + (threadIdx.x >> 6) * Cfg::kHomeStride;
+    // (a launch with TraceArgs::tail_on: the wave's tail block follows its primary masks)
+    const size_t stride = Cfg::kHomeStride + (Cfg::kTailBytes != 0 && A.tail_on ? Cfg::kTailBytes : 0);
+    unsigned char* hb = lds_raw + ((off + 7) & ~(size_t)7) + (threadIdx.x >> 6) * stride;
     h_sum = reinterpret_cast<double*>(hb);
     h_u32 = reinterpret_cast<uint32_t*>(hb + 3 * 64 * 8);
     // (the primary masks are h_u32[256 ...]: right after it, the same address register with other offsets)
@@ -263,19 +268,20 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
 
   // A finished sample joins its chunk sum (main.zig:393); a finished unit is
   // published.  (A miss added its colour; depth limit and absorption add 0.)
-  auto finish_sample = [&]() {
+  auto publish_unit = [&]() __attribute__((always_inline)) {
+    const uint32_t npix = RTW_KA(row_count) * RTW_KA(W);
+    double* dst = RTW_KA(partial) +
+                  ((size_t)h_u32[128 + lid] * npix + (size_t)h_u32[64 + lid] * RTW_KA(W) + h_u32[lid]) * 3;
+    dst[0] = h_sum[lid];
+    dst[1] = h_sum[64 + lid];
+    dst[2] = h_sum[128 + lid];
+    have_unit = false;
+  };
+  auto finish_sample = [&]() __attribute__((always_inline)) {
     L.s++;
     have_ray = false;
     if (STATS) st.samples++;
-    if (L.s == h_u32[192 + lid]) {
-      const uint32_t npix = RTW_KA(row_count) * RTW_KA(W);
-      double* dst = RTW_KA(partial) +
-                    ((size_t)h_u32[128 + lid] * npix + (size_t)h_u32[64 + lid] * RTW_KA(W) + h_u32[lid]) * 3;
-      dst[0] = h_sum[lid];
-      dst[1] = h_sum[64 + lid];
-      dst[2] = h_sum[128 + lid];
-      have_unit = false;
-    }
+    if (L.s == h_u32[192 + lid]) publish_unit();
   };
   // One closest-hit step for a lane with a live ray (main.zig:103-112).
   // Returns 1 when the sample ended (depth limit or miss), 2 when the hit is
@@ -284,7 +290,8 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
   // memory — a store + load per iteration on the critical path.)
   // prim (the primary-first loop): the lane's camera ray, from the mask of its tile
   // (closest_hit's PRIMARY form) instead of the wave's pretest.
-  auto bounce = [&](uint32_t& kind, int& hit, R& tmax, auto prim) -> int {
+  // (always_inline: with the loop body compiled twice its call sites are too many for the inliner)
+  auto bounce = [&](uint32_t& kind, int& hit, R& tmax, auto prim) __attribute__((always_inline)) -> int {
     constexpr bool PRIM = decltype(prim)::value;
     if (L.depth == RTW_KA(max_depth)) {  // rayColor depth == 0 (main.zig:105-108)
       return 1;
@@ -325,21 +332,131 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
       // tie rule and the NaN fallback are closest_hit's.
       primary_ran = true;
       LaneFlag<8u> shading{lane_flags};
+      LaneFlag<16u> helping{lane_flags};  // tail: the lane traces sample L.s of lane h_u32[128 + lid]'s unit
       uint32_t kind = 0;
       int hit = -1;
       R tmax = kInf;
-      for (;;) {
+      // The wave's tail block (TraceArgs::tail_on; after the wave's primary masks), words per lane:
+      //   [lid]                the unit's first sample no lane has been given (`next`)
+      //   [64 + lid]           nonzero while the lane traces or holds a sample of another lane's unit
+      //   [128 + i]            the dealing list
+      //   [192 + 64 j + lid]   the unit's window: 0x80 | helper lane of sample s, j = s % kTailWindow,
+      //                        | 0x40 once that helper's h_sum triple holds the sample's radiance
+      // The tail copy reaches it, and the other lanes' home entries, through wave_u32(): the wave's h_u32 made
+      // from the lane's own h_me, so that no value of the tail lives in the bulk copy's registers.  (The lane
+      // index is laundered, not the pointer: a laundered pointer is a generic one, 64 bits and flat accesses.)
+      auto wave_u32 = [&]() -> uint32_t* {
+        uint32_t l = lid;
+        asm volatile("" : "+v"(l));
+        return h_me - l;
+      };
+      constexpr uint32_t kTl = (uint32_t)((Cfg::kHomeStride - 3 * 64 * 8) / 4);  // the tail block, from h_u32
+      auto tail_block = [&]() -> uint32_t* { return wave_u32() + kTl; };
+      // The loop body, compiled twice (as rtw_world.hip's): without the tail for the bulk of the launch, and
+      // with it once the queue ran dry for some lane of the wave.  Returns true when the wave has finished.
+      // Tail (dealing on): the lanes left without a unit trace the NEXT samples of the wave's other units,
+      // up to kTailWindow - 1 ahead of the owner's, each into its own (free) h_sum triple; the owner, after
+      // the sample it traces itself, adds the finished ones in ascending sample order with finish_sample's
+      // path's own additions (a sample that added nothing: + 0.0), starts nothing while the next sample in
+      // order is in flight, and alone publishes the chunk sum.  The RNG state is a function of (pixel,
+      // sample), so the sums keep their bits.
+      // (always_inline: called twice, the body would stay a function, its captures in scratch memory)
+      auto body = [&](auto tail_tag) __attribute__((always_inline)) -> bool {
+        constexpr bool TAIL = decltype(tail_tag)::value;
         RTW_STAMP(5)
-        take_units();
-        if (!__any(have_unit)) {
-          if (__all(done)) break;
-          continue;
+        // (the tail's per-lane `start` is a flag bit and `deal` is re-read where used: as variables they were
+        // SGPRs held across the closest hits, spilled to VGPR lanes)
+        LaneFlag<32u> start{lane_flags};
+        auto deal = [&]() -> bool { return RTW_KA(tail_on) != 0u; };
+        if constexpr (!TAIL) {
+          take_units();
+        } else {
+          // (a wave takes its units in ascending order, and one lay past the queue's end: the next do too)
+          if (!have_unit) done = true;
         }
+        if (!__any(have_unit)) {
+          if (__all(done)) return true;
+          return false;
+        }
+        if constexpr (TAIL) {
+          start = have_unit && !have_ray;
+          if (deal()) {
+            uint32_t* const tl = tail_block();
+            // an owner takes its own next sample from `next` too, before any is handed out
+            if (start) {
+              if (tl[lid] == L.s)
+                tl[lid] = L.s + 1u;
+              else
+                start = false;
+            }
+            for (;;) {
+              wave_lds_sync();
+              const bool free_lane = !have_unit && !helping && tl[64 + lid] == 0u;
+              const uint64_t needm = wballot(free_lane);
+              if (!needm) break;
+              uint32_t nx = 0;
+              bool offer = false;
+              if (have_unit) {  // (L.s: the owner's sample in flight, or the first one not yet in its sum)
+                nx = tl[lid];
+                offer = nx < h_me[192] && nx < L.s + kTailWindow;
+              }
+              const uint64_t offm = wballot(offer);
+              if (!offm) break;
+              const uint32_t ro = mbcnt64(offm);
+              if (offer) {
+                tl[128 + ro] = lid | (nx << 6);
+                if (ro < popc64(needm)) tl[lid] = nx + 1u;
+              }
+              wave_lds_sync();
+              const uint32_t rw = mbcnt64(needm);
+              if (free_lane && rw < popc64(offm)) {
+                const uint32_t e = tl[128 + rw], o = e & 63u;
+                helping = true;
+                L.s = e >> 6;
+                double z = 0.0;
+                asm volatile("" : "+v"(z));
+                const uint32_t* const ho = tl - kTl + o;  // the owner's home entries
+                h_me[0] = ho[0];
+                h_me[64] = ho[64];
+                h_me[128] = o;
+                h_me[kPm] = ho[kPm];
+                h_me[kPm + 64] = ho[kPm + 64];
+                h_sum[lid] = h_sum[64 + lid] = h_sum[128 + lid] = z;
+                tl[64 + lid] = 1u;
+                tl[192 + 64 * (L.s % kTailWindow) + o] = 0x80u | lid;
+              }
+            }
+            if (helping && !have_ray) start = true;
+          }
+          if constexpr (STATS) {
+            if (lid == (uint32_t)__builtin_ctzll(__ballot(true))) st.tail_iters++;
+            if (!have_ray && !start) st.tail_idle++;
+          }
+        }
+        // A finished sample: finish_sample, but in the dealing tail a helper leaves its sample's radiance in
+        // its h_sum triple for the owner, and an owner's unit ends in the fold below.
+        auto finish = [&]() {
+          if constexpr (!TAIL) {
+            finish_sample();
+          } else if (!deal()) {
+            finish_sample();
+          } else {
+            have_ray = false;
+            if (STATS) st.samples++;
+            if (helping) {
+              helping = false;
+              if (STATS) st.tail_helped++;
+              tail_block()[192 + 64 * (L.s % kTailWindow) + h_me[128]] = 0xC0u | lid;
+            } else {
+              L.s++;
+            }
+          }
+        };
         RTW_STAMP(0)
         // (at the loop's top a lane has a ray exactly when it is shading)
         // (the lens-disk point from the lane's own loop: 0.6 % faster than a disk-only cooperative pass
         // before the camera rays, profiles/r11/README.md)
-        if (have_unit && !have_ray) {
+        if (TAIL ? (bool)start : (have_unit && !have_ray)) {
           R u = (R)0, v = (R)0, dk[2] = {(R)0, (R)0};
           L.px = h_u32[lid];
           L.ly = h_u32[64 + lid];
@@ -352,7 +469,7 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
           start_sample_ray<R>(kargs<R>(), L, u, v, dk[0], dk[1]);
           have_ray = true;
           if (bounce(kind, hit, tmax, std::true_type{}) == 1) {  // miss or depth limit
-            finish_sample();
+            finish();
             if (STATS) st.prim_idle++;
           } else {
             shading = true;
@@ -364,7 +481,7 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
         if (__any(dim != 0u)) coop_reject_mixed<R>(dim, L.rs, pt, raw, slots, lid);
         RTW_STAMP(7)
         if (shading) {
-          if (scatter_hit<R, F32, true>(T, L, hit, tmax, kind, pt, raw)) finish_sample();  // absorbed
+          if (scatter_hit<R, F32, true>(T, L, hit, tmax, kind, pt, raw)) finish();  // absorbed
         }
         RTW_STAMP(8)
         shading = false;
@@ -377,7 +494,50 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
           shading = b == 2;
         }
         RTW_STAMP(3)
-        if (ended) finish_sample();
+        if (ended) finish();
+        if constexpr (TAIL) {
+          if (deal()) {
+            // An owner between samples adds the finished samples that follow, in sample order, and frees
+            // their lanes; its unit ends here.
+            wave_lds_sync();
+            if (have_unit && !have_ray) {
+              uint32_t* const tl = tail_block();
+              const uint32_t nx = tl[lid];
+              while (L.s != nx) {  // sample L.s went to another lane
+                const uint32_t w = tl[192 + 64 * (L.s % kTailWindow) + lid];
+                if (!(w & 0x40u)) break;  // still in flight
+                const uint32_t hl = w & 63u;
+                const double* const hs = reinterpret_cast<const double*>(tl - kTl - 3 * 64 * 2) + hl;  // lane hl's triple
+                h_sum[lid] += hs[0];
+                h_sum[64 + lid] += hs[64];
+                h_sum[128 + lid] += hs[128];
+                tl[64 + hl] = 0u;
+                L.s++;
+              }
+              if (L.s == h_me[192]) publish_unit();
+            }
+          }
+        }
+        return false;
+      };
+      // The bulk copy runs until the wave has finished or, in a launch with the tail, until one of its lanes
+      // is done; the tail copy then runs to the wave's end (at once, if the bulk copy finished).  One way out
+      // of the bulk loop: with two, the loop held more SGPRs and re-read the kernel-argument pointer from a
+      // spill lane a dozen times per iteration.
+      // (the counting pass runs the tail copy with dealing off too: its tail words)
+      // (`done` first: tail_on is re-read from the kernel argument, a load and its wait)
+      for (;;) {
+        if (body(std::false_type{})) break;
+        if (__any(done) && (STATS || RTW_KA(tail_on) != 0u)) break;
+      }
+      if (STATS || RTW_KA(tail_on) != 0u) {
+        if (RTW_KA(tail_on) != 0u) {
+          uint32_t* const tl = tail_block();
+          tl[lid] = have_ray ? L.s + 1u : L.s;
+          tl[64 + lid] = 0u;
+        }
+        while (!body(std::true_type{})) {
+        }
       }
     }
   }
@@ -466,6 +626,9 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
       atomicAdd(A.stats + 14, st.prim_rounds);
       atomicAdd(A.stats + 15, st.prim_idle);
       atomicAdd(A.stats + 16, st.mask_pop);
+      atomicAdd(A.stats + 17, st.tail_helped);
+      atomicAdd(A.stats + 18, st.tail_iters);
+      atomicAdd(A.stats + 19, st.tail_idle);
     }
   }
   if constexpr (MODE == 2) {
@@ -550,6 +713,10 @@ bool trace_primary_first(int precision, bool masked) {
 size_t trace_home_lds_bytes(int precision, bool masked) {
   return 8 + (kTraceBlock / 64) *
                  with_cfg(precision, masked, [](auto f32, auto m) { return TraceCfg<f32.value, m.value>::kHomeStride; });
+}
+size_t trace_tail_lds_bytes(int precision, bool masked) {
+  return (kTraceBlock / 64) *
+         with_cfg(precision, masked, [](auto f32, auto m) { return TraceCfg<f32.value, m.value>::kTailBytes; });
 }
 
 }  // namespace rtwk

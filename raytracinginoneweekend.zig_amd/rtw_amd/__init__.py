@@ -40,7 +40,8 @@ STAT_NAMES = ["samples", "segments", "f32_skips", "cand_wave_iters", "cand_lanes
               "sphere_loop_wave_iters", "cull_survivor_lanes", "cull_exact_wave_iters", "drain_segments",
               "drain_samples", "cluster_wave_tests", "cluster_wave_skips", "drain_wave_iters", "primary_rounds",
               "primary_idle_lanes"]  # RTW_STAT_*
-STAT_NAMES_EX = STAT_NAMES + ["primary_mask_popcount"]  # rtw_render_stats_ex: word 16 on
+STAT_NAMES_EX = STAT_NAMES + ["primary_mask_popcount", "tail_helped_samples", "tail_wave_iters",
+                              "tail_idle_lane_iters"]  # rtw_render_stats_ex: word 16 on
 DEFAULT_CHUNK = 20
 COVER_BACKGROUND = (0.70, 0.80, 1.00)
 

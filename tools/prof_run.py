@@ -1,7 +1,8 @@
 """One render of BASELINE configs[1] per precision, for rocprofv3 (kernel
 trace / PMC passes).  Usage: python tools/prof_run.py [f64|f32|both|wf64] [reps] [field=value ...]
 (wf64: the same frame on the wavefront engine, BASELINE configs[3]; field=value: rtw_params
-fields of that render, e.g. wf_sets=1 — the library reads no environment for them)"""
+fields of that render, e.g. wf_sets=1 — the library reads no environment for them; spp=N: the
+frame's samples per pixel, default 500)"""
 import os
 import sys
 
@@ -18,7 +19,7 @@ def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "both"
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     kw = {k: int(v) if v.isdigit() else v for k, v in (a.split("=", 1) for a in sys.argv[3:])}
-    W, spp = 1200, 500
+    W, spp = 1200, kw.pop("spp", 500)  # (spp=20: one progressive pass's launch)
     H = R.image_height(W, 16 / 9)
     sph, mats, _ = R.cover_scene(42)
     cam = R.cover_camera(16 / 9)
