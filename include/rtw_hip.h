@@ -364,7 +364,8 @@ int rtw_built_scene_free(rtw_built_scene b);
 
 /* Upload a world to the CURRENT device: tables + a BVH over worlds of more
  * than 32 primitives (flags bit 0 = RTW_WORLD_LINEAR: no BVH, every segment
- * tests every primitive in a wave-uniform loop; bit 1 = RTW_WORLD_DEBUG_BVH). */
+ * tests every primitive in a wave-uniform loop; bit 1 = RTW_WORLD_DEBUG_BVH;
+ * bit 2 = RTW_WORLD_DYNAMIC, "dynamic worlds" below). */
 #define RTW_WORLD_LINEAR 1u
 #define RTW_WORLD_DEBUG_BVH 2u /* diagnostic: the BVH root's two children (leaf / node, boxes) to stderr */
 typedef struct rtw_world_s *rtw_world;
@@ -372,6 +373,71 @@ int rtw_world_create(const rtw_world_desc *desc, uint32_t flags, rtw_world *out)
 int rtw_world_destroy(rtw_world world);
 /* BVH statistics: nodes, leaves, max depth, max leaf size. */
 int rtw_world_bvh_info(rtw_world world, uint32_t info_out[4]);
+
+/* ---- dynamic worlds: new numbers for an uploaded world, in place ----------
+ * A world created with RTW_WORLD_DYNAMIC (rtw_world_create flags bit 2) can
+ * take new geometry numbers without being created again: each primitive's
+ * a[9] and each transform's v[][3].  Everything else is fixed at creation:
+ * kinds, materials, transform indices, op lists, textures, counts, and the
+ * BVH's topology (its refs, the stored order, rtw_world_bvh_info) — the
+ * tree is refitted, not rebuilt.  A DYNAMIC world keeps a small host copy of
+ * the fixed fields and a second device allocation (the refit's tables, freed
+ * by rtw_world_destroy); a world without the flag allocates nothing extra,
+ * its tables are the same bytes, and both entries return RTW_EINVAL for it.
+ * A DYNAMIC world without a BVH (<= 32 primitives, or RTW_WORLD_LINEAR)
+ * updates its records only.
+ *
+ * rtw_world_update takes HOST arrays shaped like the descriptor's, checks
+ * that their fixed fields equal the world's (else RTW_EINVAL), and runs on
+ * the null stream.  rtw_world_update_device takes bare doubles in DEVICE
+ * memory of the world's device: d_a is n_prims x 9 in list order, d_xv is
+ * n_xforms x RTW_MAX_XFORM_OPS x 3 or NULL (the transforms keep their values);
+ * the arrays must stay valid until the work enqueued on `stream` has run.
+ *
+ * Validate, then commit.  A first phase only reads the input: every number a
+ * primitive's kind uses (and every value of a transform's ops) must be finite
+ * and a moving sphere needs t1 > t0; the same pass reduces the world's f64
+ * box and the leaf pretest's bounds.  The host waits for that one small
+ * readback — the call's only synchronisation.  On a violation the call
+ * returns RTW_EINVAL with a message and the world is untouched.  Otherwise the
+ * commit kernels are enqueued on `stream` and the call returns without
+ * waiting: work enqueued later on that stream sees the new world.  An update
+ * while a render or query of the same world is in flight on ANOTHER stream is
+ * the caller's race.
+ *
+ * Contract: after an update, every render, guide buffer and ray query of the
+ * world is byte-identical to that of a world freshly created from the updated
+ * description (any engine choice, traversal, feature set or accumulator
+ * state), hence to the oracle.  The device tables themselves are specified
+ * too: they equal rtw_world_refit_tables_host of the same numbers byte for
+ * byte, and an update with the creation's own numbers reproduces the created
+ * tables.
+ *
+ * Leaf pretest under motion: a leaf keeps its pretest iff it had a record at
+ * creation and each of its spheres still qualifies (untransformed, |r| < 100,
+ * static or moving over the shutter [0, 1]); when the update's Cmax (the
+ * largest |centre| + |centre1 - centre0| over those leaves) exceeds 2^20
+ * every leaf loses it until a later update is back within the limit.  A world
+ * that had no pretest table at creation never gets one.  All of this changes
+ * speed only, never a result.
+ *
+ * Tree quality degrades as primitives move far from where the builder put
+ * them: boxes grow and overlap.  There is no automatic rebuild; when renders
+ * slow down, create the world again. */
+#define RTW_WORLD_DYNAMIC 4u
+int rtw_world_update(rtw_world w, const rtw_prim *prims, uint32_t n_prims,
+                     const rtw_xform *xforms, uint32_t n_xforms);
+int rtw_world_update_device(rtw_world w, const double *d_a, const double *d_xv, void *stream);
+/* Diagnostics (tests): the size of the world's device tables; a synchronous
+ * copy of them with cull_out = {cull_cmax, cull_rho} and bounds_out = the
+ * world box {lo[3], hi[3]} (any world; bytes must equal the size); and what
+ * the tables of `desc` created with `flags` hold after an update with a / xv
+ * (HOST arrays shaped as rtw_world_update_device's; a == NULL: as created),
+ * computed on the host alone.  RTW_EINVAL where the update would refuse. */
+size_t rtw_world_table_bytes(rtw_world w);
+int rtw_world_read_tables(rtw_world w, void *out, size_t bytes, float cull_out[2], double bounds_out[6]);
+int rtw_world_refit_tables_host(const rtw_world_desc *desc, uint32_t flags, const double *a, const double *xv,
+                                void *out, size_t bytes, float cull_out[2], double bounds_out[6]);
 
 /* Device workspace of a world render on the CURRENT device (the world's):
  * rtw_workspace_bytes(params) + the tail dealing's per-lane sample rings

@@ -49,6 +49,7 @@
 #include <vector>
 
 #include "rtw_host.hpp"
+#include "rtw_orbit.hpp"
 
 static double parse_aspect(const char* s) {
   const char* c = std::strchr(s, ':');
@@ -147,7 +148,8 @@ static std::shared_ptr<rtw::Image> loadPNG(const std::string& path) {
 int main(int argc, char** argv) {
   uint32_t scene = 6;  // main.zig:313
   uint32_t width = 0, spp = 0, depth = 50, chunk = 0, precision = RTW_PRECISION_F64, engine = RTW_ENGINE_MEGAKERNEL;
-  uint32_t pass_spp = 0, min_spp = 0;
+  uint32_t pass_spp = 0, min_spp = 0, frames = 1;
+  double orbit = 0;
   double aspect = 0, max_noise = 0, pixel_noise = 0;
   uint64_t seed = 42;
   std::string out = "out.ppm", image_path, preview_dir, spp_map;
@@ -181,6 +183,8 @@ int main(int argc, char** argv) {
     else if (k == "--pixel-noise") pixel_noise = std::atof(v);
     else if (k == "--min-spp") min_spp = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--spp-map") spp_map = v;
+    else if (k == "--frames") frames = (uint32_t)std::strtoul(v, nullptr, 10);
+    else if (k == "--orbit") orbit = std::atof(v);
     else if (k == "--denoise-levels") denoise_levels = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--pick" || k == "--focus-at") {
       const bool is_pick = k == "--pick";
@@ -201,6 +205,10 @@ int main(int argc, char** argv) {
   }
   if ((denoise_levels || denoise_spatial) && !denoise) {
     std::fprintf(stderr, "--denoise-levels and --denoise-spatial need --denoise\n");
+    return 2;
+  }
+  if (frames == 0 || (frames > 1 && (pass_spp || denoise || pick || focus_at))) {
+    std::fprintf(stderr, "--frames needs N >= 1 and renders one-shot frames (no --pass-spp, --denoise, --pick, --focus-at)\n");
     return 2;
   }
   if (!(pixel_noise > 0) && (min_spp || !spp_map.empty())) {
@@ -321,7 +329,21 @@ int main(int argc, char** argv) {
     p.width = W, p.height = H, p.spp = S, p.max_depth = depth, p.seed = seed;
     for (int k = 0; k < 3; ++k) p.background[k] = st.background[k];
     p.row_begin = 0, p.row_stride = 1, p.row_count = H, p.chunk = chunk, p.device = -1;
-    if (scene == 1 && pass_spp) {
+    if (frames > 1) {
+      // --frames N --orbit DEG: one upload, an in-place update per frame (rtw_hip.h "dynamic worlds");
+      // frame_0000.ppm ... next to --out, the last frame in --out itself
+      const rtw::FlatWorld fw = rtw::flattenWorld(world);
+      const rtw_world_desc desc = fw.desc();
+      p.precision = RTW_PRECISION_F64, p.engine = RTW_ENGINE_MEGAKERNEL;
+      const size_t slash = out.find_last_of('/');
+      const std::string dir = slash == std::string::npos ? "" : out.substr(0, slash + 1);
+      rtw::renderOrbit(cam.to_c(), p, desc, frames, orbit, [&](uint32_t k, const std::vector<uint8_t>& img) {
+        char name[32];
+        std::snprintf(name, sizeof(name), "frame_%04u.ppm", k);
+        rtw::writePPM(dir + name, img, W, H);
+        rgb = img;
+      });
+    } else if (scene == 1 && pass_spp) {
       p.precision = precision, p.engine = engine;
       const rtw::FlatScene fs = rtw::flatten(world);
       rgb = progressive(p, &fs, nullptr);

@@ -1,0 +1,21 @@
+// rtw_orbit.hpp — frames of a moving world for the CLI (rtw_render --frames N
+// --orbit DEG): the world is uploaded once with RTW_WORLD_DYNAMIC and updated
+// in place per frame (rtw_hip.h "dynamic worlds"; rtw_world_capi.hip).
+#pragma once
+#include <cstdint>
+#include <functional>
+#include <vector>
+
+#include "rtw_hip.h"
+
+namespace rtw {
+
+// Frame k of `frames` (k = 0 is the description as it stands): every sphere
+// centre (both ends of a moving sphere) turned by k * deg degrees about the y
+// axis, every RotateY op's angle advanced by as much — spheres orbit the
+// scene's axis, boxes turn in place.  on_frame gets each frame's RGB8 image.
+using FrameFn = std::function<void(uint32_t frame, const std::vector<uint8_t>& rgb)>;
+void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames, double deg,
+                 const FrameFn& on_frame);
+
+}  // namespace rtw

@@ -15,7 +15,12 @@
 #include "rtw_hip.h"
 #include "rtw_capi_shared.hpp"
 #include "rtw_internal.hpp"
+#include "rtw_cull.hpp"
+#include "rtw_host.hpp"
+#include "rtw_libm.hpp"
+#include "rtw_orbit.hpp"
 #include "rtw_world_pack.hpp"
+#include "rtw_world_update.hpp"
 
 struct rtw_world_s {
   int device = 0;
@@ -26,7 +31,59 @@ struct rtw_world_s {
   uint32_t feat = 0;  // features used (rtw_world.hip kFeat*): picks the kernel instantiation
   uint32_t info[4] = {0, 0, 0, 0};
   bool packed = false;  // the BVH carries the refs in its bounds' low bits (rtw_world_pack.cpp pack_refs)
+  size_t table_bytes = 0;  // of buf
+  // RTW_WORLD_DYNAMIC (rtw_hip.h "dynamic worlds"): the refit's tables, the validation's partials and
+  // the host entry's staging arrays in a second allocation; nullptr for a frozen world
+  rtwp::RefitPack* refit = nullptr;
+  void* refit_buf = nullptr;
+  rtwk::UpdateArgs upd{};  // device pointers of both allocations (a / xv: per call)
+  double* stage_a = nullptr;
+  double* stage_xv = nullptr;
 };
+
+namespace {
+// The second allocation of a DYNAMIC world: RefitPack::blob | partials | result | staging a | staging xv.
+int make_dynamic(rtw_world_s* w, const rtw_world_desc* d, const rtwp::WorldPack& k) {
+  auto* r = new rtwp::RefitPack;
+  rtwp::make_refit(d, k, *r);
+  const uint32_t n_wg = std::max(1u, (std::max(k.n_prims, d->n_xforms) + rtwr::kBlock - 1) / rtwr::kBlock);
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_part = r->blob.size(), o_res = o_part + al((size_t)n_wg * rtwr::kPartial * 8),
+               o_a = o_res + al(rtwr::kPartial * 8), o_xv = o_a + al((size_t)k.n_prims * 9 * 8 + 8),
+               total = o_xv + al((size_t)d->n_xforms * 3 * RTW_MAX_XFORM_OPS * 8 + 8);
+  void* buf = nullptr;
+  if (hipMalloc(&buf, total) != hipSuccess) {
+    delete r;
+    return rtw_fail(RTW_ENOMEM, "rtw_world_create: hipMalloc(%zu) for the refit tables", total);
+  }
+  if (hipMemset(buf, 0, total) != hipSuccess ||
+      hipMemcpy(buf, r->blob.data(), r->blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(buf);
+    delete r;
+    return rtw_fail(RTW_EHIP, "rtw_world_create: upload of the refit tables failed");
+  }
+  auto* rb = static_cast<unsigned char*>(buf);
+  rtwr::View& V = w->upd.v;
+  V.prim = const_cast<double*>(w->view.prim), V.xform = const_cast<double*>(w->view.xform);
+  V.node = const_cast<float*>(w->view.node), V.order = w->view.order, V.cull = const_cast<float*>(w->view.cull);
+  V.by_height = reinterpret_cast<const uint32_t*>(rb + r->o_by_height);
+  V.heights = reinterpret_cast<const uint32_t*>(rb + r->o_heights);
+  V.plain = reinterpret_cast<float*>(rb + r->o_plain);
+  V.cand = reinterpret_cast<const uint32_t*>(rb + r->o_cand);
+  V.mate = reinterpret_cast<const uint32_t*>(rb + r->o_mate);
+  V.n_prims = k.n_prims, V.n_xforms = d->n_xforms, V.n_nodes = k.n_nodes;
+  V.packed = k.packed ? 1u : 0u, V.has_table = k.has_cull ? 1u : 0u;
+  w->upd.partials = reinterpret_cast<double*>(rb + o_part);
+  w->upd.result = reinterpret_cast<double*>(rb + o_res);
+  w->upd.n_wg = n_wg;
+  w->stage_a = reinterpret_cast<double*>(rb + o_a);
+  w->stage_xv = reinterpret_cast<double*>(rb + o_xv);
+  r->blob = std::vector<unsigned char>();  // (the device holds it now)
+  w->refit = r;
+  w->refit_buf = buf;
+  return RTW_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -73,6 +130,15 @@ int rtw_world_create(const rtw_world_desc* d, uint32_t flags, rtw_world* out) {
   w->feat = k.feat;
   std::memcpy(w->info, k.info, sizeof(w->info));
   w->packed = k.packed;
+  w->table_bytes = total;
+  if (flags & RTW_WORLD_DYNAMIC) {
+    const int sd = make_dynamic(w, d, k);
+    if (sd != RTW_OK) {
+      (void)hipFree(buf);
+      delete w;
+      return sd;
+    }
+  }
   *out = w;
   return RTW_OK;
 }
@@ -80,7 +146,92 @@ int rtw_world_create(const rtw_world_desc* d, uint32_t flags, rtw_world* out) {
 int rtw_world_destroy(rtw_world w) {
   if (!w) return RTW_OK;
   if (w->buf) (void)hipFree(w->buf);
+  if (w->refit_buf) (void)hipFree(w->refit_buf);
+  delete w->refit;
   delete w;
+  return RTW_OK;
+}
+
+int rtw_world_update_device(rtw_world w, const double* d_a, const double* d_xv, void* stream) {
+  if (!w) return rtw_fail(RTW_EINVAL, "rtw_world_update_device: world is NULL");
+  if (!w->refit) return rtw_fail(RTW_EINVAL, "rtw_world_update_device: the world was not created with RTW_WORLD_DYNAMIC");
+  if (!d_a && w->view.n_prims) return rtw_fail(RTW_EINVAL, "rtw_world_update_device: d_a is NULL");
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != w->device)
+    return rtw_fail(RTW_EINVAL, "rtw_world_update_device: world lives on device %d, current is %d", w->device, dev);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  rtwk::UpdateArgs a = w->upd;
+  a.v.a = d_a ? d_a : w->stage_a, a.v.xv = d_xv;
+  // validate: reads the input only; the one readback the host waits for
+  hipError_t e = rtwk::launch_update_validate(a, s);
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "update validation launch: %s", hipGetErrorString(e));
+  double res[rtwr::kPartial];
+  HIP_TRY(hipMemcpyAsync(res, a.result, sizeof(res), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  rtwr::Partial p;
+  rtwr::partial_load(p, res);
+  if (p.bad != 0.0)
+    return rtw_fail(RTW_EINVAL, "rtw_world_%s", rtwp::refit_violation(p.bad, p.first_bad, w->view.n_prims).c_str());
+  // commit
+  rtwp::refit_scalars(p, w->view.n_nodes, w->view.cull_cmax, w->view.cull_rho, w->bounds_lo, w->bounds_hi);
+  a.v.cull_on = (a.v.has_table && w->view.cull_cmax <= rtwc::kCmaxLimit) ? 1u : 0u;
+  e = rtwk::launch_update_commit(a, w->refit->h_off.data(), w->refit->h_max, w->refit->h_star, s);
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "update commit launch: %s", hipGetErrorString(e));
+  return RTW_OK;
+}
+
+int rtw_world_update(rtw_world w, const rtw_prim* prims, uint32_t n_prims, const rtw_xform* xforms, uint32_t n_xforms) {
+  if (!w) return rtw_fail(RTW_EINVAL, "rtw_world_update: world is NULL");
+  if (!w->refit) return rtw_fail(RTW_EINVAL, "rtw_world_update: the world was not created with RTW_WORLD_DYNAMIC");
+  if ((n_prims && !prims) || (n_xforms && !xforms)) return rtw_fail(RTW_EINVAL, "rtw_world_update: NULL array with a non-zero count");
+  std::string msg;
+  if (!rtwp::same_fixed_fields(*w->refit, prims, n_prims, xforms, n_xforms, msg))
+    return rtw_fail(RTW_EINVAL, "rtw_world_update: %s", msg.c_str());
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != w->device) return rtw_fail(RTW_EINVAL, "rtw_world_update: world lives on device %d, current is %d", w->device, dev);
+  std::vector<double> a((size_t)9 * n_prims), xv((size_t)3 * RTW_MAX_XFORM_OPS * n_xforms);
+  for (uint32_t i = 0; i < n_prims; ++i) std::memcpy(a.data() + (size_t)9 * i, prims[i].a, sizeof(prims[i].a));
+  for (uint32_t i = 0; i < n_xforms; ++i) std::memcpy(xv.data() + (size_t)12 * i, xforms[i].v, sizeof(xforms[i].v));
+  // (the null stream: an earlier update's kernels have read the staging arrays before these copies land)
+  if (!a.empty()) HIP_TRY(hipMemcpy(w->stage_a, a.data(), a.size() * 8, hipMemcpyHostToDevice));
+  if (!xv.empty()) HIP_TRY(hipMemcpy(w->stage_xv, xv.data(), xv.size() * 8, hipMemcpyHostToDevice));
+  return rtw_world_update_device(w, w->stage_a, n_xforms ? w->stage_xv : nullptr, nullptr);
+}
+
+size_t rtw_world_table_bytes(rtw_world w) { return w ? w->table_bytes : 0; }
+
+int rtw_world_read_tables(rtw_world w, void* out, size_t bytes, float cull_out[2], double bounds_out[6]) {
+  if (!w || !out) return rtw_fail(RTW_EINVAL, "rtw_world_read_tables: world/out is NULL");
+  if (bytes != w->table_bytes) return rtw_fail(RTW_EINVAL, "rtw_world_read_tables: %zu bytes, the tables have %zu", bytes, w->table_bytes);
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, w->buf, bytes, hipMemcpyDeviceToHost));
+  if (cull_out) cull_out[0] = w->view.cull_cmax, cull_out[1] = w->view.cull_rho;
+  if (bounds_out)
+    for (int c = 0; c < 3; ++c) bounds_out[c] = w->bounds_lo[c], bounds_out[3 + c] = w->bounds_hi[c];
+  return RTW_OK;
+}
+
+int rtw_world_refit_tables_host(const rtw_world_desc* d, uint32_t flags, const double* a, const double* xv, void* out,
+                                size_t bytes, float cull_out[2], double bounds_out[6]) {
+  if (!d || !out) return rtw_fail(RTW_EINVAL, "rtw_world_refit_tables_host: desc/out is NULL");
+  const char* nc = rtw_dev_knob("RTW_WORLD_NOCULL");  // (as rtw_world_create)
+  rtwp::WorldPack k;
+  std::string msg;
+  const int st = rtwp::pack_world(d, flags, nc && *nc, k, msg);
+  if (st != RTW_OK) return rtw_fail(st, "%s", msg.c_str());
+  if (bytes != k.blob.size()) return rtw_fail(RTW_EINVAL, "rtw_world_refit_tables_host: %zu bytes, the tables have %zu", bytes, k.blob.size());
+  if (a || xv) {
+    if (!a && d->n_prims) return rtw_fail(RTW_EINVAL, "rtw_world_refit_tables_host: xv without a");
+    rtwp::RefitPack r;
+    rtwp::make_refit(d, k, r);
+    if (rtwp::refit_world(k, r, a, xv) != RTW_OK) return rtw_fail(RTW_EINVAL, "rtw_world_%s", r.msg.c_str());
+  }
+  std::memcpy(out, k.blob.data(), bytes);
+  if (cull_out) cull_out[0] = k.cull_cmax, cull_out[1] = k.cull_rho;
+  if (bounds_out)
+    for (int c = 0; c < 3; ++c) bounds_out[c] = k.bounds_lo[c], bounds_out[3 + c] = k.bounds_hi[c];
   return RTW_OK;
 }
 
@@ -474,3 +625,55 @@ int rtw_world_render(const rtw_camera* cam, const rtw_world_desc* desc, const rt
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------ rtw_render --frames --
+namespace rtw {
+
+void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames, double deg,
+                 const FrameFn& on_frame) {
+  struct Dev {  // released on every way out
+    rtw_world w = nullptr;
+    void *ws = nullptr, *rgb = nullptr;
+    ~Dev() {
+      if (ws) (void)hipFree(ws);
+      if (rgb) (void)hipFree(rgb);
+      rtw_world_destroy(w);
+    }
+  } d;
+  auto ok = [](int st) {
+    if (st != RTW_OK) throw Error(st, rtw_last_error());
+  };
+  ok(rtw_world_create(&desc, RTW_WORLD_DYNAMIC, &d.w));
+  const size_t wsb = rtw_world_workspace_bytes(d.w, &p);
+  if (wsb == 0) throw Error(RTW_EINVAL, rtw_last_error());
+  std::vector<uint8_t> rgb((size_t)p.width * p.row_count * 3);
+  if (hipMalloc(&d.ws, wsb) != hipSuccess || hipMalloc(&d.rgb, rgb.size()) != hipSuccess)
+    throw Error(RTW_ENOMEM, "renderOrbit: device allocation failed");
+  std::vector<rtw_prim> prims(desc.prims, desc.prims + desc.n_prims);
+  std::vector<rtw_xform> xforms(desc.xforms, desc.xforms + desc.n_xforms);
+  for (uint32_t k = 0; k < frames; ++k) {
+    if (k) {  // (frame 0: the description as it stands)
+      const double phi = (double)k * deg * (3.14159265358979323846 / 180.0), sn = rtwl::sin(phi), cs = rtwl::cos(phi);
+      for (uint32_t i = 0; i < desc.n_prims; ++i) {
+        if (desc.prims[i].kind > RTW_PRIM_MOVING_SPHERE) continue;
+        for (int e = 0; e < 2; ++e) {  // RotateY's forward map (hittable.zig:531-537) of both centres
+          const double x = desc.prims[i].a[3 * e], z = desc.prims[i].a[3 * e + 2];
+          prims[i].a[3 * e] = cs * x + sn * z, prims[i].a[3 * e + 2] = -sn * x + cs * z;
+        }
+      }
+      for (uint32_t i = 0; i < desc.n_xforms; ++i)
+        for (uint32_t c = 0; c < desc.xforms[i].n; ++c)
+          if (desc.xforms[i].op[c] == RTW_XF_ROTATE_Y) {
+            const double t = desc.xforms[i].v[c][2] + phi;
+            xforms[i].v[c][0] = rtwl::sin(t), xforms[i].v[c][1] = rtwl::cos(t), xforms[i].v[c][2] = t;
+          }
+      ok(rtw_world_update(d.w, prims.data(), desc.n_prims, xforms.data(), desc.n_xforms));
+    }
+    ok(rtw_world_render_device(d.w, &cam, &p, d.ws, wsb, static_cast<uint8_t*>(d.rgb), nullptr, nullptr, nullptr));
+    if (hipMemcpy(rgb.data(), d.rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)
+      throw Error(RTW_EHIP, "renderOrbit: the render failed on the device");
+    on_frame(k, rgb);
+  }
+}
+
+}  // namespace rtw

@@ -13,6 +13,7 @@
 #include "rtw_cull.hpp"
 #include "rtw_layout.hpp"
 #include "rtw_world_box.hpp"
+#include "rtw_world_refit.hpp"
 
 namespace rtwp {
 namespace {
@@ -277,16 +278,8 @@ class Builder {
     const uint32_t c1 = m == e ? (rtwk::kLeafBit | e) : child(lo1, hi1, depth + 1);
     const Box b0 = range_box(lo0, hi0), b1 = range_box(lo1, hi1);
     float* nd = out_.nodes.data() + (size_t)rtwk::kNodeWords * n;
-    auto down = [](double x) {  // largest float <= x
-      float f = (float)x;
-      if ((double)f > x) f = std::nextafter(f, -INFINITY);
-      return f;
-    };
-    auto up = [](double x) {  // smallest float >= x
-      float f = (float)x;
-      if ((double)f < x) f = std::nextafter(f, INFINITY);
-      return f;
-    };
+    using rtwr::down;  // largest float <= x
+    using rtwr::up;    // smallest float >= x
     for (int k = 0; k < 3; ++k) {  // {lo0, lo1} and {hi0, hi1} pairs per axis (packed-f32 operands)
       nd[2 * k] = down(b0.lo[k]), nd[2 * k + 1] = down(b1.lo[k]);
       nd[6 + 2 * k] = up(b0.hi[k]), nd[7 + 2 * k] = up(b1.hi[k]);
@@ -298,10 +291,8 @@ class Builder {
 
 }  // namespace
 
-uint32_t compact_ref(uint32_t r) {
-  if (r < rtwk::kLeafBit) return r;
-  return 0x800000u | ((((r >> 23) & rtwk::kLeafCountMask) - 1u) << 22) | (r & 0x7FFFFFu);
-}
+uint32_t compact_ref(uint32_t r) { return rtwr::compact_ref(r); }
+float pack_lower_with_low8(float f, uint32_t payload) { return lower_with_low8(f, payload); }
 
 int pack_world(const rtw_world_desc* d, uint32_t flags, bool no_leaf_pretest, WorldPack& out, std::string& msg) {
   if ((d->n_prims && !d->prims) || (d->n_xforms && !d->xforms) || (d->n_textures && !d->textures) ||
@@ -396,21 +387,7 @@ int pack_world(const rtw_world_desc* d, uint32_t flags, bool no_leaf_pretest, Wo
     list_to_pos[li] = pos;
     const rtw_prim& p = d->prims[li];
     double* r = prim.data() + (size_t)rtwk::kWorldRec * pos;
-    if (p.kind <= RTW_PRIM_MOVING_SPHERE) {
-      for (int k = 0; k < 3; ++k) r[k] = p.a[k];
-      if (p.kind == RTW_PRIM_MOVING_SPHERE) {
-        for (int k = 0; k < 3; ++k) r[3 + k] = p.a[3 + k] - p.a[k];  // center1.sub(center0)
-        r[7] = p.a[7];
-        r[8] = p.a[8] - p.a[7];  // time1 - time0
-        r[10] = 1.0 / r[8];      // its reciprocal (Markstein division in the kernel)
-      }
-      r[6] = p.a[6];
-      r[9] = p.a[6] * p.a[6];  // sphere.radius * sphere.radius
-    } else {
-      for (int k = 0; k < 5; ++k) r[k] = p.a[k];
-      r[5] = p.a[1] - p.a[0];
-      r[6] = p.a[3] - p.a[2];
-    }
+    rtwr::fill_record(p.kind, p.a, r);  // doubles 0-10 (shared with the refit)
     const uint32_t meta[4] = {p.kind | ((uint32_t)(p.xform + 1) << 8), p.mat, li, 0u};
     std::memcpy(r + 14, meta, sizeof(meta));
     // the kind and list index again in double 11, so the per-lane walk's root
@@ -430,8 +407,7 @@ int pack_world(const rtw_world_desc* d, uint32_t flags, bool no_leaf_pretest, Wo
   if (use_bvh) {
     auto eligible = [&](uint32_t pos) {
       const rtw_prim& p = d->prims[bvh.order[pos]];
-      if (p.xform >= 0 || !(std::fabs(p.a[6]) < 100.0)) return false;
-      return p.kind == RTW_PRIM_SPHERE || (p.kind == RTW_PRIM_MOVING_SPHERE && p.a[7] == 0.0 && p.a[8] == 1.0);
+      return rtwr::eligible(p.kind | ((uint32_t)(p.xform + 1) << 8), p.a);
     };
     std::vector<uint32_t> leaf_refs;  // (node, child) slots whose leaf qualifies
     double cmax_c = 0.0, cmax_d = 0.0, rho_max = 1.0;
@@ -462,11 +438,7 @@ int pack_world(const rtw_world_desc* d, uint32_t flags, bool no_leaf_pretest, Wo
         std::memcpy(&ref, nw, 4);
         const uint32_t first = ref & 0x7FFFFFu, cnt = (ref >> 23) & rtwk::kLeafCountMask;
         for (uint32_t j = 0; j < cnt; ++j) {  // sphere j of the leaf -> lane j of each f2
-          const double* r = prim.data() + (size_t)rtwk::kWorldRec * (first + j);
-          float* q = cull.data() + (size_t)16 * first + j;
-          for (int k = 0; k < 3; ++k) q[2 * k] = (float)r[k], q[2 * (3 + k)] = -(float)r[3 + k];
-          const float rf = (float)r[6];
-          q[12] = -(rf * rf);
+          rtwr::fill_cull(cull.data() + (size_t)16 * first, j, prim.data() + (size_t)rtwk::kWorldRec * (first + j));
         }
         ref |= rtwk::kCullBit;  // (cnt <= 2 here, so no ref is all ones: the traversal's kNoRef, rtw_world.hip)
         std::memcpy(nw, &ref, 4);
@@ -543,6 +515,7 @@ int pack_world(const rtw_world_desc* d, uint32_t flags, bool no_leaf_pretest, Wo
   for (int c = 0; c < 3; ++c) wp.bounds_lo[c] = bounds.lo[c], wp.bounds_hi[c] = bounds.hi[c];
   wp.info[0] = bvh.n_nodes, wp.info[1] = bvh.n_leaves, wp.info[2] = bvh.max_depth, wp.info[3] = bvh.max_leaf;
   wp.packed = bvh.packed;
+  wp.has_cull = !cull.empty();
   out = std::move(wp);
   return RTW_OK;
 }

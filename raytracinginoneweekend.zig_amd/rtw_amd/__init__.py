@@ -229,6 +229,14 @@ def lib() -> C.CDLL:
         L.rtw_world_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, P(QueryOpts), C.c_void_p]
         L.rtw_scene_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.rtw_world_query_info.argtypes = [C.c_void_p, P(QueryOpts), C.c_uint32 * 4]
+    if hasattr(L, "rtw_world_update_device"):  # dynamic worlds (an older A/B build has none)
+        L.rtw_world_update.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.rtw_world_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rtw_world_table_bytes.restype = C.c_size_t
+        L.rtw_world_table_bytes.argtypes = [C.c_void_p]
+        L.rtw_world_read_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float * 2, C.c_double * 6]
+        L.rtw_world_refit_tables_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_size_t, C.c_float * 2, C.c_double * 6]
     _lib = L
     return L
 

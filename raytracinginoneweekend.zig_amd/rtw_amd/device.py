@@ -234,3 +234,25 @@ class TorchTracer:
         out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=self.device)
         self._launch(self.target.occluded, rays, out, opts)
         return out != 0
+
+
+def update_world(dw, a: torch.Tensor, xv: torch.Tensor | None = None):
+    """New numbers for a dynamic world.DeviceWorld from torch tensors of its device
+    (rtw_world_update_device on torch's current stream, no host round trip): a is
+    (n_prims, 9) float64 in list order, xv (n_xforms, 4, 3) float64 or None (the transforms
+    keep their values).  Renders and queries enqueued afterwards on that stream see the new
+    world; torch's caching allocator keeps the tensors' memory valid for work of that stream."""
+    for name, t, tail in (("a", a, (9,)), ("xv", xv, (4, 3))):
+        if t is None:
+            continue
+        if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float64 tensor on the world's device")
+        if tuple(t.shape[1:]) != tail or t.dim() != len(tail) + 1:
+            raise ValueError(f"{name} must have shape (n, {', '.join(map(str, tail))})")
+    if a.shape[0] != dw.n_prims or (xv is not None and xv.shape[0] != dw.n_xforms):
+        raise ValueError(f"the world has {dw.n_prims} primitives and {dw.n_xforms} transforms")
+    if xv is not None and xv.device != a.device:
+        raise ValueError("a and xv live on different devices")
+    with torch.cuda.device(a.device):
+        dw.update_device(a.data_ptr(), xv.data_ptr() if xv is not None and xv.numel() else None,
+                         torch.cuda.current_stream(a.device).cuda_stream)

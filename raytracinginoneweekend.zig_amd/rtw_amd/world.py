@@ -26,6 +26,7 @@ XF_TRANSLATE, XF_ROTATE_Y = 0, 1
 TEX_SOLID, TEX_CHECKER, TEX_NOISE, TEX_IMAGE = 0, 1, 2, 3
 WMAT_LAMBERT, WMAT_METAL, WMAT_DIELECTRIC, WMAT_LIGHT = 0, 1, 2, 3
 WORLD_LINEAR = 1
+WORLD_DYNAMIC = 4  # rtw_hip.h RTW_WORLD_DYNAMIC: the world takes updates (update / update_device)
 WORLD_DEBUG_BVH = 2  # rtw_hip.h RTW_WORLD_DEBUG_BVH: the BVH root's children to stderr (diagnostic)
 SCENES = {1: "cover", 2: "two_spheres", 3: "two_perlin_spheres", 4: "earth", 5: "simple_light",
           6: "cornell_box", 7: "globe_10k"}
@@ -272,16 +273,79 @@ def render_world(cam: Camera, desc: WorldDesc, params: Params, want_mean=False):
     return (rgb, mean) if want_mean else rgb
 
 
+def refit_tables_host(desc: WorldDesc, flags: int, table_bytes: int, a=None, xv=None) -> dict:
+    """rtw_world_refit_tables_host: what the tables of `desc` created with `flags` hold after an
+    update with a ((n_prims, 9) float64) and xv ((n_xforms, 4, 3) float64 or None), computed on
+    the host alone; a=None: as created.  table_bytes: DeviceWorld.table_bytes() of such a world.
+    Same keys as DeviceWorld.read_tables()."""
+    L = _wlib()
+    cull, bounds = (C.c_float * 2)(), (C.c_double * 6)()
+    a = None if a is None else np.ascontiguousarray(a, np.float64)
+    xv = None if xv is None else np.ascontiguousarray(xv, np.float64)
+    if a is not None and a.shape != (desc.n_prims, 9):
+        raise ValueError(f"a must be ({desc.n_prims}, 9)")
+    if xv is not None and xv.shape != (desc.n_xforms, 4, 3):
+        raise ValueError(f"xv must be ({desc.n_xforms}, 4, 3)")
+    blob = np.zeros(table_bytes, np.uint8)
+    _check(L.rtw_world_refit_tables_host(C.byref(desc), flags, a.ctypes.data if a is not None else None,
+                                         xv.ctypes.data if xv is not None else None, blob.ctypes.data, table_bytes,
+                                         cull, bounds))
+    return {"blob": blob, "cull": np.array(cull[:], np.float32), "bounds": np.array(bounds[:], np.float64)}
+
+
+def desc_numbers(desc: WorldDesc):
+    """The numbers an update replaces, out of a descriptor: a (n_prims, 9) and xv (n_xforms, 4, 3)."""
+    a = np.array([list(desc.prims[i].a) for i in range(desc.n_prims)], np.float64).reshape(desc.n_prims, 9)
+    xv = np.array([[list(desc.xforms[i].v[k]) for k in range(4)] for i in range(desc.n_xforms)],
+                  np.float64).reshape(desc.n_xforms, 4, 3)
+    return a, xv
+
+
 TRAVERSAL_NAMES = {1: "union", 2: "lane", 3: "linear"}  # rtw_world_traversal (rtw_hip.h)
 
 
 class DeviceWorld:
     """A world resident in HBM of the current device (rtw_world_create)."""
 
-    def __init__(self, desc: WorldDesc, linear: bool = False, debug_bvh: bool = False):
+    def __init__(self, desc: WorldDesc, linear: bool = False, debug_bvh: bool = False, dynamic: bool = False):
         self.h = C.c_void_p()
-        flags = (WORLD_LINEAR if linear else 0) | (WORLD_DEBUG_BVH if debug_bvh else 0)
+        flags = ((WORLD_LINEAR if linear else 0) | (WORLD_DEBUG_BVH if debug_bvh else 0) |
+                 (WORLD_DYNAMIC if dynamic else 0))
+        self.flags, self.n_prims, self.n_xforms = flags, int(desc.n_prims), int(desc.n_xforms)
         _check(_wlib().rtw_world_create(C.byref(desc), flags, C.byref(self.h)))
+
+    def update(self, prims, xforms=None):
+        """rtw_world_update: new numbers from HOST arrays shaped like the descriptor's — a
+        WorldDesc (its prims and xforms are taken), or ctypes arrays of Prim and Xform (all of
+        them, in list order); kinds, materials, transform indices and op lists must equal the
+        world's.  The world must have been created with dynamic=True."""
+        if isinstance(prims, WorldDesc):
+            pp, n, xp, nx = prims.prims, prims.n_prims, prims.xforms, prims.n_xforms
+        else:
+            pp, n = prims, (len(prims) if prims is not None else 0)
+            xp, nx = xforms, (len(xforms) if xforms is not None else 0)
+        _check(_wlib().rtw_world_update(self.h, C.cast(pp, C.c_void_p) if n else None, n,
+                                        C.cast(xp, C.c_void_p) if nx else None, nx))
+
+    def update_device(self, a_ptr: int, xv_ptr: int | None = None, stream: int | None = None):
+        """rtw_world_update_device: a_ptr = n_prims x 9 float64 in device memory (list order),
+        xv_ptr = n_xforms x 4 x 3 float64 or None (the transforms keep their values).  Waits for
+        the validation's readback, then enqueues the commit on `stream` and returns."""
+        _check(_wlib().rtw_world_update_device(self.h, C.c_void_p(a_ptr) if a_ptr else None,
+                                               C.c_void_p(xv_ptr) if xv_ptr else None,
+                                               C.c_void_p(stream) if stream else None))
+
+    def table_bytes(self) -> int:
+        return int(_wlib().rtw_world_table_bytes(self.h))
+
+    def read_tables(self) -> dict:
+        """rtw_world_read_tables (diagnostic, synchronous): the device tables as bytes, the
+        pretest's host scalars and the world box."""
+        n = self.table_bytes()
+        blob = np.zeros(n, np.uint8)
+        cull, bounds = (C.c_float * 2)(), (C.c_double * 6)()
+        _check(_wlib().rtw_world_read_tables(self.h, blob.ctypes.data, n, cull, bounds))
+        return {"blob": blob, "cull": np.array(cull[:], np.float32), "bounds": np.array(bounds[:], np.float64)}
 
     def bvh_info(self) -> dict:
         info = (C.c_uint32 * 4)()
@@ -374,4 +438,4 @@ class DeviceWorld:
             pass
 
 
-__all__ = ["BuiltScene", "DeviceWorld", "render_world", "load_png", "earth_map", "synthetic_world_map", "RtwError", "SCENES"]
+__all__ = ["BuiltScene", "DeviceWorld", "refit_tables_host", "desc_numbers", "render_world", "load_png", "earth_map", "synthetic_world_map", "RtwError", "SCENES"]
