@@ -422,8 +422,9 @@ int rtw_world_bvh_info(rtw_world world, uint32_t info_out[4]);
  * speed only, never a result.
  *
  * Tree quality degrades as primitives move far from where the builder put
- * them: boxes grow and overlap.  There is no automatic rebuild; when renders
- * slow down, create the world again. */
+ * them: boxes grow and overlap.  rtw_world_bvh_cost measures that and
+ * rtw_world_rebuild* gives the world a new tree in place ("rebuild" below);
+ * nothing rebuilds on its own. */
 #define RTW_WORLD_DYNAMIC 4u
 int rtw_world_update(rtw_world w, const rtw_prim *prims, uint32_t n_prims,
                      const rtw_xform *xforms, uint32_t n_xforms);
@@ -438,6 +439,62 @@ size_t rtw_world_table_bytes(rtw_world w);
 int rtw_world_read_tables(rtw_world w, void *out, size_t bytes, float cull_out[2], double bounds_out[6]);
 int rtw_world_refit_tables_host(const rtw_world_desc *desc, uint32_t flags, const double *a, const double *xv,
                                 void *out, size_t bytes, float cull_out[2], double bounds_out[6]);
+
+/* ---- rebuild: a new tree for a dynamic world, on the device ----------------
+ * rtw_world_rebuild / rtw_world_rebuild_device take the arguments of
+ * rtw_world_update / rtw_world_update_device, run the same checks in the same
+ * validate-then-commit order, and also choose a new topology from the new
+ * numbers: a rebuild is an update that re-sorts the primitives.  Supported:
+ * DYNAMIC worlds whose BVH has leaves of one primitive (rtw_world_bvh_info's
+ * largest leaf == 1: worlds of >= 512 primitives).  Such a tree is a full
+ * binary tree of n_prims - 1 nodes, so node count, leaf count, largest leaf
+ * and every table's size stay; only the depth in rtw_world_bvh_info may
+ * change.  Any other world with the flag (no BVH, RTW_WORLD_LINEAR, leaves of
+ * two) gets RTW_UNSUPPORTED, a world without it RTW_EINVAL; a refused call
+ * leaves the world byte for byte as it was.
+ *
+ * The tree: each primitive's key is the 63-bit Morton code of its box's f64
+ * centroid inside the box of all centroids (21 bits per axis, x highest); the
+ * new stored order is the stable sort of the list by key.  Top-down over the
+ * sorted range, a node splits where the highest differing key bit changes
+ * while a median subtree of the rest still fits the depth cap (the per-lane
+ * walk's stack when ceil(log2 n_prims) fits it, so that walk stays
+ * available; else the union walk's), and at the median after that or when all
+ * its keys are equal.  Records are numbered breadth-first.  Bounds, packed
+ * refs, pretest records and the world box are the update's commit run over the
+ * new tree; which leaves may hold a pretest record is judged anew on the
+ * rebuild's numbers.
+ *
+ * Contract: after a rebuild every render, guide buffer, ray query and
+ * accumulator pass equals that of a world freshly created from the same
+ * numbers, byte for byte; later updates refit the new topology.  The tables,
+ * cull scalars, bounds and bvh_info equal rtw_world_rebuild_tables_host of the
+ * same numbers (info_out: rtw_world_bvh_info's): a function of the numbers,
+ * not of the history of updates and rebuilds.
+ * rtw_world_rebuild_refit_tables_host: the same, followed by an update with
+ * a2 / xv2 (a2 == NULL: none).
+ *
+ * The first rebuild makes a third device allocation (keys, the sort's storage,
+ * the staged topology) that the world keeps.  A rebuild waits once, for the
+ * update's readback widened by the new depth and the nodes per level, after
+ * validation and before anything is written.
+ *
+ * rtw_world_bvh_cost: the sum over nodes of (half-area(child 0 box) +
+ * half-area(child 1 box)) / half-area(root box), the boxes as the node table
+ * stores them, the root box the union of the root's two; summed in f64 in a
+ * fixed order, so two calls agree to the bit.  Any world with a BVH, DYNAMIC or
+ * not (else RTW_UNSUPPORTED); waits for its 8-byte readback on `stream`.  Its
+ * ratio to the cost right after creation or the last rebuild tells when a
+ * rebuild pays. */
+int rtw_world_rebuild(rtw_world w, const rtw_prim *prims, uint32_t n_prims,
+                      const rtw_xform *xforms, uint32_t n_xforms);
+int rtw_world_rebuild_device(rtw_world w, const double *d_a, const double *d_xv, void *stream);
+int rtw_world_bvh_cost(rtw_world w, void *stream, double *cost_out);
+int rtw_world_rebuild_tables_host(const rtw_world_desc *desc, uint32_t flags, const double *a, const double *xv,
+                                  void *out, size_t bytes, float cull_out[2], double bounds_out[6], uint32_t info_out[4]);
+int rtw_world_rebuild_refit_tables_host(const rtw_world_desc *desc, uint32_t flags, const double *a, const double *xv,
+                                        const double *a2, const double *xv2, void *out, size_t bytes,
+                                        float cull_out[2], double bounds_out[6], uint32_t info_out[4]);
 
 /* Device workspace of a world render on the CURRENT device (the world's):
  * rtw_workspace_bytes(params) + the tail dealing's per-lane sample rings

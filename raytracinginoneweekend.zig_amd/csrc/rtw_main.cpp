@@ -9,6 +9,7 @@
 //                            [--pixel-noise X [--min-spp N] [--spp-map FILE]]]
 //              [--denoise [--denoise-levels N] [--denoise-spatial]]
 //              [--pick X,Y] [--focus-at X,Y]
+//              [--frames N [--orbit DEG] [--rebuild-above R]]
 // --pick X,Y traces the feature ray of pixel (X, image row Y) (rtw_pixel_ray,
 // rtw_world_trace) and prints one line,
 //   pick x=.. y=.. prim=.. t=.. p=..,..,.. front=.. material=<kind>   (or: pick x=.. y=.. miss)
@@ -34,6 +35,12 @@
 // variance of pixels that hold fewer than two chunks from the image itself: the
 // way to denoise a first preview of a single chunk.  Without --denoise the
 // output bytes are unchanged, and without --denoise-spatial --denoise's are.
+// --frames N --orbit DEG uploads the world once and updates it in place per
+// frame (frame_%04d.ppm next to --out).  --rebuild-above R: after a frame's
+// update, when the tree cost (rtw_world_bvh_cost) exceeds R times its value
+// right after the creation or the last rebuild, the frame's numbers go through
+// rtw_world_rebuild; one stderr line per rebuild gives the frame and the cost
+// before and after.  The frames' bytes do not depend on it.
 // Defaults are the reference's: scene 6 (main.zig:313) with that scene's own
 // size, spp, camera and background (main.zig:316-362); --width/--aspect/--spp
 // override them.  Scenes 4 and 7 need --image (assets/sekaichizu.png).
@@ -149,7 +156,7 @@ int main(int argc, char** argv) {
   uint32_t scene = 6;  // main.zig:313
   uint32_t width = 0, spp = 0, depth = 50, chunk = 0, precision = RTW_PRECISION_F64, engine = RTW_ENGINE_MEGAKERNEL;
   uint32_t pass_spp = 0, min_spp = 0, frames = 1;
-  double orbit = 0;
+  double orbit = 0, rebuild_above = -1.0;  // (< 0: never rebuild)
   double aspect = 0, max_noise = 0, pixel_noise = 0;
   uint64_t seed = 42;
   std::string out = "out.ppm", image_path, preview_dir, spp_map;
@@ -185,6 +192,7 @@ int main(int argc, char** argv) {
     else if (k == "--spp-map") spp_map = v;
     else if (k == "--frames") frames = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--orbit") orbit = std::atof(v);
+    else if (k == "--rebuild-above") rebuild_above = std::atof(v);
     else if (k == "--denoise-levels") denoise_levels = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--pick" || k == "--focus-at") {
       const bool is_pick = k == "--pick";
@@ -209,6 +217,10 @@ int main(int argc, char** argv) {
   }
   if (frames == 0 || (frames > 1 && (pass_spp || denoise || pick || focus_at))) {
     std::fprintf(stderr, "--frames needs N >= 1 and renders one-shot frames (no --pass-spp, --denoise, --pick, --focus-at)\n");
+    return 2;
+  }
+  if (rebuild_above != -1.0 && (frames < 2 || !(rebuild_above >= 0))) {
+    std::fprintf(stderr, "--rebuild-above needs R >= 0 and --frames N with N >= 2\n");
     return 2;
   }
   if (!(pixel_noise > 0) && (min_spp || !spp_map.empty())) {
@@ -342,7 +354,7 @@ int main(int argc, char** argv) {
         std::snprintf(name, sizeof(name), "frame_%04u.ppm", k);
         rtw::writePPM(dir + name, img, W, H);
         rgb = img;
-      });
+      }, rebuild_above);
     } else if (scene == 1 && pass_spp) {
       p.precision = precision, p.engine = engine;
       const rtw::FlatScene fs = rtw::flatten(world);

@@ -14,8 +14,12 @@ namespace rtw {
 // centre (both ends of a moving sphere) turned by k * deg degrees about the y
 // axis, every RotateY op's angle advanced by as much — spheres orbit the
 // scene's axis, boxes turn in place.  on_frame gets each frame's RGB8 image.
+// rebuild_above >= 0: after a frame's update, when rtw_world_bvh_cost exceeds
+// rebuild_above times its value right after the creation or the last rebuild,
+// the frame's numbers go through rtw_world_rebuild, and one stderr line gives
+// the frame and the cost before and after.
 using FrameFn = std::function<void(uint32_t frame, const std::vector<uint8_t>& rgb)>;
 void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames, double deg,
-                 const FrameFn& on_frame);
+                 const FrameFn& on_frame, double rebuild_above = -1.0);
 
 }  // namespace rtw

@@ -20,6 +20,7 @@
 #include "rtw_libm.hpp"
 #include "rtw_orbit.hpp"
 #include "rtw_world_pack.hpp"
+#include "rtw_world_rebuild.hpp"
 #include "rtw_world_update.hpp"
 
 struct rtw_world_s {
@@ -39,6 +40,11 @@ struct rtw_world_s {
   rtwk::UpdateArgs upd{};  // device pointers of both allocations (a / xv: per call)
   double* stage_a = nullptr;
   double* stage_xv = nullptr;
+  // rtw_world_rebuild*: keys, sort storage, the staged topology (made at the first rebuild and kept)
+  void* rebuild_buf = nullptr;
+  rtwk::RebuildArgs reb{};
+  // rtw_world_bvh_cost: per-workgroup partials and the result (made at the first call and kept)
+  double* cost_buf = nullptr;
 };
 
 namespace {
@@ -147,6 +153,8 @@ int rtw_world_destroy(rtw_world w) {
   if (!w) return RTW_OK;
   if (w->buf) (void)hipFree(w->buf);
   if (w->refit_buf) (void)hipFree(w->refit_buf);
+  if (w->rebuild_buf) (void)hipFree(w->rebuild_buf);
+  if (w->cost_buf) (void)hipFree(w->cost_buf);
   delete w->refit;
   delete w;
   return RTW_OK;
@@ -198,6 +206,183 @@ int rtw_world_update(rtw_world w, const rtw_prim* prims, uint32_t n_prims, const
   if (!a.empty()) HIP_TRY(hipMemcpy(w->stage_a, a.data(), a.size() * 8, hipMemcpyHostToDevice));
   if (!xv.empty()) HIP_TRY(hipMemcpy(w->stage_xv, xv.data(), xv.size() * 8, hipMemcpyHostToDevice));
   return rtw_world_update_device(w, w->stage_a, n_xforms ? w->stage_xv : nullptr, nullptr);
+}
+
+}  // extern "C"
+
+namespace {
+// The third allocation of a DYNAMIC world, made at its first rebuild and kept:
+// self | partials | readback | centroid partials | centroid box | keys x 2 | sorted | ranges | refs |
+// schedule x 2 | meta | the sort's storage.
+int make_rebuild(rtw_world_s* w, hipStream_t s) {
+  const uint32_t n = w->view.n_prims, nn = w->view.n_nodes, n_wg = w->upd.n_wg;
+  size_t sort_bytes = 0;
+  if (rtwk::rebuild_sort_bytes(n, &sort_bytes) != hipSuccess)
+    return rtw_fail(RTW_EHIP, "rtw_world_rebuild: the sort's storage size");
+  size_t total = 0;
+  auto take = [&](size_t b) {
+    const size_t o = total;
+    total += (std::max(b, (size_t)8) + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_self = take((size_t)n * 4), o_part = take((size_t)n_wg * rtwr::kPartial * 8),
+               o_read = take(rtwb::kReadbackBytes), o_cpart = take((size_t)n_wg * 6 * 8), o_cbox = take(6 * 8),
+               o_key = take((size_t)n * 8), o_keys = take((size_t)n * 8), o_sorted = take((size_t)n * 4),
+               o_rng = take((size_t)nn * 8), o_refs = take((size_t)nn * 8), o_byh = take((size_t)nn * 4),
+               o_hts = take((size_t)nn * 4), o_meta = take((size_t)n * 24), o_sort = take(sort_bytes);
+  void* buf = nullptr;
+  if (hipMalloc(&buf, total) != hipSuccess) return rtw_fail(RTW_ENOMEM, "rtw_world_rebuild: hipMalloc(%zu) for the rebuild", total);
+  if (hipMemsetAsync(buf, 0, total, s) != hipSuccess) {
+    (void)hipFree(buf);
+    return rtw_fail(RTW_EHIP, "rtw_world_rebuild: clearing the rebuild allocation failed");
+  }
+  auto* b = static_cast<unsigned char*>(buf);
+  rtwk::RebuildArgs& a = w->reb;
+  a.v = w->upd.v;
+  a.self = reinterpret_cast<uint32_t*>(b + o_self);
+  a.partials = reinterpret_cast<double*>(b + o_part);
+  a.result = reinterpret_cast<double*>(b + o_read);
+  a.levels = reinterpret_cast<uint32_t*>(b + o_read + rtwr::kPartial * 8);
+  a.cpart = reinterpret_cast<double*>(b + o_cpart);
+  a.cbox = reinterpret_cast<double*>(b + o_cbox);
+  a.key = reinterpret_cast<uint64_t*>(b + o_key);
+  a.keys = reinterpret_cast<uint64_t*>(b + o_keys);
+  a.sorted = reinterpret_cast<uint32_t*>(b + o_sorted);
+  a.rng = reinterpret_cast<uint32_t*>(b + o_rng);
+  a.refs = reinterpret_cast<uint32_t*>(b + o_refs);
+  a.by_height = reinterpret_cast<uint32_t*>(b + o_byh);
+  a.heights = reinterpret_cast<uint32_t*>(b + o_hts);
+  a.meta = reinterpret_cast<double*>(b + o_meta);
+  a.sort_tmp = b + o_sort;
+  a.sort_bytes = sort_bytes;
+  a.n_wg = n_wg;
+  w->rebuild_buf = buf;
+  const hipError_t e = rtwk::launch_rebuild_init(a, s);
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "rebuild init launch: %s", hipGetErrorString(e));
+  return RTW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rtw_world_rebuild_device(rtw_world w, const double* d_a, const double* d_xv, void* stream) {
+  if (!w) return rtw_fail(RTW_EINVAL, "rtw_world_rebuild_device: world is NULL");
+  if (!w->refit) return rtw_fail(RTW_EINVAL, "rtw_world_rebuild_device: the world was not created with RTW_WORLD_DYNAMIC");
+  if (!rtwp::rebuild_supported(w->view.n_prims, w->view.n_nodes, w->info))
+    return rtw_fail(RTW_UNSUPPORTED, "rtw_world_rebuild_device: the world has no BVH with leaves of one primitive");
+  if (!d_a) return rtw_fail(RTW_EINVAL, "rtw_world_rebuild_device: d_a is NULL");
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != w->device)
+    return rtw_fail(RTW_EINVAL, "rtw_world_rebuild_device: world lives on device %d, current is %d", w->device, dev);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!w->rebuild_buf) {
+    const int st = make_rebuild(w, s);
+    if (st != RTW_OK) return st;
+  }
+  rtwk::RebuildArgs r = w->reb;
+  r.v.a = d_a, r.v.xv = d_xv;
+  // phase 1 reads the input and the world, and writes the rebuild allocation only: the validation with
+  // every primitive its own mate (a leaf of one is judged on its own sphere), then keys, sort and topology
+  rtwk::UpdateArgs va = w->upd;
+  va.v = r.v, va.v.mate = r.self, va.partials = r.partials, va.result = r.result;
+  hipError_t e = rtwk::launch_update_validate(va, s);
+  if (e == hipSuccess) e = rtwk::launch_rebuild_build(r, s);
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "rebuild launch: %s", hipGetErrorString(e));
+  // the one readback the host waits for: the partial, the depth, the nodes per level
+  alignas(8) unsigned char back[rtwb::kReadbackBytes];
+  HIP_TRY(hipMemcpyAsync(back, r.result, sizeof(back), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  rtwr::Partial p;
+  rtwr::partial_load(p, reinterpret_cast<const double*>(back));
+  if (p.bad != 0.0)
+    return rtw_fail(RTW_EINVAL, "rtw_world_%s", rtwp::refit_violation(p.bad, p.first_bad, w->view.n_prims).c_str());
+  uint32_t levels[1 + rtwb::kMaxLevels];
+  std::memcpy(levels, back + rtwr::kPartial * 8, sizeof(levels));
+  const uint32_t depth = levels[0];
+  uint32_t sum = 0;
+  for (uint32_t l = 0; l < depth && l < rtwb::kMaxLevels; ++l) sum += levels[1 + l];
+  if (depth == 0 || depth > rtwb::cap_of(w->view.n_prims) || sum != w->view.n_nodes)
+    return rtw_fail(RTW_EHIP, "rtw_world_rebuild_device: the device built %u levels of %u nodes", depth, sum);
+  // commit: the new topology, then the update's commit over it
+  rtwp::level_schedule(levels + 1, depth, w->view.n_nodes, *w->refit);
+  w->info[2] = depth;
+  rtwp::refit_scalars(p, w->view.n_nodes, w->view.cull_cmax, w->view.cull_rho, w->bounds_lo, w->bounds_hi);
+  r.v.cull_on = (r.v.has_table && w->view.cull_cmax <= rtwc::kCmaxLimit) ? 1u : 0u;
+  e = rtwk::launch_rebuild_apply(r, s);
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "rebuild apply launch: %s", hipGetErrorString(e));
+  rtwk::UpdateArgs ca = w->upd;
+  ca.v = r.v;
+  e = rtwk::launch_update_commit(ca, w->refit->h_off.data(), w->refit->h_max, w->refit->h_star, s);
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "rebuild commit launch: %s", hipGetErrorString(e));
+  return RTW_OK;
+}
+
+int rtw_world_rebuild(rtw_world w, const rtw_prim* prims, uint32_t n_prims, const rtw_xform* xforms, uint32_t n_xforms) {
+  if (!w) return rtw_fail(RTW_EINVAL, "rtw_world_rebuild: world is NULL");
+  if (!w->refit) return rtw_fail(RTW_EINVAL, "rtw_world_rebuild: the world was not created with RTW_WORLD_DYNAMIC");
+  if (!rtwp::rebuild_supported(w->view.n_prims, w->view.n_nodes, w->info))
+    return rtw_fail(RTW_UNSUPPORTED, "rtw_world_rebuild: the world has no BVH with leaves of one primitive");
+  if ((n_prims && !prims) || (n_xforms && !xforms)) return rtw_fail(RTW_EINVAL, "rtw_world_rebuild: NULL array with a non-zero count");
+  std::string msg;
+  if (!rtwp::same_fixed_fields(*w->refit, prims, n_prims, xforms, n_xforms, msg))
+    return rtw_fail(RTW_EINVAL, "rtw_world_rebuild: %s", msg.c_str());
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != w->device) return rtw_fail(RTW_EINVAL, "rtw_world_rebuild: world lives on device %d, current is %d", w->device, dev);
+  std::vector<double> a((size_t)9 * n_prims), xv((size_t)3 * RTW_MAX_XFORM_OPS * n_xforms);
+  for (uint32_t i = 0; i < n_prims; ++i) std::memcpy(a.data() + (size_t)9 * i, prims[i].a, sizeof(prims[i].a));
+  for (uint32_t i = 0; i < n_xforms; ++i) std::memcpy(xv.data() + (size_t)12 * i, xforms[i].v, sizeof(xforms[i].v));
+  // (the null stream, as rtw_world_update)
+  if (!a.empty()) HIP_TRY(hipMemcpy(w->stage_a, a.data(), a.size() * 8, hipMemcpyHostToDevice));
+  if (!xv.empty()) HIP_TRY(hipMemcpy(w->stage_xv, xv.data(), xv.size() * 8, hipMemcpyHostToDevice));
+  return rtw_world_rebuild_device(w, w->stage_a, n_xforms ? w->stage_xv : nullptr, nullptr);
+}
+
+int rtw_world_bvh_cost(rtw_world w, void* stream, double* cost_out) {
+  if (!w || !cost_out) return rtw_fail(RTW_EINVAL, "rtw_world_bvh_cost: world/cost_out is NULL");
+  if (!w->view.n_nodes) return rtw_fail(RTW_UNSUPPORTED, "rtw_world_bvh_cost: the world has no BVH");
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != w->device) return rtw_fail(RTW_EINVAL, "rtw_world_bvh_cost: world lives on device %d, current is %d", w->device, dev);
+  const uint32_t wg = (w->view.n_nodes + rtwr::kBlock - 1) / rtwr::kBlock;
+  if (!w->cost_buf && hipMalloc(reinterpret_cast<void**>(&w->cost_buf), ((size_t)wg + 1) * 8) != hipSuccess)
+    return rtw_fail(RTW_ENOMEM, "rtw_world_bvh_cost: hipMalloc");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const hipError_t e = rtwk::launch_bvh_cost(w->view.node, w->view.n_nodes, w->cost_buf + 1, w->cost_buf, s);
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "tree cost launch: %s", hipGetErrorString(e));
+  HIP_TRY(hipMemcpyAsync(cost_out, w->cost_buf, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return RTW_OK;
+}
+
+int rtw_world_rebuild_tables_host(const rtw_world_desc* d, uint32_t flags, const double* a, const double* xv, void* out,
+                                  size_t bytes, float cull_out[2], double bounds_out[6], uint32_t info_out[4]) {
+  return rtw_world_rebuild_refit_tables_host(d, flags, a, xv, nullptr, nullptr, out, bytes, cull_out, bounds_out, info_out);
+}
+
+int rtw_world_rebuild_refit_tables_host(const rtw_world_desc* d, uint32_t flags, const double* a, const double* xv,
+                                        const double* a2, const double* xv2, void* out, size_t bytes, float cull_out[2],
+                                        double bounds_out[6], uint32_t info_out[4]) {
+  if (!d || !out || !a) return rtw_fail(RTW_EINVAL, "rtw_world_rebuild_tables_host: desc/out/a is NULL");
+  const char* nc = rtw_dev_knob("RTW_WORLD_NOCULL");  // (as rtw_world_create)
+  rtwp::WorldPack k;
+  std::string msg;
+  const int st = rtwp::pack_world(d, flags, nc && *nc, k, msg);
+  if (st != RTW_OK) return rtw_fail(st, "%s", msg.c_str());
+  if (bytes != k.blob.size()) return rtw_fail(RTW_EINVAL, "rtw_world_rebuild_tables_host: %zu bytes, the tables have %zu", bytes, k.blob.size());
+  rtwp::RefitPack r;
+  rtwp::make_refit(d, k, r);
+  const int sb = rtwp::rebuild_world(k, r, a, xv);
+  if (sb != RTW_OK) return rtw_fail(sb, "rtw_world_%s", r.msg.c_str());
+  if (rtwp::refit_world(k, r, a, xv) != RTW_OK) return rtw_fail(RTW_EINVAL, "rtw_world_%s", r.msg.c_str());
+  if (a2 && rtwp::refit_world(k, r, a2, xv2) != RTW_OK) return rtw_fail(RTW_EINVAL, "rtw_world_%s", r.msg.c_str());
+  std::memcpy(out, k.blob.data(), bytes);
+  if (cull_out) cull_out[0] = k.cull_cmax, cull_out[1] = k.cull_rho;
+  if (bounds_out)
+    for (int c = 0; c < 3; ++c) bounds_out[c] = k.bounds_lo[c], bounds_out[3 + c] = k.bounds_hi[c];
+  if (info_out) std::memcpy(info_out, k.info, sizeof(k.info));
+  return RTW_OK;
 }
 
 size_t rtw_world_table_bytes(rtw_world w) { return w ? w->table_bytes : 0; }
@@ -630,7 +815,7 @@ int rtw_world_render(const rtw_camera* cam, const rtw_world_desc* desc, const rt
 namespace rtw {
 
 void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames, double deg,
-                 const FrameFn& on_frame) {
+                 const FrameFn& on_frame, double rebuild_above) {
   struct Dev {  // released on every way out
     rtw_world w = nullptr;
     void *ws = nullptr, *rgb = nullptr;
@@ -651,6 +836,8 @@ void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_des
     throw Error(RTW_ENOMEM, "renderOrbit: device allocation failed");
   std::vector<rtw_prim> prims(desc.prims, desc.prims + desc.n_prims);
   std::vector<rtw_xform> xforms(desc.xforms, desc.xforms + desc.n_xforms);
+  double built_cost = 0.0;  // the tree cost right after the creation or the last rebuild
+  if (rebuild_above >= 0.0) ok(rtw_world_bvh_cost(d.w, nullptr, &built_cost));
   for (uint32_t k = 0; k < frames; ++k) {
     if (k) {  // (frame 0: the description as it stands)
       const double phi = (double)k * deg * (3.14159265358979323846 / 180.0), sn = rtwl::sin(phi), cs = rtwl::cos(phi);
@@ -668,6 +855,15 @@ void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_des
             xforms[i].v[c][0] = rtwl::sin(t), xforms[i].v[c][1] = rtwl::cos(t), xforms[i].v[c][2] = t;
           }
       ok(rtw_world_update(d.w, prims.data(), desc.n_prims, xforms.data(), desc.n_xforms));
+      if (rebuild_above >= 0.0) {
+        double cost = 0.0;
+        ok(rtw_world_bvh_cost(d.w, nullptr, &cost));
+        if (cost > rebuild_above * built_cost) {
+          ok(rtw_world_rebuild(d.w, prims.data(), desc.n_prims, xforms.data(), desc.n_xforms));
+          ok(rtw_world_bvh_cost(d.w, nullptr, &built_cost));
+          fprintf(stderr, "rebuild frame=%u cost_before=%.6g cost_after=%.6g\n", k, cost, built_cost);
+        }
+      }
     }
     ok(rtw_world_render_device(d.w, &cam, &p, d.ws, wsb, static_cast<uint8_t*>(d.rgb), nullptr, nullptr, nullptr));
     if (hipMemcpy(rgb.data(), d.rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)

@@ -81,4 +81,20 @@ void refit_scalars(const rtwr::Partial& p, uint32_t n_nodes, float& cull_cmax, f
 bool same_fixed_fields(const RefitPack& r, const rtw_prim* prims, uint32_t n_prims, const rtw_xform* xforms,
                        uint32_t n_xforms, std::string& msg);
 
+
+// ----------------------------------------------------------- rebuild ----
+// (rtw_world_build.cpp)  The definition of a rebuild's topology:
+// from the numbers a / xv, a new stored order (Morton keys, stable from list
+// order), a full binary tree over it numbered breadth-first, the order table,
+// the records' meta doubles at their new positions, the refs, and the refit's
+// tables (candidates judged on the new numbers; the schedule is the tree's
+// levels, the deepest first) — everything refit_world(k, r, a, xv) then needs
+// to leave the tables of a rebuilt world.  k.info[2] becomes the new depth.
+// RTW_UNSUPPORTED unless the tree has leaves of one primitive; RTW_EINVAL as
+// refit_world; in both cases k and r are untouched and r.msg is set.
+int rebuild_world(WorldPack& k, RefitPack& r, const double* a, const double* xv);
+bool rebuild_supported(uint32_t n_prims, uint32_t n_nodes, const uint32_t info[4]);
+// h_off / h_max / h_star of r from the nodes per level of a tree of `depth` levels.
+void level_schedule(const uint32_t* level_count, uint32_t depth, uint32_t n_nodes, RefitPack& r);
+
 }  // namespace rtwp

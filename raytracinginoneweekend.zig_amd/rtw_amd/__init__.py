@@ -237,6 +237,15 @@ def lib() -> C.CDLL:
         L.rtw_world_read_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float * 2, C.c_double * 6]
         L.rtw_world_refit_tables_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_size_t, C.c_float * 2, C.c_double * 6]
+    if hasattr(L, "rtw_world_rebuild_device"):  # rebuilds and the tree cost
+        L.rtw_world_rebuild.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.rtw_world_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rtw_world_bvh_cost.argtypes = [C.c_void_p, C.c_void_p, P(C.c_double)]
+        L.rtw_world_rebuild_tables_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_size_t, C.c_float * 2, C.c_double * 6, C.c_uint32 * 4]
+        L.rtw_world_rebuild_refit_tables_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_float * 2,
+                                                          C.c_double * 6, C.c_uint32 * 4]
     _lib = L
     return L
 

@@ -242,6 +242,18 @@ def update_world(dw, a: torch.Tensor, xv: torch.Tensor | None = None):
     (n_prims, 9) float64 in list order, xv (n_xforms, 4, 3) float64 or None (the transforms
     keep their values).  Renders and queries enqueued afterwards on that stream see the new
     world; torch's caching allocator keeps the tensors' memory valid for work of that stream."""
+    _numbers_to_world(dw.update_device, dw, a, xv)
+
+
+def rebuild_world(dw, a: torch.Tensor, xv: torch.Tensor | None = None):
+    """A new tree for a dynamic world.DeviceWorld from torch tensors of its device
+    (rtw_world_rebuild_device on torch's current stream): the arguments of update_world.  The
+    world takes the numbers as an update does and is re-sorted and split anew from them;
+    dw.bvh_cost() against its value after the last rebuild tells when that pays."""
+    _numbers_to_world(dw.rebuild_device, dw, a, xv)
+
+
+def _numbers_to_world(entry, dw, a, xv):
     for name, t, tail in (("a", a, (9,)), ("xv", xv, (4, 3))):
         if t is None:
             continue
@@ -254,5 +266,5 @@ def update_world(dw, a: torch.Tensor, xv: torch.Tensor | None = None):
     if xv is not None and xv.device != a.device:
         raise ValueError("a and xv live on different devices")
     with torch.cuda.device(a.device):
-        dw.update_device(a.data_ptr(), xv.data_ptr() if xv is not None and xv.numel() else None,
-                         torch.cuda.current_stream(a.device).cuda_stream)
+        entry(a.data_ptr(), xv.data_ptr() if xv is not None and xv.numel() else None,
+              torch.cuda.current_stream(a.device).cuda_stream)

@@ -293,6 +293,39 @@ def refit_tables_host(desc: WorldDesc, flags: int, table_bytes: int, a=None, xv=
     return {"blob": blob, "cull": np.array(cull[:], np.float32), "bounds": np.array(bounds[:], np.float64)}
 
 
+def rebuild_tables_host(desc: WorldDesc, flags: int, table_bytes: int, a, xv=None, then_a=None, then_xv=None) -> dict:
+    """rtw_world_rebuild_tables_host: what the tables of `desc` created with `flags` hold after a
+    rebuild with a / xv, computed on the host alone; then_a / then_xv: followed by an update with
+    these (rtw_world_rebuild_refit_tables_host).  The keys of refit_tables_host, and "info": the
+    four numbers of rtw_world_bvh_info."""
+    L = _wlib()
+    cull, bounds, info = (C.c_float * 2)(), (C.c_double * 6)(), (C.c_uint32 * 4)()
+
+    def arr(x, shape, what):
+        if x is None:
+            return None
+        x = np.ascontiguousarray(x, np.float64)
+        if x.shape != shape:
+            raise ValueError(f"{what} must be {shape}")
+        return x
+    a, then_a = arr(a, (desc.n_prims, 9), "a"), arr(then_a, (desc.n_prims, 9), "then_a")
+    xv, then_xv = arr(xv, (desc.n_xforms, 4, 3), "xv"), arr(then_xv, (desc.n_xforms, 4, 3), "then_xv")
+    if a is None:
+        raise ValueError("a is required")
+
+    def ptr(x):
+        return x.ctypes.data if x is not None and x.size else None
+    blob = np.zeros(table_bytes, np.uint8)
+    if then_a is None:
+        _check(L.rtw_world_rebuild_tables_host(C.byref(desc), flags, ptr(a), ptr(xv), blob.ctypes.data, table_bytes,
+                                               cull, bounds, info))
+    else:
+        _check(L.rtw_world_rebuild_refit_tables_host(C.byref(desc), flags, ptr(a), ptr(xv), ptr(then_a), ptr(then_xv),
+                                                     blob.ctypes.data, table_bytes, cull, bounds, info))
+    return {"blob": blob, "cull": np.array(cull[:], np.float32), "bounds": np.array(bounds[:], np.float64),
+            "info": {"nodes": info[0], "leaves": info[1], "max_depth": info[2], "max_leaf": info[3]}}
+
+
 def desc_numbers(desc: WorldDesc):
     """The numbers an update replaces, out of a descriptor: a (n_prims, 9) and xv (n_xforms, 4, 3)."""
     a = np.array([list(desc.prims[i].a) for i in range(desc.n_prims)], np.float64).reshape(desc.n_prims, 9)
@@ -334,6 +367,32 @@ class DeviceWorld:
         _check(_wlib().rtw_world_update_device(self.h, C.c_void_p(a_ptr) if a_ptr else None,
                                                C.c_void_p(xv_ptr) if xv_ptr else None,
                                                C.c_void_p(stream) if stream else None))
+
+    def rebuild(self, prims, xforms=None):
+        """rtw_world_rebuild: the arguments of update(); the world takes the numbers and gets a
+        new tree built from them on the device (dynamic worlds whose BVH has leaves of one
+        primitive: >= 512 primitives; others raise RTW_UNSUPPORTED)."""
+        if isinstance(prims, WorldDesc):
+            pp, n, xp, nx = prims.prims, prims.n_prims, prims.xforms, prims.n_xforms
+        else:
+            pp, n = prims, (len(prims) if prims is not None else 0)
+            xp, nx = xforms, (len(xforms) if xforms is not None else 0)
+        _check(_wlib().rtw_world_rebuild(self.h, C.cast(pp, C.c_void_p) if n else None, n,
+                                         C.cast(xp, C.c_void_p) if nx else None, nx))
+
+    def rebuild_device(self, a_ptr: int, xv_ptr: int | None = None, stream: int | None = None):
+        """rtw_world_rebuild_device: the arguments of update_device().  Waits for one readback
+        (validation, the new depth and the nodes per level), then enqueues the commit."""
+        _check(_wlib().rtw_world_rebuild_device(self.h, C.c_void_p(a_ptr) if a_ptr else None,
+                                                C.c_void_p(xv_ptr) if xv_ptr else None,
+                                                C.c_void_p(stream) if stream else None))
+
+    def bvh_cost(self, stream: int | None = None) -> float:
+        """rtw_world_bvh_cost: sum over nodes of the two child boxes' half-areas over the root
+        box's, from the node table as stored; waits for its 8-byte readback."""
+        out = C.c_double(0.0)
+        _check(_wlib().rtw_world_bvh_cost(self.h, C.c_void_p(stream) if stream else None, C.byref(out)))
+        return float(out.value)
 
     def table_bytes(self) -> int:
         return int(_wlib().rtw_world_table_bytes(self.h))
@@ -438,4 +497,4 @@ class DeviceWorld:
             pass
 
 
-__all__ = ["BuiltScene", "DeviceWorld", "refit_tables_host", "desc_numbers", "render_world", "load_png", "earth_map", "synthetic_world_map", "RtwError", "SCENES"]
+__all__ = ["BuiltScene", "DeviceWorld", "refit_tables_host", "rebuild_tables_host", "desc_numbers", "render_world", "load_png", "earth_map", "synthetic_world_map", "RtwError", "SCENES"]
