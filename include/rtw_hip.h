@@ -261,7 +261,11 @@ enum {
    * for another lane's unit; wave-iterations run in that state; lane-slots of those iterations with no
    * sample in flight or to start, the lane's own or another lane's.  The last two are counted whether
    * or not the launch hands samples out. */
-  RTW_STAT_TAIL_HELPED_SAMPLES = 17, RTW_STAT_TAIL_WAVE_ITERS = 18, RTW_STAT_TAIL_IDLE_LANE_ITERS = 19
+  RTW_STAT_TAIL_HELPED_SAMPLES = 17, RTW_STAT_TAIL_WAVE_ITERS = 18, RTW_STAT_TAIL_IDLE_LANE_ITERS = 19,
+  /* megakernel, primary-first loop: units, and their samples, finished without tracing because no camera
+   * ray of their tile can hit a sphere (each sample adds the background once; counted in SAMPLES and
+   * SEGMENTS as a traced miss is, in no other word) */
+  RTW_STAT_UNTRACED_UNITS = 20, RTW_STAT_UNTRACED_SAMPLES = 21
 };
 int rtw_render_stats_ex(rtw_scene scene, const rtw_camera *cam, const rtw_params *params,
                         void *workspace, size_t workspace_bytes, uint64_t *stats_out, uint32_t n_words);

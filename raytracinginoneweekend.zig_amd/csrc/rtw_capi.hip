@@ -263,6 +263,7 @@ void fill_args(rtwk::TraceArgs<R>& a, const rtwk::SceneView<R>& v, const rtw_cam
   // (rtw_fill_trace_args), each the faster in the in-process A/Bs
   // (profiles/r03/unit_order_ab.txt); RTW_UNIT_ORDER=fwd|rev overrides.
   a.unit_order = unit_order(0u);
+  a.empty_on = 0u;  // (launch_engine)
   a.partial = reinterpret_cast<double*>(ws + L.partial_off);
   a.counter = reinterpret_cast<uint32_t*>(ws + L.counter_off);
   a.stats = reinterpret_cast<unsigned long long*>(ws + L.stats_off);
@@ -307,6 +308,12 @@ int launch_engine(const rtwk::SceneView<R>& view, const rtw_camera* cam, const r
                      : 0u;
   // Its tail dealing, where launch_all found room for the tail blocks (tail_lds, after `lds`).
   a.tail_on = (a.primary_on && tail_lds) ? 1u : 0u;
+  // Its batches of tiles that no camera ray can hit a sphere from are finished without tracing: the beam pass
+  // answers for the wide spheres too, on the lanes after the slots, where they fit; at max_depth 0 a sample
+  // adds nothing, not the background.  (RTW_TRACE_EMPTY=0, -DRTW_MEASURE only: off, for the A/B.)
+  const uint32_t n_wide = a.sc.g_static_wide + (a.sc.g_moving_wide - a.sc.g_static);
+  a.empty_on = (a.primary_on && a.max_depth >= 1u && a.sc.n_clusters * rtwk::kClusterSlots + n_wide <= 64u) ? 1u : 0u;
+  if (const char* ek = dev_knob("RTW_TRACE_EMPTY"); ek && ek[0] == '0') a.empty_on = 0u;
   if (a.tail_on) lds += tail_lds;
   if (p->engine == RTW_ENGINE_WAVEFRONT) {
     if (mode == 2) return rtw_fail(RTW_UNSUPPORTED, "phase profile runs on the megakernel engine");

@@ -775,6 +775,8 @@ struct KStats {
   // its tail (the wave's queue ran dry): samples traced for another lane's unit, wave-iterations, lane-slots of
   // those with no sample in flight or to start, its own or another lane's
   unsigned long long tail_helped = 0, tail_iters = 0, tail_idle = 0;
+  // units and samples of batches finished without tracing (TraceArgs::empty_on)
+  unsigned long long empty_units = 0, empty_samples = 0;
   uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t t_last = 0;
 };

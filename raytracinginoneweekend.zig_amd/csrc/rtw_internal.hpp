@@ -79,6 +79,9 @@ struct TraceArgs {
   uint32_t primary_on;            // the primary-first loop runs (f64 unmasked; clusters on, one 64-slot block)
   uint32_t tail_on;               // that loop deals a wave's remaining samples to its idle lanes once the queue is
                                   // dry (the launch's LDS then holds trace_tail_lds_bytes more)
+  uint32_t empty_on;              // that loop finishes the units of a batch whose tile no camera ray can hit a sphere
+                                  // from without tracing them: the slots and the wide spheres fit the 64 lanes of
+                                  // the beam pass together, and max_depth >= 1 (a miss adds the background)
   uint64_t seed_base;            // SplitMix64(seed).next()
   double* partial;                // [n_chunks][row_count*W][3] chunk sums
   uint32_t* counter;              // work-queue head (zeroed before launch)

@@ -161,23 +161,25 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
       const uint32_t rank = mbcnt64(needmask);
       const uint32_t rem = qend - qnext;
       uint32_t base2 = 0;
-      if (n > rem) {
+      uint32_t nb_bm0 = 0u, nb_bm1 = 0u;
+      // (PF: a loop only over batches finished without tracing, TraceArgs::empty_on, below)
+      if (n > rem) for (;;) {
         uint32_t b = 0;
         if (lid == 0) b = atomicAdd(RTW_KA(counter), kBatch);
         if constexpr (PF)  // (lane 0's value by a constant address: __shfl's lane arithmetic was held in a register)
           base2 = (uint32_t)__builtin_amdgcn_ds_bpermute(0, (int)b);
         else
           base2 = __shfl(b, 0);
-      }
-      uint32_t nb_bm0 = 0u, nb_bm1 = 0u;
-      if constexpr (PF) {
-        if (n > rem)  // (a dealt batch is a 64-aligned batch in every order)
+        if constexpr (!PF) {
+          break;
+        } else {
+          // (a dealt batch is a 64-aligned batch in every order)
           decode_batch(dealt_unit(base2, *opaque(kargs<R>())) & ~63u, nb_tx, nb_ty, nb_c, nb_pad);
-        // The new batch's mask: which clustered slots can a camera ray of its
-        // tile hit (rtw_beam.hpp)?  Lane j answers for slot j; every lane of
-        // the wave is here (wave-uniform branch at the loop's top).  A batch
-        // past the queue's end names no tile: its units are refused below.
-        if (n > rem && RTW_KA(primary_on)) {
+          // The new batch's mask: which clustered slots can a camera ray of its
+          // tile hit (rtw_beam.hpp)?  Lane j answers for slot j; every lane of
+          // the wave is here (wave-uniform branch at the loop's top).  A batch
+          // past the queue's end names no tile: its units are refused below.
+          if (!RTW_KA(primary_on)) break;
           const auto* ka = opaque(kargs<R>());
           const double org[3] = {ka->origin[0], ka->origin[1], ka->origin[2]};
           const double llc[3] = {ka->llc[0], ka->llc[1], ka->llc[2]};
@@ -189,11 +191,17 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
           const rtwb::Beam beam =
               rtwb::tile_beam(org, llc, hor, ver, cu, cv, ka->lens_radius, ka->W, ka->H, px0, px1,
                               ka->row_begin + ly0 * ka->row_stride, ka->row_begin + ly1 * ka->row_stride);
+          // TraceArgs::empty_on: the lanes after the slots answer for the wide spheres, lane n_slots + w for
+          // the w-th of [0, g_static_wide) and [g_static, g_moving_wide), with their records of the same tables.
           bool may = false;
-          if (lid < kClusterSlots * ka->sc.n_clusters) {  // (primary_on: one 64-slot block)
+          const uint32_t n_slots = kClusterSlots * ka->sc.n_clusters;  // (primary_on: one 64-slot block)
+          const uint32_t n_wide = ka->empty_on ? ka->sc.g_static_wide + (ka->sc.g_moving_wide - ka->sc.g_static) : 0u;
+          if (lid < n_slots + n_wide) {
             uint32_t slot = lid;  // (laundered: the table's address is made here, not held across the loop)
             asm volatile("" : "+v"(slot));
-            const uint32_t k = T.cpos[slot];
+            const uint32_t w = lid - n_slots;
+            const uint32_t k = lid < n_slots ? T.cpos[slot]
+                                             : (w < ka->sc.g_static_wide ? w : ka->sc.g_static + (w - ka->sc.g_static_wide));
             const uint32_t meta = T.meta[k];
             const bool mv = (meta & kMoving) != 0;
             const uint32_t g = mv ? (meta >> 2) & 63u : 0u;
@@ -202,12 +210,38 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
             const double dc[3] = {(double)T.sph[8 * k + 3], (double)T.sph[8 * k + 4], (double)T.sph[8 * k + 5]};
             may = rtwb::beam_may_hit(beam, c0, dc, (double)T.rad[k], mv, g0, g1, ka->time0, ka->time1);
           }
-          const uint64_t bal = wballot(may);  // bit j = slot j; the survivor loop wants slot 32h + r at bit 31 - r of word h
+          // bit j = slot j; the survivor loop wants slot 32h + r at bit 31 - r of word h
+          const uint64_t bal = wballot(may && lid < n_slots);
           nb_bm0 = __builtin_bitreverse32((uint32_t)bal);
           nb_bm1 = __builtin_bitreverse32((uint32_t)(bal >> 32));
+          const RTW_CONST uint32_t* cval = cptr(ka->sc.cvalid);  // (dummy slots answer for table position 0)
           if constexpr (STATS) {
-            const RTW_CONST uint32_t* cval = cptr(ka->sc.cvalid);  // (dummy slots answer for table position 0)
             if (lid == 0 && base2 < RTW_KA(total_units)) st.mask_pop += __popc(nb_bm0 & cval[0]) + __popc(nb_bm1 & cval[1]);
+          }
+          // A batch no camera ray of which can hit a sphere, real slot or wide (TraceArgs::empty_on; the host
+          // set it only with max_depth >= 1: at depth 0 a sample ends before its miss adds anything): every
+          // sample of its units is bounce's miss with L.T = (1, 1, 1), so lane j finishes unit base2 + j here —
+          // 0.0, + bg once per sample as that path adds it, stored as publish_unit stores — and the wave
+          // fetches the next batch.  No lane's unit, ray or path changes; a lane waiting for a unit still is.
+          if (!ka->empty_on || base2 >= RTW_KA(total_units)) break;
+          if (((nb_bm0 & cval[0]) | (nb_bm1 & cval[1])) != 0u || wballot(may && lid >= n_slots) != 0ull) break;
+          {
+            const uint32_t l = dealt_unit(base2 + lid, *ka) & 63u;
+            const uint32_t px = nb_tx * kTileW + (l & 7u), ly = nb_ty * kTileH + (l >> 3);
+            if (px < ka->W && ly < ka->row_count) {  // else: a padding unit
+              const uint32_t s0 = nb_c * ka->chunk, ns = min(s0 + ka->chunk, ka->spp) - s0;
+              const double bg0 = (double)ka->bg[0], bg1 = (double)ka->bg[1], bg2 = (double)ka->bg[2];
+              double z = 0.0;  // (laundered, as the take's)
+              asm volatile("" : "+v"(z));
+              double e0 = z, e1 = z, e2 = z;
+#pragma unroll 1
+              for (uint32_t i = 0; i < ns; ++i) e0 += bg0, e1 += bg1, e2 += bg2;
+              double* dst = ka->partial + ((size_t)nb_c * (ka->row_count * ka->W) + (size_t)ly * ka->W + px) * 3;
+              dst[0] = e0;
+              dst[1] = e1;
+              dst[2] = e2;
+              if constexpr (STATS) st.samples += ns, st.segments += ns, st.empty_units++, st.empty_samples += ns;
+            }
           }
         }
       }
@@ -629,6 +663,8 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
       atomicAdd(A.stats + 17, st.tail_helped);
       atomicAdd(A.stats + 18, st.tail_iters);
       atomicAdd(A.stats + 19, st.tail_idle);
+      atomicAdd(A.stats + 20, st.empty_units);
+      atomicAdd(A.stats + 21, st.empty_samples);
     }
   }
   if constexpr (MODE == 2) {
