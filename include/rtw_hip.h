@@ -265,7 +265,11 @@ enum {
   /* megakernel, primary-first loop: units, and their samples, finished without tracing because no camera
    * ray of their tile can hit a sphere (each sample adds the background once; counted in SAMPLES and
    * SEGMENTS as a traced miss is, in no other word) */
-  RTW_STAT_UNTRACED_UNITS = 20, RTW_STAT_UNTRACED_SAMPLES = 21
+  RTW_STAT_UNTRACED_UNITS = 20, RTW_STAT_UNTRACED_SAMPLES = 21,
+  /* megakernel, primary-first loop: atomics issued on the launch's unit queue (a claim takes one or
+   * several 64-unit batches; the count varies from run to run), and beam passes made (a fetched batch of
+   * the tile of the wave's last pass reuses it; PRIMARY_MASK_POPCOUNT stays per fetched batch) */
+  RTW_STAT_QUEUE_CLAIMS = 22, RTW_STAT_BEAM_PASSES = 23
 };
 int rtw_render_stats_ex(rtw_scene scene, const rtw_camera *cam, const rtw_params *params,
                         void *workspace, size_t workspace_bytes, uint64_t *stats_out, uint32_t n_words);

@@ -19,6 +19,7 @@
 
 #include "rtw_hip.h"
 #include "rtw_capi_shared.hpp"
+#include "rtw_claim.hpp"
 #include "rtw_internal.hpp"
 #include "rtw_math.hpp"
 #include "rtw_scene_pack.hpp"
@@ -320,6 +321,15 @@ int launch_engine(const rtwk::SceneView<R>& view, const rtw_camera* cam, const r
     return rtw_run_wavefront<R>(a, p, ws, L, dev, lds, stream, mode == 1);
   }
   const uint32_t grid = std::max(1u, std::min(grid_cap, (a.total_units + 255) / 256));
+  // Its guided claims (rtw_claim.hpp): several batches per atomic in a run of proven-empty batches while the
+  // queue is long, from the waves of this grid.  Only in a launch that can make such a claim: batches are
+  // proven empty (empty_on) and the queue is at least 2 x claim_waves batches long, so that the guided K is 2
+  // or more at its head; in any other launch every claim would be one batch, and the reserve's bookkeeping
+  // cost a 20-sample pass of the cover frame 0.9 % (profiles/r19/README.md).
+  // (RTW_TRACE_CLAIM=1, -DRTW_MEASURE only: claims of one batch and no proof reuse, for the A/B.)
+  const uint32_t claim_waves = rtwc::kClaimDiv * grid * (uint32_t)(rtwk::kTraceBlock / 64);
+  a.claim_waves = (a.empty_on && a.total_units / rtwk::kBatch >= 2u * claim_waves) ? claim_waves : 0u;
+  if (const char* ck = dev_knob("RTW_TRACE_CLAIM"); ck && ck[0] == '1') a.claim_waves = 0u;
   hipError_t e;
   if constexpr (sizeof(R) == 8)
     e = rtwk::launch_trace_f64(a, grid, lds, stream, mode, masked);

@@ -777,6 +777,8 @@ struct KStats {
   unsigned long long tail_helped = 0, tail_iters = 0, tail_idle = 0;
   // units and samples of batches finished without tracing (TraceArgs::empty_on)
   unsigned long long empty_units = 0, empty_samples = 0;
+  // atomics issued on the unit queue and beam passes made (rtw_claim.hpp; the primary-first loop)
+  unsigned long long claims = 0, beam_passes = 0;
   uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t t_last = 0;
 };

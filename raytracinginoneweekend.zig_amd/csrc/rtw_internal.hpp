@@ -82,6 +82,9 @@ struct TraceArgs {
   uint32_t empty_on;              // that loop finishes the units of a batch whose tile no camera ray can hit a sphere
                                   // from without tracing them: the slots and the wide spheres fit the 64 lanes of
                                   // the beam pass together, and max_depth >= 1 (a miss adds the background)
+  uint32_t claim_waves;           // that loop claims several batches per queue atomic and reuses a tile's beam pass
+                                  // (rtw_claim.hpp): kClaimDiv x the waves of the grid; 0: claims of one batch (a
+                                  // launch without empty_on, or with a queue too short for a claim of two)
   uint64_t seed_base;            // SplitMix64(seed).next()
   double* partial;                // [n_chunks][row_count*W][3] chunk sums
   uint32_t* counter;              // work-queue head (zeroed before launch)
@@ -120,7 +123,11 @@ bool trace_primary_first(int precision, bool masked);
 // which clustered slots its tile's camera rays may hit (two words per lane, bit order of SceneView::cvalid),
 // then the wave's current batch's (a copy per lane), kPrimaryLdsBytesPerWave.  (8: alignment of the home block)
 constexpr size_t kHomeLdsBytesPerWave = 2560;
-constexpr size_t kPrimaryLdsBytesPerWave = 4 * 64 * 4;
+// After them the wave's claim words (rtw_claim.hpp): its reserve of claimed batches, the tile of its last
+// beam pass with its verdict, that pass's two mask words and its run of proven-empty batches,
+// kClaimLdsBytesPerWave.
+constexpr size_t kClaimLdsBytesPerWave = 32;
+constexpr size_t kPrimaryLdsBytesPerWave = 4 * 64 * 4 + kClaimLdsBytesPerWave;
 size_t trace_home_lds_bytes(int precision, bool masked);
 constexpr int kTraceBlock = 256;
 // The primary-first loop's tail dealing (TraceArgs::tail_on): a block per wave after the workgroup's home

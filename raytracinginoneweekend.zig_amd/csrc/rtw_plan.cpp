@@ -51,7 +51,13 @@ int validate_params(const rtw_params* p, std::string& msg) {
   if (p->engine == RTW_ENGINE_WAVEFRONT && p->max_depth > 0xFFFFu)
     return fail(msg, RTW_UNSUPPORTED, "wavefront engine: max_depth %u > 65535", p->max_depth);
   const uint64_t units = total_units(p);
-  if (units > 0x7FFFFFFFull)  // headroom: waves overshoot the queue by < 2^31 units
+  // Headroom: waves overshoot the queue by < 2^31 units.  A claim of the primary-first loop (rtw_claim.hpp) is
+  // at most kClaimMax = 8 batches, so a wave's claim that crosses the end adds at most 8 x 64 units.  A wave of
+  // a launch without the tail goes on claiming one batch at a time past the end, but every such claim is
+  // made for a lane without a unit and retires it (its unit is refused: the lane is done), so a wave makes
+  // at most 64 of them.  A grid of G workgroups (4 waves each; G <= CUs x resident workgroups per CU) ends
+  // the counter below units + 4 G x (8 + 64) x 64: G = 2^15 workgroups would still stay under units + 2^30.
+  if (units > 0x7FFFFFFFull)
     return fail(msg, RTW_UNSUPPORTED, "%llu work units exceed the 32-bit queue; raise params.chunk",
                 (unsigned long long)units);
   return RTW_OK;

@@ -38,6 +38,7 @@
 
 #include <type_traits>
 
+#include "rtw_claim.hpp"
 #include "rtw_device.hpp"
 
 // (Round 4) The lane's state flags (have_unit, have_ray, done, shading) as bits of one
@@ -137,6 +138,23 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
   constexpr uint32_t kPm = 4 * 64, kBm = 6 * 64;
   uint32_t* const h_me = h_u32 + lid;
   constexpr bool PF = Cfg::kPrimaryFirst;
+  // Cfg::kPrimaryFirst: the wave's claim words after the masks (wave-uniform, kClaimLdsBytesPerWave):
+  // h_u32[kRs], [kRs + 1] = the reserve of claimed batches [next, end), [kRs + 2] = the tile of the wave's
+  // last beam pass with its verdict, [kRs + 3], [kRs + 4] = that pass's mask words, [kRs + 5] = its run of
+  // proven-empty batches (rtw_claim.hpp; take_units).
+  // In LDS, not in registers held across the closest hit.
+  constexpr uint32_t kRs = 8 * 64;
+  // (made from the lane's own h_me where used, the lane index laundered: no address of them lives in a register
+  // of the loop)
+  auto claim_words = [&]() __attribute__((always_inline)) -> uint32_t* {
+    uint32_t l = lid;
+    asm volatile("" : "+v"(l));
+    return h_me - l + kRs;
+  };
+  if constexpr (PF) {
+    uint32_t* const cwd = claim_words();
+    cwd[0] = 0u, cwd[1] = 0u, cwd[2] = rtwc::kNoPass, cwd[5] = 0u;
+  }
   // Cfg::kPrimaryFirst: (tile x, tile y, chunk) of a newly fetched unit batch (wave-uniform).  A batch is 64
   // aligned units = one (tile, chunk): decoded once, for the tile's beam.
   // (nb_pad is never written.  The kernels were measured with a 64-bit word in this place; without it the
@@ -153,7 +171,9 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
     tx = tile - ty * txs;
   };
   // ---- take units for lanes that need one (wave-uniform control) ----
-  auto take_units = [&]() {
+  // (always_inline: the primary-first kernel calls it from both of its loops, and out of line its captures
+  // are in scratch memory)
+  auto take_units = [&]() __attribute__((always_inline)) {
     const bool need = !have_unit && !done;
     const uint64_t needmask = __ballot(need);
     if (needmask) {
@@ -163,16 +183,39 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
       uint32_t base2 = 0;
       uint32_t nb_bm0 = 0u, nb_bm1 = 0u;
       // (PF: a loop only over batches finished without tracing, TraceArgs::empty_on, below)
+      // PF with TraceArgs::claim_waves (rtw_claim.hpp): the wave claims K batches with one atomic and fetches
+      // the others from its reserve, and a batch of the tile of the wave's last beam pass reuses that pass.
+      // The reserve and the last pass — its tile with its verdict, its mask words — are wave-uniform words of
+      // the wave's LDS (h_u32[kRs ...]), read and written where used: nothing of them is held in a register
+      // across the beam pass or the closest hit.  Ascending order: a claim is made only with an empty
+      // reserve, the counter only grows, and the reserve is handed out from its low end; a batch at or past
+      // the queue's end empties it (after_fetch), so one refused unit still means all later ones are refused.
+      uint32_t nb_empty = 0u;
       if (n > rem) for (;;) {
         uint32_t b = 0;
-        if (lid == 0) b = atomicAdd(RTW_KA(counter), kBatch);
-        if constexpr (PF)  // (lane 0's value by a constant address: __shfl's lane arithmetic was held in a register)
-          base2 = (uint32_t)__builtin_amdgcn_ds_bpermute(0, (int)b);
-        else
-          base2 = __shfl(b, 0);
         if constexpr (!PF) {
+          if (lid == 0) b = atomicAdd(RTW_KA(counter), kBatch);
+          base2 = __shfl(b, 0);
           break;
         } else {
+          const uint32_t cw = RTW_KA(claim_waves);
+          uint32_t* const cwd = claim_words();
+          rtwc::Reserve rs;
+          if (cw != 0u) rs.next = cwd[0], rs.end = cwd[1];
+          if (!rtwc::reserve_has(rs)) {
+            const uint32_t k = cw != 0u ? rtwc::claim_k(cwd[5], rs.end, RTW_KA(total_units), cw) : 1u;
+            if (lid == 0) b = atomicAdd(RTW_KA(counter), k * kBatch);
+            // (lane 0's value by a constant address: __shfl's lane arithmetic was held in a register)
+            rs = rtwc::after_claim((uint32_t)__builtin_amdgcn_ds_bpermute(0, (int)b), k);
+            if constexpr (STATS) {
+              if (lid == 0) st.claims++;
+            }
+          }
+          base2 = rs.next;
+          if (cw != 0u) {
+            rs = rtwc::after_fetch(rs, base2, RTW_KA(total_units));
+            cwd[0] = rs.next, cwd[1] = rs.end;  // (every lane, the same words)
+          }
           // (a dealt batch is a 64-aligned batch in every order)
           decode_batch(dealt_unit(base2, *opaque(kargs<R>())) & ~63u, nb_tx, nb_ty, nb_c, nb_pad);
           // The new batch's mask: which clustered slots can a camera ray of its
@@ -181,50 +224,68 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
           // past the queue's end names no tile: its units are refused below.
           if (!RTW_KA(primary_on)) break;
           const auto* ka = opaque(kargs<R>());
-          const double org[3] = {ka->origin[0], ka->origin[1], ka->origin[2]};
-          const double llc[3] = {ka->llc[0], ka->llc[1], ka->llc[2]};
-          const double hor[3] = {ka->horizontal[0], ka->horizontal[1], ka->horizontal[2]};
-          const double ver[3] = {ka->vertical[0], ka->vertical[1], ka->vertical[2]};
-          const double cu[3] = {ka->cu[0], ka->cu[1], ka->cu[2]}, cv[3] = {ka->cv[0], ka->cv[1], ka->cv[2]};
-          const uint32_t px0 = nb_tx * kTileW, ly0 = nb_ty * kTileH;
-          const uint32_t px1 = min(px0 + (kTileW - 1u), ka->W - 1u), ly1 = min(ly0 + (kTileH - 1u), ka->row_count - 1u);
-          const rtwb::Beam beam =
-              rtwb::tile_beam(org, llc, hor, ver, cu, cv, ka->lens_radius, ka->W, ka->H, px0, px1,
-                              ka->row_begin + ly0 * ka->row_stride, ka->row_begin + ly1 * ka->row_stride);
-          // TraceArgs::empty_on: the lanes after the slots answer for the wide spheres, lane n_slots + w for
-          // the w-th of [0, g_static_wide) and [g_static, g_moving_wide), with their records of the same tables.
-          bool may = false;
-          const uint32_t n_slots = kClusterSlots * ka->sc.n_clusters;  // (primary_on: one 64-slot block)
-          const uint32_t n_wide = ka->empty_on ? ka->sc.g_static_wide + (ka->sc.g_moving_wide - ka->sc.g_static) : 0u;
-          if (lid < n_slots + n_wide) {
-            uint32_t slot = lid;  // (laundered: the table's address is made here, not held across the loop)
-            asm volatile("" : "+v"(slot));
-            const uint32_t w = lid - n_slots;
-            const uint32_t k = lid < n_slots ? T.cpos[slot]
-                                             : (w < ka->sc.g_static_wide ? w : ka->sc.g_static + (w - ka->sc.g_static_wide));
-            const uint32_t meta = T.meta[k];
-            const bool mv = (meta & kMoving) != 0;
-            const uint32_t g = mv ? (meta >> 2) & 63u : 0u;
-            const double g0 = mv ? (double)T.tg[4 * g] : 0.0, g1 = mv ? (double)T.tg[4 * g + 1] : 1.0;
-            const double c0[3] = {(double)T.sph[8 * k], (double)T.sph[8 * k + 1], (double)T.sph[8 * k + 2]};
-            const double dc[3] = {(double)T.sph[8 * k + 3], (double)T.sph[8 * k + 4], (double)T.sph[8 * k + 5]};
-            may = rtwb::beam_may_hit(beam, c0, dc, (double)T.rad[k], mv, g0, g1, ka->time0, ka->time1);
+          const uint32_t last = cwd[2];
+          if (cw != 0u && rtwc::same_tile(nb_ty * ka->tiles_x + nb_tx, last)) {
+            nb_bm0 = cwd[3], nb_bm1 = cwd[4];
+            nb_empty = rtwc::pass_empty(last);
+          } else {
+            const double org[3] = {ka->origin[0], ka->origin[1], ka->origin[2]};
+            const double llc[3] = {ka->llc[0], ka->llc[1], ka->llc[2]};
+            const double hor[3] = {ka->horizontal[0], ka->horizontal[1], ka->horizontal[2]};
+            const double ver[3] = {ka->vertical[0], ka->vertical[1], ka->vertical[2]};
+            const double cu[3] = {ka->cu[0], ka->cu[1], ka->cu[2]}, cv[3] = {ka->cv[0], ka->cv[1], ka->cv[2]};
+            const uint32_t px0 = nb_tx * kTileW, ly0 = nb_ty * kTileH;
+            const uint32_t px1 = min(px0 + (kTileW - 1u), ka->W - 1u), ly1 = min(ly0 + (kTileH - 1u), ka->row_count - 1u);
+            const rtwb::Beam beam =
+                rtwb::tile_beam(org, llc, hor, ver, cu, cv, ka->lens_radius, ka->W, ka->H, px0, px1,
+                                ka->row_begin + ly0 * ka->row_stride, ka->row_begin + ly1 * ka->row_stride);
+            // TraceArgs::empty_on: the lanes after the slots answer for the wide spheres, lane n_slots + w for
+            // the w-th of [0, g_static_wide) and [g_static, g_moving_wide), with their records of the same tables.
+            bool may = false;
+            const uint32_t n_slots = kClusterSlots * ka->sc.n_clusters;  // (primary_on: one 64-slot block)
+            const uint32_t n_wide = ka->empty_on ? ka->sc.g_static_wide + (ka->sc.g_moving_wide - ka->sc.g_static) : 0u;
+            if (lid < n_slots + n_wide) {
+              uint32_t slot = lid;  // (laundered: the table's address is made here, not held across the loop)
+              asm volatile("" : "+v"(slot));
+              const uint32_t w = lid - n_slots;
+              const uint32_t k = lid < n_slots ? T.cpos[slot]
+                                               : (w < ka->sc.g_static_wide ? w : ka->sc.g_static + (w - ka->sc.g_static_wide));
+              const uint32_t meta = T.meta[k];
+              const bool mv = (meta & kMoving) != 0;
+              const uint32_t g = mv ? (meta >> 2) & 63u : 0u;
+              const double g0 = mv ? (double)T.tg[4 * g] : 0.0, g1 = mv ? (double)T.tg[4 * g + 1] : 1.0;
+              const double c0[3] = {(double)T.sph[8 * k], (double)T.sph[8 * k + 1], (double)T.sph[8 * k + 2]};
+              const double dc[3] = {(double)T.sph[8 * k + 3], (double)T.sph[8 * k + 4], (double)T.sph[8 * k + 5]};
+              may = rtwb::beam_may_hit(beam, c0, dc, (double)T.rad[k], mv, g0, g1, ka->time0, ka->time1);
+            }
+            // bit j = slot j; the survivor loop wants slot 32h + r at bit 31 - r of word h
+            const uint64_t bal = wballot(may && lid < n_slots);
+            nb_bm0 = __builtin_bitreverse32((uint32_t)bal);
+            nb_bm1 = __builtin_bitreverse32((uint32_t)(bal >> 32));
+            // The tile's verdict: no camera ray of it can hit a sphere, real slot or wide (TraceArgs::empty_on).
+            const RTW_CONST uint32_t* cval = cptr(ka->sc.cvalid);  // (dummy slots answer for table position 0)
+            nb_empty = (ka->empty_on && ((nb_bm0 & cval[0]) | (nb_bm1 & cval[1])) == 0u &&
+                        wballot(may && lid >= n_slots) == 0ull)
+                           ? 1u
+                           : 0u;
+            cwd[2] = rtwc::pass_word(nb_ty * ka->tiles_x + nb_tx, nb_empty);
+            cwd[3] = nb_bm0, cwd[4] = nb_bm1;
+            if constexpr (STATS) {
+              if (lid == 0 && base2 < RTW_KA(total_units)) st.beam_passes++;
+            }
           }
-          // bit j = slot j; the survivor loop wants slot 32h + r at bit 31 - r of word h
-          const uint64_t bal = wballot(may && lid < n_slots);
-          nb_bm0 = __builtin_bitreverse32((uint32_t)bal);
-          nb_bm1 = __builtin_bitreverse32((uint32_t)(bal >> 32));
-          const RTW_CONST uint32_t* cval = cptr(ka->sc.cvalid);  // (dummy slots answer for table position 0)
+          const RTW_CONST uint32_t* cval = cptr(ka->sc.cvalid);
+          if (base2 < RTW_KA(total_units)) cwd[5] = rtwc::run_after(cwd[5], nb_empty);
+          // (per fetched batch, its pass made or reused)
           if constexpr (STATS) {
             if (lid == 0 && base2 < RTW_KA(total_units)) st.mask_pop += __popc(nb_bm0 & cval[0]) + __popc(nb_bm1 & cval[1]);
           }
-          // A batch no camera ray of which can hit a sphere, real slot or wide (TraceArgs::empty_on; the host
-          // set it only with max_depth >= 1: at depth 0 a sample ends before its miss adds anything): every
+          // A batch no camera ray of which can hit a sphere (the host set empty_on
+          // only with max_depth >= 1: at depth 0 a sample ends before its miss adds anything): every
           // sample of its units is bounce's miss with L.T = (1, 1, 1), so lane j finishes unit base2 + j here —
           // 0.0, + bg once per sample as that path adds it, stored as publish_unit stores — and the wave
           // fetches the next batch.  No lane's unit, ray or path changes; a lane waiting for a unit still is.
-          if (!ka->empty_on || base2 >= RTW_KA(total_units)) break;
-          if (((nb_bm0 & cval[0]) | (nb_bm1 & cval[1])) != 0u || wballot(may && lid >= n_slots) != 0ull) break;
+          if (nb_empty == 0u || base2 >= RTW_KA(total_units)) break;
           {
             const uint32_t l = dealt_unit(base2 + lid, *ka) & 63u;
             const uint32_t px = nb_tx * kTileW + (l & 7u), ly = nb_ty * kTileH + (l >> 3);
@@ -665,6 +726,8 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
       atomicAdd(A.stats + 19, st.tail_idle);
       atomicAdd(A.stats + 20, st.empty_units);
       atomicAdd(A.stats + 21, st.empty_samples);
+      atomicAdd(A.stats + 22, st.claims);
+      atomicAdd(A.stats + 23, st.beam_passes);
     }
   }
   if constexpr (MODE == 2) {

@@ -41,7 +41,8 @@ STAT_NAMES = ["samples", "segments", "f32_skips", "cand_wave_iters", "cand_lanes
               "drain_samples", "cluster_wave_tests", "cluster_wave_skips", "drain_wave_iters", "primary_rounds",
               "primary_idle_lanes"]  # RTW_STAT_*
 STAT_NAMES_EX = STAT_NAMES + ["primary_mask_popcount", "tail_helped_samples", "tail_wave_iters",
-                              "tail_idle_lane_iters", "untraced_units", "untraced_samples"]  # rtw_render_stats_ex: word 16 on
+                              "tail_idle_lane_iters", "untraced_units", "untraced_samples", "queue_claims",
+                              "beam_passes"]  # rtw_render_stats_ex: word 16 on (24 = RTW_STATS_WORDS_EX)
 DEFAULT_CHUNK = 20
 COVER_BACKGROUND = (0.70, 0.80, 1.00)
 
