@@ -879,6 +879,105 @@ int rtw_scene_trace(rtw_scene s, const rtw_ray *rays, uint64_t n, rtw_hit *hits_
  * workgroup}. */
 int rtw_world_query_info(rtw_world w, const rtw_query_opts *opts, uint32_t info_out[4]);
 
+/* =================================================== temporal accumulation ===
+ *   An animation's frames share what they see: each pixel's
+ * first-hit surface point is followed back into the previous frame, and where it
+ * was visible there the frame's mean is blended into a running mean kept per
+ * pixel, with the luminance moments that give the denoiser a variance.  New
+ * symbols only: a render without these calls is untouched.  First-hit
+ * reprojection only: what a mirror or a glass shows is accumulated at the
+ * mirror's own surface point.
+ *
+ * One frame: render (seed + k: equal seeds give equal noise, which no mean
+ * reduces), rtw_pixel_rays_device, rtw_world_trace_device, rtw_world_guides_device,
+ * rtw_world_prev_points_device with the previous frame's numbers,
+ * rtw_temporal_device, then rtw_denoise_device on d_mean_out with d_var_out as
+ * its d_var.  The caller ping-pongs two history images.
+ *
+ * History record, one per pixel, rows contiguous as for rtw_denoise_device. */
+typedef struct {
+  float mean[3];   /* accumulated linear colour */
+  float len;       /* frames in it; 0: no history */
+  float m1, m2;    /* accumulated luminance and squared luminance */
+  float depth;     /* the guide's depth and prim of the frame that wrote the record: */
+  uint32_t prim;   /* the next frame checks visibility against them */
+} rtw_history;     /* 32 bytes; buffers of it are 16-byte aligned */
+
+typedef struct {   /* every field 0 = its default */
+  uint32_t max_history;  /* 1..4096, default 32: the blend weight never falls below 1 / (max_history + 1) */
+  double depth_tol;      /* finite, > 0, default 0.02: relative to the larger of the two depths */
+  uint32_t min_len_var;  /* >= 2, default 4: shorter histories report RTW_VAR_UNKNOWN */
+  uint32_t flags;        /* 0 */
+} rtw_temporal_opts;
+
+/* Per pixel (x, image row y) — csrc/rtw_temporal.hpp has the arithmetic, f64 with
+ * one IEEE operation per operator, each output rounded to f32 once; the device's
+ * bytes are the host's:
+ *  1. Where it was.  A hit pixel (guide prim != 0) with d_prev_p: the point is
+ *     projected through cam_prev (Cramer's rule on d0 + s h + t v = mu q, q = the
+ *     point - origin, d0 = lower_left_corner - origin); invalid when an input is
+ *     not finite, the determinant is 0 or mu <= 0; fx = s (W - 1) - 0.5,
+ *     fy = (H - 1) + 0.5 - t (H - 1), expected depth tp = 1 / mu; an fx or fy
+ *     within 2^-10 of an integer becomes that integer.  A hit pixel with
+ *     d_prev_p == NULL (nothing moved): its own position, tp = its depth.  A miss:
+ *     its own position if cam_prev and cam are bytewise equal, else no history.
+ *  2. The four bilinear taps around (fx, fy): a tap counts iff it lies inside the
+ *     image, its record has len > 0 and the pixel's prim, and for a hit
+ *     |rec.depth - tp| <= depth_tol * max(rec.depth, tp).  Their weights summed in
+ *     row-major order below 2^-7: no history.
+ *  3. No history: {mean, len 1, m1 = Y, m2 = Y Y}.  Else hist = the
+ *     weight-normalised taps, N = min(hist.len, max_history), a = 1 / (N + 1),
+ *     colour, m1, m2 = hist + a (cur - hist), len = N + 1.  depth, prim: the guide's.
+ *  4. d_var_out = max(0, m2 - m1 m1) / len when len >= min_len_var, else
+ *     RTW_VAR_UNKNOWN.
+ * d_hist_in == NULL: the first frame, no pixel has history.  d_mean_out
+ * (W*H*3 floats, the record's mean) and d_var_out (W*H floats) are optional,
+ * d_hist_out is required; outputs may not alias inputs.  d_prev_p: W*H*3 doubles
+ * or NULL.  Asynchronous on `stream`, graph-capturable, no workspace, no state, no
+ * atomics: the same inputs give the same bytes.  RTW_EINVAL for null pointers,
+ * width or height < 2 or > 65536, more than 2^28 pixels (an 8-GiB history image),
+ * history or guides not 16-byte aligned, d_prev_p not 8-byte aligned, a float
+ * image not 4-byte aligned, an output whose W*H records overlap an input's or
+ * another output's anywhere (byte ranges are compared, not only the pointers),
+ * opts out of range (opts NULL = defaults). */
+int rtw_temporal_device(const float *d_mean, const rtw_guide *d_guides, const double *d_prev_p,
+                        const rtw_camera *cam_prev, const rtw_camera *cam,
+                        const rtw_history *d_hist_in, uint32_t width, uint32_t height,
+                        const rtw_temporal_opts *opts, rtw_history *d_hist_out,
+                        float *d_mean_out, float *d_var_out, void *stream);
+/* The same on HOST buffers, on the CPU: needs no GPU.  `stream` is ignored. */
+int rtw_temporal_host(const float *mean, const rtw_guide *guides, const double *prev_p,
+                      const rtw_camera *cam_prev, const rtw_camera *cam,
+                      const rtw_history *hist_in, uint32_t width, uint32_t height,
+                      const rtw_temporal_opts *opts, rtw_history *hist_out,
+                      float *mean_out, float *var_out, void *stream);
+
+/* The width*height feature rays of a frame in row-major order, each record
+ * byte-equal to rtw_pixel_ray's.  Asynchronous on `stream`.  RTW_EINVAL for null
+ * pointers, width or height < 2, more than 2^31 pixels, d_rays not 8-byte aligned. */
+int rtw_pixel_rays_device(const rtw_camera *cam, uint32_t width, uint32_t height, rtw_ray *d_rays, void *stream);
+
+/* For each hit record of the world as it is NOW, the same surface point under the
+ * PREVIOUS frame's numbers: d_a_prev (n_prims x 9) and d_xv_prev (n_xforms x
+ * RTW_MAX_XFORM_OPS x 3) shaped as rtw_world_update_device's, NULL = this frame's
+ * values.  Any uploaded world.  d_prev_p: n x 3 doubles.  The surface
+ * parametrisation comes from the record alone, nothing is inverted numerically:
+ * a sphere's outward object-space normal is the record's normal (negated when
+ * front == 0) taken back through the primitive's current transform chain as a
+ * direction, and the point is c_prev + r_prev * n (a moving sphere's centre at
+ * `time`, c0 + (c1 - c0) * ((time - t0) / (t1 - t0))); a rect's is a0' + u (a1' -
+ * a0'), b0' + v (b1' - b0'), k' on its axes; then the previous transform values
+ * are applied forward in the chain's order.  A miss (prim == 0, or a prim beyond
+ * the world's list) gets three zeros.  With both arrays NULL the output is the
+ * record's p bit for bit.  One kernel launch, asynchronous on `stream`; the
+ * device's bytes are the host form's.  RTW_EINVAL for null pointers, buffers not
+ * 8-byte aligned, n > 2^31, a non-finite time; n == 0 launches nothing. */
+int rtw_world_prev_points_device(rtw_world w, const rtw_hit *d_hits, uint64_t n, double time,
+                                 const double *d_a_prev, const double *d_xv_prev,
+                                 double *d_prev_p, void *stream);
+int rtw_world_prev_points_host(const rtw_world_desc *desc, const rtw_hit *hits, uint64_t n, double time,
+                               const double *a_prev, const double *xv_prev, double *prev_p);
+
 #ifdef __cplusplus
 }
 #endif

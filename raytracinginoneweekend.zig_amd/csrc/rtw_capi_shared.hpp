@@ -119,6 +119,9 @@ int rtw_run_wavefront(const rtwk::TraceArgs<R>& ta, const rtw_params* p, unsigne
                       int dev, size_t lds, hipStream_t stream, bool stats);
 // feature buffers (rtw_guides.hip): checks the arguments of a guide entry and fills the feature ray
 int rtw_guide_ray_fill(rtwk::GuideRay& g, const char* who, const rtw_camera* cam, const rtw_params* p, void* d_guides);
+// The device tables of an uploaded world (rtw_world_capi.hip), for entries in other files: RTW_EINVAL when the
+// world is NULL or lives on another device than the current one.
+int rtw_world_view(rtw_world w, const char* who, rtwk::WorldView* view);
 // accumulator passes (rtw_accum_capi.hip)
 bool rtw_accum_size_params(const rtw_params* p, uint32_t n, rtw_params* pp);
 int rtw_accum_pass_begin(rtw_accum a, uint32_t pass_spp, rtw_params* pp, uint64_t* seed_adv);

@@ -9,7 +9,8 @@
 //                            [--pixel-noise X [--min-spp N] [--spp-map FILE]]]
 //              [--denoise [--denoise-levels N] [--denoise-spatial]]
 //              [--pick X,Y] [--focus-at X,Y]
-//              [--frames N [--orbit DEG] [--rebuild-above R]]
+//              [--frames N [--orbit DEG] [--rebuild-above R]
+//                          [--temporal [--temporal-history M] [--denoise ...]]]
 // --pick X,Y traces the feature ray of pixel (X, image row Y) (rtw_pixel_ray,
 // rtw_world_trace) and prints one line,
 //   pick x=.. y=.. prim=.. t=.. p=..,..,.. front=.. material=<kind>   (or: pick x=.. y=.. miss)
@@ -41,6 +42,13 @@
 // right after the creation or the last rebuild, the frame's numbers go through
 // rtw_world_rebuild; one stderr line per rebuild gives the frame and the cost
 // before and after.  The frames' bytes do not depend on it.
+// --temporal (with --frames) accumulates the frames over time:
+// frame k renders with seed S + k, its first hits are followed back into frame
+// k - 1 and blended with what was seen there (at most --temporal-history M
+// frames, default 32); each frame_%04d.ppm is the accumulated image, and with
+// --denoise the denoiser's image of it, steered by the temporal variance
+// (--denoise-spatial still fills the pixels whose history is too short for one).
+// Without --temporal every run and every refusal is unchanged.
 // Defaults are the reference's: scene 6 (main.zig:313) with that scene's own
 // size, spp, camera and background (main.zig:316-362); --width/--aspect/--spp
 // override them.  Scenes 4 and 7 need --image (assets/sekaichizu.png).
@@ -160,14 +168,14 @@ int main(int argc, char** argv) {
   double aspect = 0, max_noise = 0, pixel_noise = 0;
   uint64_t seed = 42;
   std::string out = "out.ppm", image_path, preview_dir, spp_map;
-  bool denoise = false, denoise_spatial = false;
-  uint32_t denoise_levels = 0;
+  bool denoise = false, denoise_spatial = false, temporal = false;
+  uint32_t denoise_levels = 0, temporal_history = 0;
   bool pick = false, focus_at = false;
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0};
   for (int i = 1; i < argc; i += 2) {
     const std::string k = argv[i];
-    if (k == "--denoise" || k == "--denoise-spatial") {  // (the options without a value)
-      (k == "--denoise" ? denoise : denoise_spatial) = true;
+    if (k == "--denoise" || k == "--denoise-spatial" || k == "--temporal") {  // (the options without a value)
+      (k == "--denoise" ? denoise : k == "--temporal" ? temporal : denoise_spatial) = true;
       --i;
       continue;
     }
@@ -193,6 +201,7 @@ int main(int argc, char** argv) {
     else if (k == "--frames") frames = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--orbit") orbit = std::atof(v);
     else if (k == "--rebuild-above") rebuild_above = std::atof(v);
+    else if (k == "--temporal-history") temporal_history = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--denoise-levels") denoise_levels = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--pick" || k == "--focus-at") {
       const bool is_pick = k == "--pick";
@@ -215,7 +224,15 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--denoise-levels and --denoise-spatial need --denoise\n");
     return 2;
   }
-  if (frames == 0 || (frames > 1 && (pass_spp || denoise || pick || focus_at))) {
+  if (temporal_history && !temporal) {
+    std::fprintf(stderr, "--temporal-history needs --temporal\n");
+    return 2;
+  }
+  if (temporal && (frames < 2 || pass_spp || pick || focus_at || temporal_history > 4096)) {
+    std::fprintf(stderr, "--temporal needs --frames N with N >= 2 (no --pass-spp, --pick, --focus-at) and M <= 4096\n");
+    return 2;
+  }
+  if (frames == 0 || (frames > 1 && (pass_spp || (denoise && !temporal) || pick || focus_at))) {
     std::fprintf(stderr, "--frames needs N >= 1 and renders one-shot frames (no --pass-spp, --denoise, --pick, --focus-at)\n");
     return 2;
   }
@@ -308,8 +325,8 @@ int main(int argc, char** argv) {
     std::memset(&dn, 0, sizeof(dn));
     dn.levels = denoise_levels;
     if (denoise_spatial) dn.flags |= RTW_DENOISE_SPATIAL_VAR;
-    if (denoise && pass_spp == 0) pass_spp = S;  // the whole frame as one pass of the accumulator
-    if (denoise) {
+    if (denoise && pass_spp == 0 && !temporal) pass_spp = S;  // the whole frame as one pass of the accumulator
+    if (denoise && !temporal) {
       // The colour term needs a variance, and the variance two full chunks (without it the
       // filter blurs what no guide describes — reflections, shadows — and a 20-spp preview gets worse).
       const uint32_t c = std::min(chunk ? chunk : RTW_DEFAULT_CHUNK, S);
@@ -349,12 +366,19 @@ int main(int argc, char** argv) {
       p.precision = RTW_PRECISION_F64, p.engine = RTW_ENGINE_MEGAKERNEL;
       const size_t slash = out.find_last_of('/');
       const std::string dir = slash == std::string::npos ? "" : out.substr(0, slash + 1);
-      rtw::renderOrbit(cam.to_c(), p, desc, frames, orbit, [&](uint32_t k, const std::vector<uint8_t>& img) {
+      const rtw::FrameFn write_frame = [&](uint32_t k, const std::vector<uint8_t>& img) {
         char name[32];
         std::snprintf(name, sizeof(name), "frame_%04u.ppm", k);
         rtw::writePPM(dir + name, img, W, H);
         rgb = img;
-      }, rebuild_above);
+      };
+      if (temporal) {
+        rtw::TemporalRun run;
+        run.max_history = temporal_history, run.denoise = denoise, run.dn = dn;
+        rtw::renderOrbitTemporal(cam.to_c(), p, desc, frames, orbit, write_frame, run, rebuild_above);
+      } else {
+        rtw::renderOrbit(cam.to_c(), p, desc, frames, orbit, write_frame, rebuild_above);
+      }
     } else if (scene == 1 && pass_spp) {
       p.precision = precision, p.engine = engine;
       const rtw::FlatScene fs = rtw::flatten(world);

@@ -22,4 +22,19 @@ using FrameFn = std::function<void(uint32_t frame, const std::vector<uint8_t>& r
 void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames, double deg,
                  const FrameFn& on_frame, double rebuild_above = -1.0);
 
+// The same frames, accumulated over time (rtw_hip.h "temporal accumulation"; rtw_render --frames N
+// --temporal): frame k renders with seed p.seed + k; before its update the previous frame's numbers are
+// kept on the device; after the render come the pixel rays, their first hits, the guides, the hits'
+// previous points (time = the feature ray's) and rtw_temporal_device.  on_frame gets the accumulated
+// mean quantised as a render's (frame 0, whose accumulated mean is the render's own: the render's image),
+// or with `denoise` rtw_denoise_device's image of the accumulated mean and the temporal variance.
+// A turn of 0 degrees reprojects nothing (no previous points).  Whole frames only (row_stride 1).
+struct TemporalRun {
+  uint32_t max_history = 0;  // rtw_temporal_opts.max_history (0 = default)
+  bool denoise = false;
+  rtw_denoise_opts dn{};
+};
+void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames,
+                         double deg, const FrameFn& on_frame, const TemporalRun& run, double rebuild_above = -1.0);
+
 }  // namespace rtw

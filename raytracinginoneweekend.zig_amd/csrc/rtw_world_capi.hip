@@ -11,11 +11,13 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "rtw_hip.h"
 #include "rtw_capi_shared.hpp"
 #include "rtw_internal.hpp"
 #include "rtw_cull.hpp"
+#include "rtw_denoise.hpp"
 #include "rtw_host.hpp"
 #include "rtw_libm.hpp"
 #include "rtw_orbit.hpp"
@@ -811,63 +813,173 @@ int rtw_world_render(const rtw_camera* cam, const rtw_world_desc* desc, const rt
 
 }  // extern "C"
 
+int rtw_world_view(rtw_world w, const char* who, rtwk::WorldView* view) {
+  if (!w) return rtw_fail(RTW_EINVAL, "%s: world is NULL", who);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != w->device) return rtw_fail(RTW_EINVAL, "%s: world lives on device %d, current is %d", who, w->device, dev);
+  *view = w->view;
+  return RTW_OK;
+}
+
 // ------------------------------------------------------ rtw_render --frames --
 namespace rtw {
 
+namespace {
+// The numbers of frame k (rtw_orbit.hpp): the description's, turned by k * deg degrees.
+void orbit_numbers(const rtw_world_desc& desc, uint32_t k, double deg, std::vector<rtw_prim>& prims,
+                   std::vector<rtw_xform>& xforms) {
+  const double phi = (double)k * deg * (3.14159265358979323846 / 180.0), sn = rtwl::sin(phi), cs = rtwl::cos(phi);
+  for (uint32_t i = 0; i < desc.n_prims; ++i) {
+    if (desc.prims[i].kind > RTW_PRIM_MOVING_SPHERE) continue;
+    for (int e = 0; e < 2; ++e) {  // RotateY's forward map (hittable.zig:531-537) of both centres
+      const double x = desc.prims[i].a[3 * e], z = desc.prims[i].a[3 * e + 2];
+      prims[i].a[3 * e] = cs * x + sn * z, prims[i].a[3 * e + 2] = -sn * x + cs * z;
+    }
+  }
+  for (uint32_t i = 0; i < desc.n_xforms; ++i)
+    for (uint32_t c = 0; c < desc.xforms[i].n; ++c)
+      if (desc.xforms[i].op[c] == RTW_XF_ROTATE_Y) {
+        const double t = desc.xforms[i].v[c][2] + phi;
+        xforms[i].v[c][0] = rtwl::sin(t), xforms[i].v[c][1] = rtwl::cos(t), xforms[i].v[c][2] = t;
+      }
+}
+
+void ok(int st) {
+  if (st != RTW_OK) throw Error(st, rtw_last_error());
+}
+
+// What a turntable holds on the device, released on every way out.
+struct OrbitDev {
+  rtw_world w = nullptr;
+  std::vector<void*> bufs;
+  ~OrbitDev() {
+    for (void* b : bufs) (void)hipFree(b);
+    rtw_world_destroy(w);
+  }
+  void* alloc(const char* who, size_t bytes) {
+    void* b = nullptr;
+    if (hipMalloc(&b, bytes ? bytes : 8) != hipSuccess) throw Error(RTW_ENOMEM, std::string(who) + ": device allocation failed");
+    bufs.push_back(b);
+    return b;
+  }
+};
+
+// Frame k's numbers (k >= 1) given to the world: the update, and with rebuild_above >= 0 the tree's cost after
+// it and a rebuild where that exceeds rebuild_above times the cost right after the creation or the last rebuild.
+void orbit_apply(rtw_world w, const rtw_world_desc& desc, uint32_t k, double deg, double rebuild_above,
+                 std::vector<rtw_prim>& prims, std::vector<rtw_xform>& xforms, double& built_cost) {
+  orbit_numbers(desc, k, deg, prims, xforms);
+  ok(rtw_world_update(w, prims.data(), desc.n_prims, xforms.data(), desc.n_xforms));
+  if (rebuild_above < 0.0) return;
+  double cost = 0.0;
+  ok(rtw_world_bvh_cost(w, nullptr, &cost));
+  if (cost > rebuild_above * built_cost) {
+    ok(rtw_world_rebuild(w, prims.data(), desc.n_prims, xforms.data(), desc.n_xforms));
+    ok(rtw_world_bvh_cost(w, nullptr, &built_cost));
+    fprintf(stderr, "rebuild frame=%u cost_before=%.6g cost_after=%.6g\n", k, cost, built_cost);
+  }
+}
+}  // namespace
+
 void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames, double deg,
                  const FrameFn& on_frame, double rebuild_above) {
-  struct Dev {  // released on every way out
-    rtw_world w = nullptr;
-    void *ws = nullptr, *rgb = nullptr;
-    ~Dev() {
-      if (ws) (void)hipFree(ws);
-      if (rgb) (void)hipFree(rgb);
-      rtw_world_destroy(w);
-    }
-  } d;
-  auto ok = [](int st) {
-    if (st != RTW_OK) throw Error(st, rtw_last_error());
-  };
+  OrbitDev d;
   ok(rtw_world_create(&desc, RTW_WORLD_DYNAMIC, &d.w));
   const size_t wsb = rtw_world_workspace_bytes(d.w, &p);
   if (wsb == 0) throw Error(RTW_EINVAL, rtw_last_error());
   std::vector<uint8_t> rgb((size_t)p.width * p.row_count * 3);
-  if (hipMalloc(&d.ws, wsb) != hipSuccess || hipMalloc(&d.rgb, rgb.size()) != hipSuccess)
-    throw Error(RTW_ENOMEM, "renderOrbit: device allocation failed");
+  void* ws = d.alloc("renderOrbit", wsb);
+  uint8_t* d_rgb = static_cast<uint8_t*>(d.alloc("renderOrbit", rgb.size()));
   std::vector<rtw_prim> prims(desc.prims, desc.prims + desc.n_prims);
   std::vector<rtw_xform> xforms(desc.xforms, desc.xforms + desc.n_xforms);
   double built_cost = 0.0;  // the tree cost right after the creation or the last rebuild
   if (rebuild_above >= 0.0) ok(rtw_world_bvh_cost(d.w, nullptr, &built_cost));
   for (uint32_t k = 0; k < frames; ++k) {
-    if (k) {  // (frame 0: the description as it stands)
-      const double phi = (double)k * deg * (3.14159265358979323846 / 180.0), sn = rtwl::sin(phi), cs = rtwl::cos(phi);
-      for (uint32_t i = 0; i < desc.n_prims; ++i) {
-        if (desc.prims[i].kind > RTW_PRIM_MOVING_SPHERE) continue;
-        for (int e = 0; e < 2; ++e) {  // RotateY's forward map (hittable.zig:531-537) of both centres
-          const double x = desc.prims[i].a[3 * e], z = desc.prims[i].a[3 * e + 2];
-          prims[i].a[3 * e] = cs * x + sn * z, prims[i].a[3 * e + 2] = -sn * x + cs * z;
-        }
-      }
-      for (uint32_t i = 0; i < desc.n_xforms; ++i)
-        for (uint32_t c = 0; c < desc.xforms[i].n; ++c)
-          if (desc.xforms[i].op[c] == RTW_XF_ROTATE_Y) {
-            const double t = desc.xforms[i].v[c][2] + phi;
-            xforms[i].v[c][0] = rtwl::sin(t), xforms[i].v[c][1] = rtwl::cos(t), xforms[i].v[c][2] = t;
-          }
-      ok(rtw_world_update(d.w, prims.data(), desc.n_prims, xforms.data(), desc.n_xforms));
-      if (rebuild_above >= 0.0) {
-        double cost = 0.0;
-        ok(rtw_world_bvh_cost(d.w, nullptr, &cost));
-        if (cost > rebuild_above * built_cost) {
-          ok(rtw_world_rebuild(d.w, prims.data(), desc.n_prims, xforms.data(), desc.n_xforms));
-          ok(rtw_world_bvh_cost(d.w, nullptr, &built_cost));
-          fprintf(stderr, "rebuild frame=%u cost_before=%.6g cost_after=%.6g\n", k, cost, built_cost);
-        }
-      }
-    }
-    ok(rtw_world_render_device(d.w, &cam, &p, d.ws, wsb, static_cast<uint8_t*>(d.rgb), nullptr, nullptr, nullptr));
-    if (hipMemcpy(rgb.data(), d.rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    if (k) orbit_apply(d.w, desc, k, deg, rebuild_above, prims, xforms, built_cost);  // (frame 0: the description as it stands)
+    ok(rtw_world_render_device(d.w, &cam, &p, ws, wsb, d_rgb, nullptr, nullptr, nullptr));
+    if (hipMemcpy(rgb.data(), d_rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)
       throw Error(RTW_EHIP, "renderOrbit: the render failed on the device");
+    on_frame(k, rgb);
+  }
+}
+
+// The frames of renderOrbit, each accumulated over the ones before it (rtw_hip.h "temporal accumulation").
+void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p0, const rtw_world_desc& desc, uint32_t frames,
+                         double deg, const FrameFn& on_frame, const TemporalRun& run, double rebuild_above) {
+  const char* who = "renderOrbitTemporal";
+  OrbitDev d;
+  if (p0.row_begin != 0 || p0.row_stride != 1 || p0.row_count != p0.height)
+    throw Error(RTW_UNSUPPORTED, "renderOrbitTemporal: the accumulation needs whole frames of contiguous rows");
+  ok(rtw_world_create(&desc, RTW_WORLD_DYNAMIC, &d.w));
+  rtw_params p = p0;
+  const size_t wsb = rtw_world_workspace_bytes(d.w, &p);
+  if (wsb == 0) throw Error(RTW_EINVAL, rtw_last_error());
+  const uint32_t W = p.width, H = p.height;
+  const size_t npix = (size_t)W * H, na = (size_t)9 * desc.n_prims, nxv = (size_t)3 * RTW_MAX_XFORM_OPS * desc.n_xforms;
+  rtw_denoise_opts dn = run.dn;
+  const size_t dnb = run.denoise ? rtw_denoise_workspace_bytes(W, H, &dn) : 0;
+  if (run.denoise && dnb == 0) throw Error(RTW_EINVAL, rtw_last_error());
+  void* ws = d.alloc(who, wsb);
+  uint8_t* d_rgb = static_cast<uint8_t*>(d.alloc(who, npix * 3));
+  float* d_mean = static_cast<float*>(d.alloc(who, npix * 12));
+  float* d_acc = static_cast<float*>(d.alloc(who, npix * 12));
+  float* d_var = static_cast<float*>(d.alloc(who, npix * 4));
+  rtw_ray* d_rays = static_cast<rtw_ray*>(d.alloc(who, npix * sizeof(rtw_ray)));
+  rtw_hit* d_hits = static_cast<rtw_hit*>(d.alloc(who, npix * sizeof(rtw_hit)));
+  rtw_guide* d_guides = static_cast<rtw_guide*>(d.alloc(who, npix * sizeof(rtw_guide)));
+  double* d_pp = static_cast<double*>(d.alloc(who, npix * 24));
+  rtw_history* d_hist[2] = {static_cast<rtw_history*>(d.alloc(who, npix * sizeof(rtw_history))),
+                            static_cast<rtw_history*>(d.alloc(who, npix * sizeof(rtw_history)))};
+  double* d_a_prev = static_cast<double*>(d.alloc(who, na * 8));
+  double* d_xv_prev = static_cast<double*>(d.alloc(who, nxv * 8));
+  void* d_dn = run.denoise ? d.alloc(who, dnb) : nullptr;
+  rtw_temporal_opts to{};
+  to.max_history = run.max_history;
+  std::vector<uint8_t> rgb(npix * 3);
+  std::vector<float> acc;
+  std::vector<rtw_prim> prims(desc.prims, desc.prims + desc.n_prims);
+  std::vector<rtw_xform> xforms(desc.xforms, desc.xforms + desc.n_xforms);
+  std::vector<double> a_prev(na), xv_prev(nxv);
+  const bool moves = deg != 0.0;  // (a turn of 0 degrees: nothing moved, no previous points)
+  const double time = cam.time0 + 0.5 * (cam.time1 - cam.time0);  // the feature ray's
+  double built_cost = 0.0;
+  if (rebuild_above >= 0.0) ok(rtw_world_bvh_cost(d.w, nullptr, &built_cost));
+  for (uint32_t k = 0; k < frames; ++k) {
+    if (k) {
+      if (moves) {  // the previous frame's numbers stay on the device for the reprojection
+        for (uint32_t i = 0; i < desc.n_prims; ++i) std::memcpy(&a_prev[(size_t)9 * i], prims[i].a, sizeof(prims[i].a));
+        for (uint32_t i = 0; i < desc.n_xforms; ++i) std::memcpy(&xv_prev[(size_t)12 * i], xforms[i].v, sizeof(xforms[i].v));
+        if ((na && hipMemcpy(d_a_prev, a_prev.data(), na * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+            (nxv && hipMemcpy(d_xv_prev, xv_prev.data(), nxv * 8, hipMemcpyHostToDevice) != hipSuccess))
+          throw Error(RTW_EHIP, "renderOrbitTemporal: upload of the previous numbers failed");
+      }
+      orbit_apply(d.w, desc, k, deg, rebuild_above, prims, xforms, built_cost);
+    }
+    p.seed = p0.seed + k;  // equal seeds give equal noise, which no mean reduces
+    ok(rtw_world_render_device(d.w, &cam, &p, ws, wsb, d_rgb, d_mean, nullptr, nullptr));
+    ok(rtw_pixel_rays_device(&cam, W, H, d_rays, nullptr));
+    ok(rtw_world_trace_device(d.w, d_rays, npix, nullptr, d_hits, nullptr));
+    ok(rtw_world_guides_device(d.w, &cam, &p, d_guides, nullptr));
+    const bool reproject = k && moves;
+    if (reproject)
+      ok(rtw_world_prev_points_device(d.w, d_hits, npix, time, na ? d_a_prev : nullptr, nxv ? d_xv_prev : nullptr, d_pp,
+                                      nullptr));
+    ok(rtw_temporal_device(d_mean, d_guides, reproject ? d_pp : nullptr, &cam, &cam, k ? d_hist[(k + 1) & 1] : nullptr, W,
+                           H, &to, d_hist[k & 1], d_acc, d_var, nullptr));
+    if (run.denoise) {
+      ok(rtw_denoise_device(d_acc, d_var, d_guides, W, H, &dn, d_dn, dnb, d_rgb, nullptr, nullptr));
+      if (hipMemcpy(rgb.data(), d_rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)
+        throw Error(RTW_EHIP, "renderOrbitTemporal: the frame failed on the device");
+    } else if (k == 0) {  // the first frame's accumulated mean is the render's own: so is its image
+      if (hipMemcpy(rgb.data(), d_rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)
+        throw Error(RTW_EHIP, "renderOrbitTemporal: the frame failed on the device");
+    } else {  // the accumulated mean, quantised as a render's
+      acc.resize(npix * 3);
+      if (hipMemcpy(acc.data(), d_acc, acc.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        throw Error(RTW_EHIP, "renderOrbitTemporal: the frame failed on the device");
+      for (size_t i = 0; i < acc.size(); ++i) rgb[i] = rtwd::quantise((double)acc[i]);
+    }
     on_frame(k, rgb);
   }
 }

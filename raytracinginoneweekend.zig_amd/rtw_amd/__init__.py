@@ -108,6 +108,26 @@ class QueryOpts(C.Structure):
     _fields_ = [("traversal", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class History(C.Structure):
+    """rtw_history: a pixel's temporal accumulation record (32 bytes)."""
+    _fields_ = [("mean", C.c_float * 3), ("len", C.c_float), ("m1", C.c_float), ("m2", C.c_float),
+                ("depth", C.c_float), ("prim", C.c_uint32)]
+
+
+class TemporalOpts(C.Structure):
+    """rtw_temporal_opts: every field 0 = its default (32, 0.02, 4, 0)."""
+    _fields_ = [("max_history", C.c_uint32), ("depth_tol", C.c_double), ("min_len_var", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+HISTORY_DTYPE = np.dtype([("mean", np.float32, 3), ("len", np.float32), ("m1", np.float32), ("m2", np.float32),
+                          ("depth", np.float32), ("prim", np.uint32)])
+
+
+def temporal_opts(max_history=0, depth_tol=0.0, min_len_var=0, flags=0) -> TemporalOpts:
+    return TemporalOpts(max_history, depth_tol, min_len_var, flags)
+
+
 RAY_DTYPE = np.dtype([("origin", np.float64, 3), ("dir", np.float64, 3), ("time", np.float64),
                       ("t_min", np.float64), ("t_max", np.float64)])
 HIT_DTYPE = np.dtype([("t", np.float64), ("p", np.float64, 3), ("normal", np.float64, 3), ("u", np.float64),
@@ -247,6 +267,15 @@ def lib() -> C.CDLL:
         L.rtw_world_rebuild_refit_tables_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_float * 2,
                                                           C.c_double * 6, C.c_uint32 * 4]
+    if hasattr(L, "rtw_temporal_device"):  # temporal accumulation
+        for f in (L.rtw_temporal_device, L.rtw_temporal_host):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(Camera), P(Camera), C.c_void_p, C.c_uint32, C.c_uint32,
+                          P(TemporalOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rtw_pixel_rays_device.argtypes = [P(Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rtw_world_prev_points_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rtw_world_prev_points_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -297,6 +326,45 @@ def pixel_ray(cam: Camera, width: int, height: int, x: int, y: int) -> Ray:
     if st != RTW_OK:
         raise RtwError(st, f"rtw_pixel_ray: pixel ({x}, {y}) of {width}x{height}")
     return r
+
+
+def _vp(p):
+    return C.c_void_p(p) if p else None
+
+
+def temporal_device(mean_ptr: int, guides_ptr: int, prev_p_ptr: int | None, cam_prev: Camera, cam: Camera,
+                    hist_in_ptr: int | None, width: int, height: int, hist_out_ptr: int, mean_out_ptr: int | None = None,
+                    var_out_ptr: int | None = None, opts: TemporalOpts | None = None, stream: int | None = None):
+    """rtw_temporal_device on device pointers, asynchronous on `stream`: one frame's mean (W*H*3 f32) and
+    guides blended into the history image hist_out (W*H rtw_history) from hist_in (None: the first frame);
+    prev_p (W*H*3 f64, None: nothing moved) from DeviceWorld.prev_points_device."""
+    _check(lib().rtw_temporal_device(_vp(mean_ptr), _vp(guides_ptr), _vp(prev_p_ptr), C.byref(cam_prev), C.byref(cam),
+                                     _vp(hist_in_ptr), width, height, C.byref(opts) if opts is not None else None,
+                                     _vp(hist_out_ptr), _vp(mean_out_ptr), _vp(var_out_ptr), _vp(stream)))
+
+
+def temporal_host(mean, guides, cam_prev: Camera, cam: Camera, hist_in=None, prev_p=None,
+                  opts: TemporalOpts | None = None):
+    """rtw_temporal_host on numpy arrays (no GPU): mean (H, W, 3) float32, guides (H, W) GUIDE_DTYPE, hist_in
+    (H, W) HISTORY_DTYPE or None, prev_p (H, W, 3) float64 or None -> (hist_out, mean_out, var_out)."""
+    m = np.ascontiguousarray(mean, np.float32)
+    g = np.ascontiguousarray(guides, GUIDE_DTYPE)
+    H, W = g.shape
+    hi = np.ascontiguousarray(hist_in, HISTORY_DTYPE) if hist_in is not None else None
+    pp = np.ascontiguousarray(prev_p, np.float64) if prev_p is not None else None
+    if m.shape != (H, W, 3) or (hi is not None and hi.shape != (H, W)) or (pp is not None and pp.shape != (H, W, 3)):
+        raise ValueError("mean (H, W, 3), guides (H, W), hist_in (H, W), prev_p (H, W, 3)")
+    ho, mo, vo = np.zeros((H, W), HISTORY_DTYPE), np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.float32)
+    _check(lib().rtw_temporal_host(m.ctypes.data, g.ctypes.data, pp.ctypes.data if pp is not None else None,
+                                   C.byref(cam_prev), C.byref(cam), hi.ctypes.data if hi is not None else None, W, H,
+                                   C.byref(opts) if opts is not None else None, ho.ctypes.data, mo.ctypes.data,
+                                   vo.ctypes.data, None))
+    return ho, mo, vo
+
+
+def pixel_rays_device(cam: Camera, width: int, height: int, rays_ptr: int, stream: int | None = None):
+    """rtw_pixel_rays_device: the width*height feature rays (rtw_ray records, row-major) into device memory."""
+    _check(lib().rtw_pixel_rays_device(C.byref(cam), width, height, _vp(rays_ptr), _vp(stream)))
 
 
 def cover_scene(seed: int = 42):

@@ -6,7 +6,8 @@ from __future__ import annotations
 
 import torch
 
-from . import Accumulator, Camera, DeviceScene, Params, QueryOpts, Timer, workspace_bytes
+from . import (Accumulator, Camera, DeviceScene, Params, QueryOpts, TemporalOpts, Timer, temporal_device,
+               workspace_bytes)
 
 
 class TorchRenderer:
@@ -268,3 +269,56 @@ def _numbers_to_world(entry, dw, a, xv):
     with torch.cuda.device(a.device):
         entry(a.data_ptr(), xv.data_ptr() if xv is not None and xv.numel() else None,
               torch.cuda.current_stream(a.device).cuda_stream)
+
+
+class TemporalAccumulator:
+    """Temporal accumulation on torch tensors (rtw_hip.h "temporal accumulation"): owns the two
+    history images of a width x height animation and blends one frame per step() into them on
+    torch's current HIP stream.
+
+        ta = TemporalAccumulator(W, H)
+        mean_out, var_out = ta.step(mean, guides, cam, prev_p)   # feed both to the denoiser
+    """
+
+    def __init__(self, width: int, height: int, opts: TemporalOpts | None = None,
+                 device: int | torch.device | None = None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("no GPU visible: the rtw temporal path has no CPU fallback")
+        if device is None:
+            device = torch.cuda.current_device()
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self.width, self.height, self.opts = int(width), int(height), opts
+        self.hist = [torch.zeros((self.height, self.width, 32), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self.reset()
+
+    def reset(self):
+        """Forget the history: the next step() is a first frame."""
+        self.frames, self.cam_prev = 0, None
+
+    def history(self) -> torch.Tensor:
+        """The history image the last step() wrote ((H, W, 32) uint8: rtw_history records)."""
+        return self.hist[(self.frames + 1) & 1]
+
+    def step(self, mean: torch.Tensor, guides: torch.Tensor, cam: Camera, prev_p: torch.Tensor | None = None):
+        """One frame: mean (H, W, 3) float32, guides (H, W, 32) uint8 (rtw_guide records), prev_p
+        (H, W, 3) float64 or None (nothing moved).  Returns (mean_out (H, W, 3) float32, var_out
+        (H, W) float32): the accumulated mean and the variance for rtw_denoise_device's d_var."""
+        H, W = self.height, self.width
+        for name, t, dt, n in (("mean", mean, torch.float32, H * W * 3), ("guides", guides, torch.uint8, H * W * 32),
+                               ("prev_p", prev_p, torch.float64, H * W * 3)):
+            if t is None:
+                continue
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.numel() != n:
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} elements on {self.device}")
+        src, dst = self.hist[(self.frames + 1) & 1], self.hist[self.frames & 1]
+        mean_out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
+        var_out = torch.empty((H, W), dtype=torch.float32, device=self.device)
+        cam_now = Camera.from_buffer_copy(cam)
+        with torch.cuda.device(self.device):
+            temporal_device(mean.data_ptr(), guides.data_ptr(), prev_p.data_ptr() if prev_p is not None else None,
+                            self.cam_prev if self.frames else cam_now, cam_now, src.data_ptr() if self.frames else None,
+                            W, H, dst.data_ptr(), mean_out.data_ptr(), var_out.data_ptr(), self.opts,
+                            torch.cuda.current_stream(self.device).cuda_stream)
+        self.frames += 1
+        self.cam_prev = cam_now
+        return mean_out, var_out

@@ -334,6 +334,22 @@ def desc_numbers(desc: WorldDesc):
     return a, xv
 
 
+def prev_points_host(desc: WorldDesc, hits, time: float, a_prev=None, xv_prev=None) -> np.ndarray:
+    """rtw_world_prev_points_host (no GPU): hits (n,) HIT_DTYPE of the world `desc` describes -> (n, 3)
+    float64, each hit's surface point under the numbers a_prev ((n_prims, 9)) / xv_prev ((n_xforms, 4, 3)),
+    None = the descriptor's own."""
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    a = np.ascontiguousarray(a_prev, np.float64) if a_prev is not None else None
+    xv = np.ascontiguousarray(xv_prev, np.float64) if xv_prev is not None else None
+    if (a is not None and a.shape != (desc.n_prims, 9)) or (xv is not None and xv.shape != (desc.n_xforms, 4, 3)):
+        raise ValueError("a_prev must be (n_prims, 9) and xv_prev (n_xforms, 4, 3)")
+    out = np.zeros((h.size, 3), np.float64)
+    _check(_wlib().rtw_world_prev_points_host(C.byref(desc), h.ctypes.data, h.size, float(time),
+                                              a.ctypes.data if a is not None else None,
+                                              xv.ctypes.data if xv is not None and xv.size else None, out.ctypes.data))
+    return out
+
+
 TRAVERSAL_NAMES = {1: "union", 2: "lane", 3: "linear"}  # rtw_world_traversal (rtw_hip.h)
 
 
@@ -464,6 +480,17 @@ class DeviceWorld:
                                        out.ctypes.data))
         return out
 
+    def prev_points_device(self, hits_ptr: int, n: int, time: float, out_ptr: int, a_prev_ptr: int | None = None,
+                           xv_prev_ptr: int | None = None, stream: int | None = None):
+        """rtw_world_prev_points_device: for n rtw_hit records of this world as it is now, the same surface
+        points under the previous frame's numbers (device arrays shaped as update_device's, None = the
+        current values) into n x 3 float64, asynchronous on `stream`."""
+        _check(_wlib().rtw_world_prev_points_device(self.h, C.c_void_p(hits_ptr) if hits_ptr else None, n, float(time),
+                                                    C.c_void_p(a_prev_ptr) if a_prev_ptr else None,
+                                                    C.c_void_p(xv_prev_ptr) if xv_prev_ptr else None,
+                                                    C.c_void_p(out_ptr) if out_ptr else None,
+                                                    C.c_void_p(stream) if stream else None))
+
     def query_info(self, opts: QueryOpts | None = None) -> dict:
         """rtw_world_query_info: the walk a query runs (after AUTO and the world's limits),
         its kernel feature set, the workgroups of a device-filling batch, LDS per workgroup."""
@@ -497,4 +524,4 @@ class DeviceWorld:
             pass
 
 
-__all__ = ["BuiltScene", "DeviceWorld", "refit_tables_host", "rebuild_tables_host", "desc_numbers", "render_world", "load_png", "earth_map", "synthetic_world_map", "RtwError", "SCENES"]
+__all__ = ["BuiltScene", "DeviceWorld", "refit_tables_host", "rebuild_tables_host", "prev_points_host", "desc_numbers", "render_world", "load_png", "earth_map", "synthetic_world_map", "RtwError", "SCENES"]

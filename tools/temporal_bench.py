@@ -1,0 +1,307 @@
+#!/usr/bin/env python3
+"""Cost and worth of temporal accumulation (rtw_hip.h "temporal accumulation",
+DESIGN.md §18) on turntables of scene 1 (configs[1]'s scene as a world) and of
+the globe + 10k spheres (scene 7, the real map).
+
+  python tools/temporal_bench.py --mode time    [--repeats 7] [--out FILE]
+  python tools/temporal_bench.py --mode quality [--frames 16] [--spp 20] [--ref-spp 500] [--width W] [--out FILE]
+                                                [--degrees 1,5,0] [--max-history M]
+
+time: at the scene's own size (1200x675), HIP events around each call, the calls
+alternating in one process after a warm-up round, median (min .. max), each
+beside its traffic floor at the 6.29 TB/s copy rate; the 20-sample render for
+scale; the shader clock (rtw_sclk_probe) noted.
+quality: frames of 20 spp, every sphere centre turned by 1 or 5 degrees per frame
+(rtw_orbit.hpp's motion), RMSE of the linear mean against ref-spp frames of the
+same positions, for the input, the spatial denoiser alone, temporal alone and
+temporal + denoise; the mean history length and the share of pixels without
+history per frame; the averaged frames' error split by what the pixel's feature
+ray hits first (the sky, the ground, a diffuse, metal or glass primitive); and
+the static case (0 degrees) frame by frame."""
+import argparse
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "raytracinginoneweekend.zig_amd"))
+
+COPY_RATE = 6.29e12  # bytes/s: the measured device copy rate floors are stated at
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("time", "quality"), required=True)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--spp", type=int, default=20)
+    ap.add_argument("--ref-spp", type=int, default=500)
+    ap.add_argument("--width", type=int, default=0)
+    ap.add_argument("--scenes", default="1,7")
+    ap.add_argument("--degrees", default="1,5,0", help="quality: degrees per frame, one turntable each (0: the static case)")
+    ap.add_argument("--max-history", type=int, default=0, help="quality: rtw_temporal_opts.max_history (0 = the default)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+
+    import rtw_amd as R
+    from rtw_amd import world as Wd
+    from rtw_amd.device import TemporalAccumulator, update_world
+    if not torch.cuda.is_available():
+        raise SystemExit("temporal_bench needs a GPU (there is no CPU path)")
+    dev = "cuda:0"
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    def fmt(v):
+        return f"median {statistics.median(v):8.4f}  ({min(v):.4f} .. {max(v):.4f})"
+
+    def stream():
+        return torch.cuda.current_stream().cuda_stream
+
+    def turned(a0, kinds, xv0, ops, deg):
+        """rtw_orbit.hpp's numbers: sphere centres about the y axis, RotateY angles advanced."""
+        phi = np.deg2rad(deg)
+        sn, cs = np.sin(phi), np.cos(phi)
+        a = a0.copy()
+        sph = kinds <= 1
+        for e in (0, 3):
+            x, z = a0[sph, e], a0[sph, e + 2]
+            a[sph, e], a[sph, e + 2] = cs * x + sn * z, -sn * x + cs * z
+        xv = xv0.copy()
+        rot = ops == 1
+        t = xv0[..., 2] + phi
+        xv[..., 0] = np.where(rot, np.sin(t), xv0[..., 0])
+        xv[..., 1] = np.where(rot, np.cos(t), xv0[..., 1])
+        xv[..., 2] = np.where(rot, t, xv0[..., 2])
+        return a, xv
+
+    class Scene:
+        def __init__(self, sid):
+            self.sid = sid
+            self.b = Wd.BuiltScene(sid, 42, image=Wd.earth_map() if sid in (4, 7) else None)
+            d = self.b.desc
+            s = self.b.settings
+            self.W = args.width or s.width
+            self.H = R.image_height(self.W, s.aspect) if args.width else s.height
+            self.cam = self.b.camera()
+            self.a0, self.xv0 = Wd.desc_numbers(d)
+            self.kinds = np.array([d.prims[i].kind for i in range(d.n_prims)])
+            self.ops = np.array([[d.xforms[i].op[k] if k < d.xforms[i].n else 0 for k in range(4)] for i in range(d.n_xforms)],
+                                dtype=np.int64).reshape(d.n_xforms, 4)
+            # the class of a pixel's first-hit primitive (index = guide prim, 0 = a miss): a sphere of radius >= 100
+            # is the ground, everything else goes by its material's kind
+            big = (self.kinds <= 1) & (self.a0[:, 6] >= 100.0)
+            mk = np.array([d.mats[d.prims[i].mat].kind for i in range(d.n_prims)])
+            self.cls = torch.from_numpy(np.concatenate([[0], np.where(big, 1, 2 + mk)]).astype(np.int64)).to(dev)
+            self.dw = Wd.DeviceWorld(d, dynamic=True)
+            self.n = self.W * self.H
+            W, H = self.W, self.H
+            self.rays = torch.empty((self.n, 9), dtype=torch.float64, device=dev)
+            self.hits = torch.empty((self.n, 10), dtype=torch.float64, device=dev)
+            self.guides = torch.empty((H, W, 32), dtype=torch.uint8, device=dev)
+            self.pp = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
+            self.rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+            self.mean = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+            self._ws = None
+            self.dn_opts = R.denoise_opts(flags=R.DENOISE_SPATIAL_VAR)
+            nb = R.denoise_workspace_bytes(W, H, self.dn_opts)
+            self.dn_ws = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+            self.dn_ptr, self.dn_bytes = (self.dn_ws.data_ptr() + 255) & ~255, nb
+
+        def params(self, spp, seed):
+            return R.make_params(self.W, self.H, spp, 50, seed, background=self.b.background)
+
+        def numbers(self, deg):
+            a, xv = turned(self.a0, self.kinds, self.xv0, self.ops, deg)
+            return torch.from_numpy(a).to(dev), (torch.from_numpy(xv).to(dev) if xv.size else None)
+
+        def render(self, p, timer=None):
+            need = self.dw.workspace_bytes(p)
+            if self._ws is None or self._ws.numel() < need + 256:
+                self._ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+            ptr = (self._ws.data_ptr() + 255) & ~255
+            self.dw.render_async(self.cam, p, ptr, need, self.rgb.data_ptr(), self.mean.data_ptr(), stream(), timer)
+
+        def pixel_rays(self):
+            R.pixel_rays_device(self.cam, self.W, self.H, self.rays.data_ptr(), stream())
+
+        def trace(self):
+            self.dw.trace(self.rays.data_ptr(), self.n, self.hits.data_ptr(), None, stream())
+
+        def make_guides(self, p):
+            self.dw.guides(self.cam, p, self.guides.data_ptr(), stream())
+
+        def prev_points(self, a_prev, xv_prev):
+            self.dw.prev_points_device(self.hits.data_ptr(), self.n, 0.5, self.pp.data_ptr(), a_prev.data_ptr(),
+                                       xv_prev.data_ptr() if xv_prev is not None else None, stream())
+
+        def denoise(self, mean, var):
+            out = torch.empty_like(mean)
+            R.denoise_device(mean.data_ptr(), var.data_ptr() if var is not None else None, self.guides.data_ptr(), self.W,
+                             self.H, self.dn_opts, self.dn_ptr, self.dn_bytes, None, out.data_ptr(), stream())
+            return out
+
+        def close(self):
+            self.dw.close()
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        f()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def mode_time():
+        for sid in [int(x) for x in args.scenes.split(",")]:
+            sc = Scene(sid)
+            W, H, n = sc.W, sc.H, sc.n
+            p = sc.params(args.spp, 42)
+            a_prev, xv_prev = sc.numbers(0.0)
+            a_now, xv_now = sc.numbers(1.0)
+            update_world(sc.dw, a_now, xv_now)
+            hist = [torch.zeros((H, W, 32), dtype=torch.uint8, device=dev) for _ in range(2)]
+            acc, var = torch.empty((H, W, 3), dtype=torch.float32, device=dev), torch.empty((H, W), dtype=torch.float32, device=dev)
+
+            def temporal(src, dst, pp):
+                R.temporal_device(sc.mean.data_ptr(), sc.guides.data_ptr(), pp, sc.cam, sc.cam, src, W, H, dst, acc.data_ptr(),
+                                  var.data_ptr(), None, stream())
+            sc.render(p)
+            sc.pixel_rays(), sc.trace(), sc.make_guides(p), sc.prev_points(a_prev, xv_prev)
+            temporal(None, hist[0].data_ptr(), None)  # a first frame: every record holds history from here on
+            torch.cuda.synchronize()
+            steps = {
+                "render (20 spp, all kernels)": lambda: sc.render(p),
+                "rtw_pixel_rays_device": sc.pixel_rays,
+                "rtw_world_trace_device": sc.trace,
+                "rtw_world_guides_device": lambda: sc.make_guides(p),
+                "rtw_world_prev_points_device": lambda: sc.prev_points(a_prev, xv_prev),
+                "rtw_temporal_device, static": lambda: temporal(hist[0].data_ptr(), hist[1].data_ptr(), None),
+                "rtw_temporal_device, motion": lambda: temporal(hist[0].data_ptr(), hist[1].data_ptr(), sc.pp.data_ptr()),
+                "rtw_denoise_device (+ spatial)": lambda: sc.denoise(acc, var),
+            }
+            floors = {"rtw_pixel_rays_device": 72, "rtw_world_prev_points_device": 80 + 24,
+                      "rtw_temporal_device, static": 12 + 32 + 32 + 48, "rtw_temporal_device, motion": 12 + 32 + 24 + 4 * 32 + 48}
+            t = {k: [] for k in steps}
+            trace_ms = []
+            est = timed(lambda: sc.render(p))
+            clk_stream = torch.cuda.Stream()
+            clk = R.SclkProbe(clk_stream.cuda_stream, max(1.0, 1.5 * est * (args.repeats + 1)))
+            for r in range(args.repeats + 1):
+                for k, f in steps.items():
+                    if k.startswith("render"):
+                        tm = R.Timer()
+                        ms = timed(lambda: sc.render(p, tm))
+                        if r:
+                            trace_ms.append(tm.elapsed_ms())
+                        tm.close()
+                    else:
+                        ms = timed(f)
+                    if r:  # (round 0 warms up)
+                        t[k].append(ms)
+            mhz = clk.read()
+            lens = hist[1].cpu().numpy().reshape(-1).view(R.HISTORY_DTYPE)["len"]
+            say(f"# scene {sid}: {sc.b.desc.n_prims} primitives, {W}x{H} = {n} pixels, every sphere centre turned by 1 degree; "
+                f"{args.repeats} alternating rounds after one warm-up, HIP-event ms; shader clock {mhz:.1f} MHz")
+            say(f"  (motion step: {float((lens > 1).mean()) * 100:.2f} % of the pixels found history)")
+            for k, v in t.items():
+                fl = f"   floor {floors[k] * n / COPY_RATE * 1e3:.4f} ms ({floors[k]} B/pixel at 6.29 TB/s): x{statistics.median(v) / (floors[k] * n / COPY_RATE * 1e3):.1f}" if k in floors else ""
+                say(f"  {k:32s} {fmt(v)}{fl}")
+            say(f"  {'  of which the trace kernel':32s} {fmt(trace_ms)}")
+            med = {k: statistics.median(v) for k, v in t.items()}
+            extra = sum(med[k] for k in ("rtw_pixel_rays_device", "rtw_world_trace_device", "rtw_world_guides_device",
+                                         "rtw_world_prev_points_device", "rtw_temporal_device, motion"))
+            rend = med["render (20 spp, all kernels)"]
+            say(f"  per animated frame: render {rend:.3f} ms + temporal steps {extra:.3f} ms (+ {extra / rend * 100:.1f} %), of which the "
+                f"guides {med['rtw_world_guides_device']:.3f} ms = {med['rtw_world_guides_device'] / (rend + extra) * 100:.1f} % of the frame; "
+                f"without the guides the steps are {extra - med['rtw_world_guides_device']:.3f} ms (+ {(extra - med['rtw_world_guides_device']) / rend * 100:.1f} %); "
+                f"the denoiser adds {med['rtw_denoise_device (+ spatial)']:.3f} ms")
+            sc.close()
+
+    CLASSES = ("miss (the sky)", "ground (r >= 100)", "diffuse", "metal", "glass", "light")
+
+    def rmse(a, b):
+        return float(torch.sqrt(((a.double() - b.double()) ** 2).mean()))
+
+    def mode_quality():
+        for sid in [int(x) for x in args.scenes.split(",")]:
+            sc = Scene(sid)
+            W, H = sc.W, sc.H
+            say(f"# scene {sid}: {W}x{H}, {args.spp} spp per frame (seed 42 + k), reference {args.ref_spp} spp (seed 1000 + k), "
+                f"RMSE of the linear mean over all pixels and channels; max_history {args.max_history or 32}, depth_tol 0.02, min_len_var 4")
+            for deg in [float(x) for x in args.degrees.split(",")]:
+                frames = args.frames if deg else 2 * args.frames
+                ta = TemporalAccumulator(W, H, R.temporal_opts(max_history=args.max_history), device=0)
+                prev = None
+                rows = []
+                by_class = np.zeros((len(CLASSES), 4))  # pixels, squared error of the input, of temporal, sum of len
+                ref0 = None
+                for k in range(frames):
+                    a, xv = sc.numbers(k * deg)
+                    if deg or k == 0:
+                        update_world(sc.dw, a, xv)
+                    if deg or ref0 is None:
+                        sc.render(sc.params(args.ref_spp, 1000 + k))
+                        ref = sc.mean.clone()
+                        ref0 = ref
+                    else:
+                        ref = ref0
+                    p = sc.params(args.spp, 42 + k)
+                    sc.render(p)
+                    cur = sc.mean.clone()
+                    sc.pixel_rays(), sc.trace(), sc.make_guides(p)
+                    pp = None
+                    if k and deg:
+                        sc.prev_points(*prev)
+                        pp = sc.pp
+                    acc, var = ta.step(cur, sc.guides, sc.cam, pp)
+                    spatial = sc.denoise(cur, None)
+                    both = sc.denoise(acc, var)
+                    torch.cuda.synchronize()
+                    if k >= frames // 2:  # the frames the summary line averages, split by what the pixel shows
+                        cls = sc.cls[sc.guides.view(torch.int32)[..., 7].long()]
+                        for c in range(len(CLASSES)):
+                            m = cls == c
+                            by_class[c] += np.array([float(m.sum()), float(((cur.double() - ref.double()) ** 2)[m].sum()),
+                                                     float(((acc.double() - ref.double()) ** 2)[m].sum()),
+                                                     float(ta.history().view(torch.float32)[..., 3][m].sum())])
+                    hist = ta.history().cpu().numpy().reshape(-1).view(R.HISTORY_DTYPE)
+                    rows.append((k, rmse(cur, ref), rmse(spatial, ref), rmse(acc, ref), rmse(both, ref), float(hist["len"].mean()),
+                                 float((hist["len"] == 1).mean()), float((var.cpu().numpy() < 0).mean())))
+                    prev = (a, xv)
+                say(f"## {deg:g} degrees per frame, {frames} frames")
+                say("  frame   input   denoise+spatial   temporal   temporal+denoise   mean len   no history   var unknown")
+                for r in rows:
+                    say(f"  {r[0]:5d}  {r[1]:.5f}       {r[2]:.5f}       {r[3]:.5f}       {r[4]:.5f}       {r[5]:7.3f}    {r[6] * 100:6.2f} %    {r[7] * 100:6.2f} %")
+                tail = rows[len(rows) // 2:]
+                m = [statistics.mean(r[i] for r in tail) for i in range(1, 5)]
+                say(f"  mean over the last {len(tail)} frames: input {m[0]:.5f}  denoise+spatial {m[1]:.5f} ({m[1] / m[0]:.3f}x)  "
+                    f"temporal {m[2]:.5f} ({m[2] / m[0]:.3f}x)  temporal+denoise {m[3]:.5f} ({m[3] / m[0]:.3f}x)")
+                say("  the same frames by what the pixel's feature ray hits first (RMSE over the class's pixels; share of the temporal "
+                    "image's squared error):")
+                for c, name in enumerate(CLASSES):
+                    n, se_in, se_t, ln = by_class[c]
+                    if n:
+                        say(f"    {name:22s} {n / by_class[:, 0].sum() * 100:6.2f} % of the pixels   input {np.sqrt(se_in / n / 3):.5f}   "
+                            f"temporal {np.sqrt(se_t / n / 3):.5f} ({np.sqrt(se_t / se_in):.3f}x)   {se_t / by_class[:, 2].sum() * 100:6.2f} % "
+                            f"of the error   mean len {ln / n:6.2f}")
+                if not deg:
+                    for frac in (0.5, 0.25):
+                        hit = next((r[0] + 1 for r in rows if r[3] <= frac * rows[0][1]), None)
+                        say(f"  static: temporal alone reaches {frac:g} x the input's RMSE after {hit} frames (1 / sqrt(n) says {round(1 / frac ** 2)})")
+            sc.close()
+
+    (mode_time if args.mode == "time" else mode_quality)()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
