@@ -879,6 +879,62 @@ int rtw_scene_trace(rtw_scene s, const rtw_ray *rays, uint64_t n, rtw_hit *hits_
  * workgroup}. */
 int rtw_world_query_info(rtw_world w, const rtw_query_opts *opts, uint32_t info_out[4]);
 
+/* ======================================================== surface queries ===
+ *   What the surface under a hit record IS: its material's
+ * kind and index, the value of its texture at the record's u, v, p — a checker,
+ * Perlin noise or an image evaluated by the render's own functions — what a
+ * light emits there, a metal's fuzz, a glass's index; and, from the same
+ * numbers, the rtw_guide record of that ray.  The hit records are those of
+ * rtw_world_trace_device / rtw_scene_trace_device over the SAME world or scene
+ * in its current state.  New symbols only: nothing else changes.
+ *
+ * Per record.  prim == 0, or prim beyond the list (the kernel checks this
+ * itself: the records are the caller's memory), is a miss: the surface record
+ * is 64 zero bytes, the guide {0,0,0, 0, f32(background), 0}.  Otherwise the
+ * material is that of list entry prim - 1, and the guide is {f32(normal),
+ * f32(t), f32(value), prim}, each f64 rounded to f32 once.
+ * Equalities.  For the hits of a frame's feature rays (rtw_pixel_rays_device,
+ * then a trace) d_guides equals the buffer of rtw_world_guides_device /
+ * rtw_scene_guides_device of that frame byte for byte; every f64 field equals
+ * the oracle's (oracle/rtw_world.h rw_texture_value on rw_hit's uv and p, and
+ * the material table).
+ * Scenes.  The cover scene's table is reported in the world's enumerations:
+ * RTW_LAMBERT_SOLID is RTW_WMAT_LAMBERT over RTW_TEX_SOLID, RTW_LAMBERT_CHECKER
+ * the same over RTW_TEX_CHECKER; `mat` indexes the scene's material array and
+ * tex is 0, a scene having no texture table.
+ * Launch.  One kernel launch, asynchronous on `stream`; no allocation, no
+ * workspace, no synchronisation, no atomics: the same input gives the same
+ * bytes.  d_surf and d_guides are optional each, at least one is required;
+ * background may be NULL only when d_guides is.  n == 0 returns RTW_OK and
+ * launches nothing.  RTW_EINVAL for a null handle or null d_hits, both outputs
+ * NULL, d_guides without background or with a non-finite one, d_hits or d_surf
+ * not 8-byte aligned, d_guides not 16-byte aligned, n > 2^31, an output whose n
+ * records overlap d_hits' or the other output's anywhere, a world or scene of
+ * another device than the current one.
+ * Records no trace produced.  The contents of their outputs are unspecified, but
+ * no access leaves the tables or the output buffers: prim is bounded as above,
+ * every index the tables hold was checked when they were packed, and what u, v
+ * and p select — the image's texel, the Perlin lattice point — is clamped or
+ * masked before use.  NaN and infinite u, v, p included. */
+typedef struct {
+  double value[3];   /* Lambert: its texture's value at the record's u, v, p; Metal: its albedo;
+                        Dielectric: 1,1,1; Light: its emit texture's value — rtw_guide.albedo before rounding */
+  double fuzz;       /* Metal: the number the render's scatter reads; else 0 */
+  double ir;         /* Dielectric: likewise; else 0 */
+  uint32_t kind;     /* rtw_wmaterial_kind + 1; 0 = a miss */
+  uint32_t mat;      /* material index + 1; 0 = a miss */
+  uint32_t tex;      /* index + 1 of the texture that gave `value`; 0 = none (Metal, Dielectric, a miss, a scene) */
+  uint32_t tex_kind; /* rtw_texture_kind + 1 of that texture; 0 = none */
+  uint32_t reserved[2]; /* 0 */
+} rtw_surface;       /* 64 bytes, 8-byte aligned */
+
+int rtw_world_surface_device(rtw_world w, const rtw_hit *d_hits, uint64_t n, const double background[3],
+                             rtw_surface *d_surf, rtw_guide *d_guides, void *stream);
+int rtw_scene_surface_device(rtw_scene s, const rtw_hit *d_hits, uint64_t n, const double background[3],
+                             rtw_surface *d_surf, rtw_guide *d_guides, void *stream);
+/* HOST buffers, synchronous (allocate, copy, query, copy back): for a pick. */
+int rtw_world_surface(rtw_world w, const rtw_hit *hits, uint64_t n, rtw_surface *surf_out);
+
 /* =================================================== temporal accumulation ===
  *   An animation's frames share what they see: each pixel's
  * first-hit surface point is followed back into the previous frame, and where it
@@ -889,7 +945,8 @@ int rtw_world_query_info(rtw_world w, const rtw_query_opts *opts, uint32_t info_
  * mirror's own surface point.
  *
  * One frame: render (seed + k: equal seeds give equal noise, which no mean
- * reduces), rtw_pixel_rays_device, rtw_world_trace_device, rtw_world_guides_device,
+ * reduces), rtw_pixel_rays_device, rtw_world_trace_device, the guides (off those
+ * hits with rtw_world_surface_device, or rtw_world_guides_device: the same bytes),
  * rtw_world_prev_points_device with the previous frame's numbers,
  * rtw_temporal_device, then rtw_denoise_device on d_mean_out with d_var_out as
  * its d_var.  The caller ping-pongs two history images.

@@ -493,6 +493,19 @@ int rtw_scene_guides_device(rtw_scene sc, const rtw_camera* cam, const rtw_param
   return RTW_OK;
 }
 
+}  // extern "C"
+
+int rtw_scene_view(rtw_scene sc, const char* who, rtwk::SceneView<double>* view) {
+  if (!sc) return rtw_fail(RTW_EINVAL, "%s: scene is NULL", who);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != sc->device) return rtw_fail(RTW_EINVAL, "%s: scene lives on device %d, current is %d", who, sc->device, dev);
+  *view = sc->v64;
+  return RTW_OK;
+}
+
+extern "C" {
+
 // Ray queries over a scene (rtw_hip.h "ray queries"; rtw_query.hip scene_query_kernel).
 static int scene_query(const char* who, rtw_scene sc, const rtw_ray* d_rays, uint64_t n, void* d_out, bool occlusion,
                        void* stream) {

@@ -120,8 +120,10 @@ int rtw_run_wavefront(const rtwk::TraceArgs<R>& ta, const rtw_params* p, unsigne
 // feature buffers (rtw_guides.hip): checks the arguments of a guide entry and fills the feature ray
 int rtw_guide_ray_fill(rtwk::GuideRay& g, const char* who, const rtw_camera* cam, const rtw_params* p, void* d_guides);
 // The device tables of an uploaded world (rtw_world_capi.hip), for entries in other files: RTW_EINVAL when the
-// world is NULL or lives on another device than the current one.
-int rtw_world_view(rtw_world w, const char* who, rtwk::WorldView* view);
+// world is NULL or lives on another device than the current one.  feat (optional): the features the world uses
+// (rtw_world.hip kFeat*), which pick a kernel's instantiation.  rtw_scene_view: the same for a scene's f64 tables.
+int rtw_world_view(rtw_world w, const char* who, rtwk::WorldView* view, uint32_t* feat = nullptr);
+int rtw_scene_view(rtw_scene sc, const char* who, rtwk::SceneView<double>* view);
 // accumulator passes (rtw_accum_capi.hip)
 bool rtw_accum_size_params(const rtw_params* p, uint32_t n, rtw_params* pp);
 int rtw_accum_pass_begin(rtw_accum a, uint32_t pass_spp, rtw_params* pp, uint64_t* seed_adv);

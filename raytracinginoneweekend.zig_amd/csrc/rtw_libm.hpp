@@ -16,9 +16,13 @@
 // same inputs plus the sphere-UV edges and every interval bound.  Compiled
 // with -ffp-contract=off: one IEEE operation per source operation.  sin/cos
 // with |x| >= 2^20 * pi/2 (the Payne-Hanek range, never produced by the
-// reference's scenes) return the platform libm's value — ocml's on the
-// device, glibc's in the oracle: outside the contract, and they do differ
-// (3 % of results, by 1 ulp; the device check prints the count; DESIGN.md, "Tier-B libm").
+// reference's scenes) are outside the contract: the oracle and the host
+// build return glibc's value.  The device returns, for sin below 2^32 — where
+// a surface query's caller can put a noise texture's argument — the value
+// rounded to nearest (sin_far below; tests/native/sin_far_check.cpp), which
+// glibc's is for 99.9 % of arguments, and ocml's beyond and for cos (3 % of
+// those differ from glibc's, by 1 ulp; the device check prints the count;
+// DESIGN.md, "Tier-B libm" and §19.3).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -142,13 +146,66 @@ RTWL_HD bool rem_pio2(double x, double& y0, double& y1, int& n) {
   return true;
 }
 
+// sin for 2^20 * pi/2 <= |x| < 2^32, rounded to nearest: every step carries a
+// pair of doubles (h + l, |l| <= ulp(h)/2), so the result's error is about
+// 2^-70 of itself before the one final rounding.
+//   x - fn * (pi/2): pi/2 = C1 + C2 + C3 (159 bits); fn * C1 and fn * C2 are
+//   taken exactly (a product and its fma remainder), x - fn * C1 is exact
+//   (Sterbenz), and what is dropped (the remainder of fn * C3, pi/2 beyond C3) is
+//   below 2^-128 — against a reduced argument that for these x stays above 2^-60.
+//   sin or cos of it: the Taylor series, 13 terms (|r| < 0.8: the 14th is below
+//   2^-75 of the sum), each from the last by * r^2 / ((m + 1)(m + 2)); the loop
+//   stays rolled, this path is cold.
+RTWL_HD void two_sum(double a, double b, double& s, double& e) {
+  s = a + b;
+  const double bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+}
+RTWL_HD double sin_far(double x) {
+  constexpr double toint = 6755399441055744.0, invpio2 = 6.36619772367581382433e-01;
+  constexpr double C1 = 0x1.921fb54442d18p+0, C2 = 0x1.1a62633145c07p-54, C3 = -0x1.f1976b7ed8fbcp-110;
+  const double fn = (x * invpio2 + toint) - toint;
+  const double h1 = fn * C1, l1 = __builtin_fma(fn, C1, -h1);
+  const double h2 = fn * C2, l2 = __builtin_fma(fn, C2, -h2);
+  double s, e1, e2, rh, rl;
+  two_sum(x - h1, -l1, s, e1);
+  two_sum(s, -h2, s, e2);
+  two_sum(s, ((e1 + e2) - l2) - fn * C3, rh, rl);
+  // r^2 as a pair
+  double zh = rh * rh, zl = __builtin_fma(rh, rh, -zh) + 2.0 * (rh * rl);
+  two_sum(zh, zl, zh, zl);
+  const uint32_t q = (uint32_t)(int64_t)fn & 3u;
+  double th = (q & 1u) ? 1.0 : rh, tl = (q & 1u) ? 0.0 : rl;  // the first term: 1 (cos) or r (sin)
+  double sh = th, sl = tl;
+  double m = (q & 1u) ? 0.0 : 1.0;
+  for (int k = 0; k < 13; ++k) {
+    // t = -t * z / ((m + 1)(m + 2))
+    const double p = th * zh, pe = __builtin_fma(th, zh, -p) + (th * zl + tl * zh);
+    const double d = (m + 1.0) * (m + 2.0);
+    const double q1 = p / d, q2 = (__builtin_fma(-q1, d, p) + pe) / d;
+    th = -(q1 + q2);
+    tl = -(q2 - (-th - q1));
+    m += 2.0;
+    double a, b;
+    two_sum(sh, th, a, b);
+    b += sl + tl;
+    sh = a + b;
+    sl = b - (sh - a);
+  }
+  return (q & 2u) ? -sh : sh;
+}
+
 RTWL_HD double sin(double x) {
   const uint32_t ix = hi(x) & 0x7fffffffu;
   if (ix <= 0x3fe921fbu) return ix < 0x3e500000u ? x : k_sin(x, 0.0, 0);
   if (ix >= 0x7ff00000u) return x - x;
   double y0, y1;
   int n;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (!rem_pio2(x, y0, y1, n)) return ix < 0x41f00000u ? sin_far(x) : ::sin(x);
+#else
   if (!rem_pio2(x, y0, y1, n)) return ::sin(x);
+#endif
   switch (n & 3) {
     case 0: return k_sin(y0, y1, 1);
     case 1: return k_cos(y0, y1);

@@ -11,6 +11,16 @@
 //              [--pick X,Y] [--focus-at X,Y]
 //              [--frames N [--orbit DEG] [--rebuild-above R]
 //                          [--temporal [--temporal-history M] [--denoise ...]]]
+//              [--aov-dir DIR]
+// --aov-dir DIR writes the frame's feature buffers as two more images, DIR/albedo.ppm
+// and DIR/normal.ppm (with --frames one pair per frame, albedo_%04d.ppm and
+// normal_%04d.ppm): the guides of the frame's feature rays (rtw_hip.h "Guides"), read
+// off their first hits by rtw_world_surface_device.  Albedo: each
+// f32 channel a is quantised as a render quantises a linear colour,
+// byte = (uint8)(256 * max(0, min(sqrt(a), 0.999))) in f64.  Normal: each component
+// n goes through the same quantiser without the gamma,
+// byte = (uint8)(256 * max(0, min(0.5 * (n + 1), 0.999))); a miss (normal 0,0,0) is
+// mid-grey and its albedo the background.  Without the option nothing changes.
 // --pick X,Y traces the feature ray of pixel (X, image row Y) (rtw_pixel_ray,
 // rtw_world_trace) and prints one line,
 //   pick x=.. y=.. prim=.. t=.. p=..,..,.. front=.. material=<kind>   (or: pick x=.. y=.. miss)
@@ -160,6 +170,21 @@ static std::shared_ptr<rtw::Image> loadPNG(const std::string& path) {
   return im;
 }
 
+// --aov-dir: the two images of a frame's guides (the rules: this file's header comment); k < 0: a single frame.
+static uint8_t quantise_unit(double x) { return (uint8_t)(256.0 * std::fmax(0.0, std::fmin(x, 0.999))); }
+static void writeAovs(const std::string& dir, int k, const std::vector<rtw_guide>& g, uint32_t w, uint32_t h) {
+  std::vector<uint8_t> albedo(g.size() * 3), normal(g.size() * 3);
+  for (size_t i = 0; i < g.size(); ++i)
+    for (int c = 0; c < 3; ++c) {
+      albedo[3 * i + c] = quantise_unit(std::sqrt((double)g[i].albedo[c]));
+      normal[3 * i + c] = quantise_unit(0.5 * ((double)g[i].normal[c] + 1.0));
+    }
+  char suffix[32] = "";
+  if (k >= 0) std::snprintf(suffix, sizeof(suffix), "_%04d", k);
+  rtw::writePPM(dir + "/albedo" + suffix + ".ppm", albedo, w, h);
+  rtw::writePPM(dir + "/normal" + suffix + ".ppm", normal, w, h);
+}
+
 int main(int argc, char** argv) {
   uint32_t scene = 6;  // main.zig:313
   uint32_t width = 0, spp = 0, depth = 50, chunk = 0, precision = RTW_PRECISION_F64, engine = RTW_ENGINE_MEGAKERNEL;
@@ -167,7 +192,7 @@ int main(int argc, char** argv) {
   double orbit = 0, rebuild_above = -1.0;  // (< 0: never rebuild)
   double aspect = 0, max_noise = 0, pixel_noise = 0;
   uint64_t seed = 42;
-  std::string out = "out.ppm", image_path, preview_dir, spp_map;
+  std::string out = "out.ppm", image_path, preview_dir, spp_map, aov_dir;
   bool denoise = false, denoise_spatial = false, temporal = false;
   uint32_t denoise_levels = 0, temporal_history = 0;
   bool pick = false, focus_at = false;
@@ -198,6 +223,7 @@ int main(int argc, char** argv) {
     else if (k == "--pixel-noise") pixel_noise = std::atof(v);
     else if (k == "--min-spp") min_spp = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--spp-map") spp_map = v;
+    else if (k == "--aov-dir") aov_dir = v;
     else if (k == "--frames") frames = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--orbit") orbit = std::atof(v);
     else if (k == "--rebuild-above") rebuild_above = std::atof(v);
@@ -372,12 +398,17 @@ int main(int argc, char** argv) {
         rtw::writePPM(dir + name, img, W, H);
         rgb = img;
       };
+      rtw::GuideFn write_guides;  // (empty without --aov-dir: the frames then compute nothing for it)
+      if (!aov_dir.empty()) {
+        (void)mkdir(aov_dir.c_str(), 0777);  // (an existing directory is fine)
+        write_guides = [&](uint32_t k, const std::vector<rtw_guide>& g) { writeAovs(aov_dir, (int)k, g, W, H); };
+      }
       if (temporal) {
         rtw::TemporalRun run;
         run.max_history = temporal_history, run.denoise = denoise, run.dn = dn;
-        rtw::renderOrbitTemporal(cam.to_c(), p, desc, frames, orbit, write_frame, run, rebuild_above);
+        rtw::renderOrbitTemporal(cam.to_c(), p, desc, frames, orbit, write_frame, run, rebuild_above, write_guides);
       } else {
-        rtw::renderOrbit(cam.to_c(), p, desc, frames, orbit, write_frame, rebuild_above);
+        rtw::renderOrbit(cam.to_c(), p, desc, frames, orbit, write_frame, rebuild_above, write_guides);
       }
     } else if (scene == 1 && pass_spp) {
       p.precision = precision, p.engine = engine;
@@ -402,6 +433,11 @@ int main(int argc, char** argv) {
       }
     }
     rtw::writePPM(out, rgb, W, H);  // main.zig:405
+    if (!aov_dir.empty() && frames == 1) {  // (with --frames the frames wrote theirs)
+      (void)mkdir(aov_dir.c_str(), 0777);
+      const rtw::FlatWorld fw = rtw::flattenWorld(world);
+      writeAovs(aov_dir, -1, rtw::frameGuides(cam.to_c(), W, H, st.background, fw.desc()), W, H);
+    }
     if (max_noise > 0) std::fprintf(stderr, "noise budget %g: %u of %u samples used\n", max_noise, used, S);
     if (pixel_noise > 0) {
       uint64_t total = 0;

@@ -813,12 +813,13 @@ int rtw_world_render(const rtw_camera* cam, const rtw_world_desc* desc, const rt
 
 }  // extern "C"
 
-int rtw_world_view(rtw_world w, const char* who, rtwk::WorldView* view) {
+int rtw_world_view(rtw_world w, const char* who, rtwk::WorldView* view, uint32_t* feat) {
   if (!w) return rtw_fail(RTW_EINVAL, "%s: world is NULL", who);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
   if (dev != w->device) return rtw_fail(RTW_EINVAL, "%s: world lives on device %d, current is %d", who, w->device, dev);
   *view = w->view;
+  if (feat) *feat = w->feat;
   return RTW_OK;
 }
 
@@ -880,17 +881,56 @@ void orbit_apply(rtw_world w, const rtw_world_desc& desc, uint32_t k, double deg
     fprintf(stderr, "rebuild frame=%u cost_before=%.6g cost_after=%.6g\n", k, cost, built_cost);
   }
 }
+// A frame's feature buffers from its feature rays' first hits (rtw_hip.h "surface queries"), on the null
+// stream, and their copy to the host.
+struct GuidePass {
+  rtw_ray* d_rays = nullptr;
+  rtw_hit* d_hits = nullptr;
+  rtw_guide* d_guides = nullptr;
+  std::vector<rtw_guide> host;
+  void alloc(OrbitDev& d, const char* who, size_t npix) {
+    d_rays = static_cast<rtw_ray*>(d.alloc(who, npix * sizeof(rtw_ray)));
+    d_hits = static_cast<rtw_hit*>(d.alloc(who, npix * sizeof(rtw_hit)));
+    d_guides = static_cast<rtw_guide*>(d.alloc(who, npix * sizeof(rtw_guide)));
+  }
+  void run(rtw_world w, const rtw_camera& cam, uint32_t W, uint32_t H, const double bg[3]) {
+    const size_t npix = (size_t)W * H;
+    ok(rtw_pixel_rays_device(&cam, W, H, d_rays, nullptr));
+    ok(rtw_world_trace_device(w, d_rays, npix, nullptr, d_hits, nullptr));
+    ok(rtw_world_surface_device(w, d_hits, npix, bg, nullptr, d_guides, nullptr));
+  }
+  const std::vector<rtw_guide>& fetch(const rtw_guide* from, size_t npix) {
+    host.resize(npix);
+    if (hipMemcpy(host.data(), from, npix * sizeof(rtw_guide), hipMemcpyDeviceToHost) != hipSuccess)
+      throw Error(RTW_EHIP, "the feature buffers failed on the device");
+    return host;
+  }
+};
 }  // namespace
 
+std::vector<rtw_guide> frameGuides(const rtw_camera& cam, uint32_t W, uint32_t H, const double background[3],
+                                   const rtw_world_desc& desc) {
+  OrbitDev d;
+  ok(rtw_world_create(&desc, 0, &d.w));
+  GuidePass g;
+  g.alloc(d, "frameGuides", (size_t)W * H);
+  g.run(d.w, cam, W, H, background);
+  return g.fetch(g.d_guides, (size_t)W * H);
+}
+
 void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames, double deg,
-                 const FrameFn& on_frame, double rebuild_above) {
+                 const FrameFn& on_frame, double rebuild_above, const GuideFn& on_guides) {
   OrbitDev d;
   ok(rtw_world_create(&desc, RTW_WORLD_DYNAMIC, &d.w));
   const size_t wsb = rtw_world_workspace_bytes(d.w, &p);
   if (wsb == 0) throw Error(RTW_EINVAL, rtw_last_error());
+  if (on_guides && (p.row_begin != 0 || p.row_stride != 1 || p.row_count != p.height))
+    throw Error(RTW_UNSUPPORTED, "renderOrbit: the feature buffers need whole frames of contiguous rows");
   std::vector<uint8_t> rgb((size_t)p.width * p.row_count * 3);
   void* ws = d.alloc("renderOrbit", wsb);
   uint8_t* d_rgb = static_cast<uint8_t*>(d.alloc("renderOrbit", rgb.size()));
+  GuidePass gp;
+  if (on_guides) gp.alloc(d, "renderOrbit", (size_t)p.width * p.height);
   std::vector<rtw_prim> prims(desc.prims, desc.prims + desc.n_prims);
   std::vector<rtw_xform> xforms(desc.xforms, desc.xforms + desc.n_xforms);
   double built_cost = 0.0;  // the tree cost right after the creation or the last rebuild
@@ -901,12 +941,17 @@ void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_des
     if (hipMemcpy(rgb.data(), d_rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)
       throw Error(RTW_EHIP, "renderOrbit: the render failed on the device");
     on_frame(k, rgb);
+    if (on_guides) {
+      gp.run(d.w, cam, p.width, p.height, p.background);
+      on_guides(k, gp.fetch(gp.d_guides, (size_t)p.width * p.height));
+    }
   }
 }
 
 // The frames of renderOrbit, each accumulated over the ones before it (rtw_hip.h "temporal accumulation").
 void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p0, const rtw_world_desc& desc, uint32_t frames,
-                         double deg, const FrameFn& on_frame, const TemporalRun& run, double rebuild_above) {
+                         double deg, const FrameFn& on_frame, const TemporalRun& run, double rebuild_above,
+                         const GuideFn& on_guides) {
   const char* who = "renderOrbitTemporal";
   OrbitDev d;
   if (p0.row_begin != 0 || p0.row_stride != 1 || p0.row_count != p0.height)
@@ -937,6 +982,7 @@ void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p0, const rtw_
   rtw_temporal_opts to{};
   to.max_history = run.max_history;
   std::vector<uint8_t> rgb(npix * 3);
+  GuidePass guide_copy;  // (its host vector only: the guides are the loop's own)
   std::vector<float> acc;
   std::vector<rtw_prim> prims(desc.prims, desc.prims + desc.n_prims);
   std::vector<rtw_xform> xforms(desc.xforms, desc.xforms + desc.n_xforms);
@@ -960,7 +1006,8 @@ void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p0, const rtw_
     ok(rtw_world_render_device(d.w, &cam, &p, ws, wsb, d_rgb, d_mean, nullptr, nullptr));
     ok(rtw_pixel_rays_device(&cam, W, H, d_rays, nullptr));
     ok(rtw_world_trace_device(d.w, d_rays, npix, nullptr, d_hits, nullptr));
-    ok(rtw_world_guides_device(d.w, &cam, &p, d_guides, nullptr));
+    // the frame's guides from the hits it already has: rtw_world_guides_device's bytes
+    ok(rtw_world_surface_device(d.w, d_hits, npix, p.background, nullptr, d_guides, nullptr));
     const bool reproject = k && moves;
     if (reproject)
       ok(rtw_world_prev_points_device(d.w, d_hits, npix, time, na ? d_a_prev : nullptr, nxv ? d_xv_prev : nullptr, d_pp,
@@ -981,6 +1028,7 @@ void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p0, const rtw_
       for (size_t i = 0; i < acc.size(); ++i) rgb[i] = rtwd::quantise((double)acc[i]);
     }
     on_frame(k, rgb);
+    if (on_guides) on_guides(k, guide_copy.fetch(d_guides, npix));
   }
 }
 

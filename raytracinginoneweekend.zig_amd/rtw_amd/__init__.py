@@ -135,6 +135,17 @@ HIT_DTYPE = np.dtype([("t", np.float64), ("p", np.float64, 3), ("normal", np.flo
 QUERY_MAX_RAYS = 1 << 31  # rtw_hip.h RTW_QUERY_MAX_RAYS
 
 
+class Surface(C.Structure):
+    """rtw_surface: what the surface under a hit record is (64 bytes; a miss is all zero; kind, mat, tex and
+    tex_kind are the enumeration value or index + 1)."""
+    _fields_ = [("value", C.c_double * 3), ("fuzz", C.c_double), ("ir", C.c_double), ("kind", C.c_uint32),
+                ("mat", C.c_uint32), ("tex", C.c_uint32), ("tex_kind", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+SURFACE_DTYPE = np.dtype([("value", np.float64, 3), ("fuzz", np.float64), ("ir", np.float64), ("kind", np.uint32),
+                          ("mat", np.uint32), ("tex", np.uint32), ("tex_kind", np.uint32), ("reserved", np.uint32, 2)])
+
+
 def query_opts(traversal="auto") -> QueryOpts:
     return QueryOpts(WORLD_TRAVERSAL[traversal] if isinstance(traversal, str) else int(traversal), 0)
 
@@ -276,6 +287,10 @@ def lib() -> C.CDLL:
                                                    C.c_void_p, C.c_void_p, C.c_void_p]
         L.rtw_world_prev_points_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]
+    if hasattr(L, "rtw_world_surface_device"):  # surface queries
+        for f in (L.rtw_world_surface_device, L.rtw_scene_surface_device):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rtw_world_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     _lib = L
     return L
 
@@ -330,6 +345,13 @@ def pixel_ray(cam: Camera, width: int, height: int, x: int, y: int) -> Ray:
 
 def _vp(p):
     return C.c_void_p(p) if p else None
+
+
+def _surface(entry, handle, hits_ptr, n, surf_ptr, guides_ptr, background, stream):
+    """rtw_world_surface_device / rtw_scene_surface_device on device pointers (DeviceWorld.surface,
+    DeviceScene.surface)."""
+    bg = (C.c_double * 3)(*background) if background is not None else None
+    _check(entry(handle, _vp(hits_ptr), n, bg, _vp(surf_ptr), _vp(guides_ptr), _vp(stream)))
 
 
 def temporal_device(mean_ptr: int, guides_ptr: int, prev_p_ptr: int | None, cam_prev: Camera, cam: Camera,
@@ -503,6 +525,13 @@ class DeviceScene:
         out = np.zeros(r.shape, HIT_DTYPE)
         _check(lib().rtw_scene_trace(self.h, r.ctypes.data, r.size, out.ctypes.data))
         return out
+
+    def surface(self, hits_ptr: int, n: int, surf_ptr: int | None = None, guides_ptr: int | None = None,
+                background=None, stream: int | None = None):
+        """rtw_scene_surface_device: for n rtw_hit records of this scene in device memory, n rtw_surface
+        records (64 bytes each) and / or n rtw_guide records, asynchronous on `stream`; the materials are
+        reported in the world's enumerations.  `background` (three numbers) is needed with guides_ptr."""
+        _surface(lib().rtw_scene_surface_device, self.h, hits_ptr, n, surf_ptr, guides_ptr, background, stream)
 
     def counts(self, cam: Camera, params: Params, workspace_ptr: int, workspace_bytes_: int) -> dict:
         out = (C.c_uint64 * 6)()

@@ -6,8 +6,8 @@ from __future__ import annotations
 
 import torch
 
-from . import (Accumulator, Camera, DeviceScene, Params, QueryOpts, TemporalOpts, Timer, temporal_device,
-               workspace_bytes)
+from . import (Accumulator, Camera, DeviceScene, Params, QueryOpts, TemporalOpts, Timer, pixel_rays_device,
+               temporal_device, workspace_bytes)
 
 
 class TorchRenderer:
@@ -184,6 +184,8 @@ class TorchTracer:
         tr = TorchTracer(world)
         hit = tr.trace(origins, dirs)          # (N, 3) float64 device tensors
         lit = ~tr.occluded(hit["p"], to_light, t_max=1.0)
+        what = tr.surface(hit)                 # material kind / index, texture value, fuzz, ir per hit
+        g = tr.guides(cam, W, H, background)   # a frame's rtw_guide records from one BVH trace
     """
 
     def __init__(self, target, device: int | torch.device | None = None):
@@ -235,6 +237,46 @@ class TorchTracer:
         out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=self.device)
         self._launch(self.target.occluded, rays, out, opts)
         return out != 0
+
+    def surface(self, hits, guides: bool = False, background=None) -> dict:
+        """What the surfaces under `hits` are (rtw_hip.h "surface queries"): hits is trace()'s dict or its
+        (N, 10) float64 record tensor.  A dict of tensors viewing one (N, 8) float64 record buffer
+        (rtw_surface) — value (N, 3), fuzz (N,), ir (N,) — and kind, mat, tex, tex_kind (N,) int64: the
+        rtw_wmaterial_kind, material index, texture index and rtw_texture_kind, -1 where there is none (a
+        miss; tex of a metal, a glass or a scene).  guides=True adds "guides": (N, 32) uint8 rtw_guide
+        records of those rays (`background`: a miss's albedo)."""
+        rec_in = hits["records"] if isinstance(hits, dict) else hits
+        if rec_in.dtype != torch.float64 or rec_in.dim() != 2 or rec_in.shape[1] != 10 or not rec_in.is_contiguous():
+            raise ValueError("hits must be trace()'s result or its contiguous (N, 10) float64 records")
+        n = rec_in.shape[0]
+        rec = torch.empty((n, 8), dtype=torch.float64, device=self.device)
+        g = torch.empty((n, 32), dtype=torch.uint8, device=self.device) if guides else None
+        if n:
+            self.target.surface(rec_in.data_ptr(), n, rec.data_ptr(), g.data_ptr() if guides else None,
+                                background if guides else None, torch.cuda.current_stream(self.device).cuda_stream)
+        words = rec.view(torch.int32)[:, 10:14].to(torch.int64) - 1  # {kind, mat, tex, tex_kind}, each + 1
+        out = {"value": rec[:, 0:3], "fuzz": rec[:, 3], "ir": rec[:, 4], "kind": words[:, 0], "mat": words[:, 1],
+               "tex": words[:, 2], "tex_kind": words[:, 3], "records": rec}
+        if guides:
+            out["guides"] = g
+        return out
+
+    def guides(self, cam: Camera, width: int, height: int, background) -> torch.Tensor:
+        """A frame's feature buffers, (height, width, 32) uint8 rtw_guide records, from the frame's feature
+        rays (rtw_pixel_rays_device), their closest hits and the surface query: the bytes of
+        rtw_world_guides_device / rtw_scene_guides_device of the whole frame, at the cost of one BVH trace.
+        On torch's current stream; the ray and hit tensors are kept between calls of one size."""
+        n = width * height
+        if getattr(self, "_frame_n", None) != n:
+            self._frame_rays = torch.empty((n, 9), dtype=torch.float64, device=self.device)
+            self._frame_hits = torch.empty((n, 10), dtype=torch.float64, device=self.device)
+            self._frame_n = n
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        pixel_rays_device(cam, width, height, self._frame_rays.data_ptr(), stream)
+        self._launch(self.target.trace, self._frame_rays, self._frame_hits, None)
+        g = torch.empty((height, width, 32), dtype=torch.uint8, device=self.device)
+        self.target.surface(self._frame_hits.data_ptr(), n, None, g.data_ptr(), background, stream)
+        return g
 
 
 def update_world(dw, a: torch.Tensor, xv: torch.Tensor | None = None):

@@ -19,7 +19,8 @@ import zlib
 
 import numpy as np
 
-from . import HIT_DTYPE, RAY_DTYPE, RTW_EINVAL, Camera, Params, QueryOpts, RtwError, Timer, _check, camera_init, lib
+from . import (HIT_DTYPE, RAY_DTYPE, RTW_EINVAL, SURFACE_DTYPE, Camera, Params, QueryOpts, RtwError, Timer, _check,
+               _surface, camera_init, lib)
 
 PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_XY_RECT, PRIM_XZ_RECT, PRIM_YZ_RECT = 0, 1, 2, 3, 4
 XF_TRANSLATE, XF_ROTATE_Y = 0, 1
@@ -478,6 +479,22 @@ class DeviceWorld:
         out = np.zeros(r.shape, HIT_DTYPE)
         _check(_wlib().rtw_world_trace(self.h, r.ctypes.data, r.size, C.byref(opts) if opts is not None else None,
                                        out.ctypes.data))
+        return out
+
+    def surface(self, hits_ptr: int, n: int, surf_ptr: int | None = None, guides_ptr: int | None = None,
+                background=None, stream: int | None = None):
+        """rtw_world_surface_device: for n rtw_hit records of this world in device memory (trace()'s), what
+        each hit surface is — n rtw_surface records (SURFACE_DTYPE, 64 bytes: the material's kind and index,
+        its texture's value at the hit, fuzz, ir) into surf_ptr and / or the n rtw_guide records of those rays
+        into guides_ptr, at least one; asynchronous on `stream`.  `background` (three numbers, a miss's
+        albedo) is needed with guides_ptr."""
+        _surface(_wlib().rtw_world_surface_device, self.h, hits_ptr, n, surf_ptr, guides_ptr, background, stream)
+
+    def surface_host(self, hits) -> np.ndarray:
+        """rtw_world_surface: hits (n,) HIT_DTYPE on the host -> (n,) SURFACE_DTYPE, synchronous."""
+        h = np.ascontiguousarray(hits, HIT_DTYPE)
+        out = np.zeros(h.shape, SURFACE_DTYPE)
+        _check(_wlib().rtw_world_surface(self.h, h.ctypes.data, h.size, out.ctypes.data))
         return out
 
     def prev_points_device(self, hits_ptr: int, n: int, time: float, out_ptr: int, a_prev_ptr: int | None = None,

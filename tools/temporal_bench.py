@@ -10,7 +10,10 @@ the globe + 10k spheres (scene 7, the real map).
 time: at the scene's own size (1200x675), HIP events around each call, the calls
 alternating in one process after a warm-up round, median (min .. max), each
 beside its traffic floor at the 6.29 TB/s copy rate; the 20-sample render for
-scale; the shader clock (rtw_sclk_probe) noted.
+scale; the shader clock (rtw_sclk_probe) noted.  The frame's guides both ways, in
+the same run: rtw_world_guides_device, and rtw_world_surface_device over the
+frame's hits (equal bytes, checked first), with the animated
+frame's total for each.
 quality: frames of 20 spp, every sphere centre turned by 1 or 5 degrees per frame
 (rtw_orbit.hpp's motion), RMSE of the linear mean against ref-spp frames of the
 same positions, for the input, the spatial denoiser alone, temporal alone and
@@ -136,6 +139,10 @@ def main():
         def make_guides(self, p):
             self.dw.guides(self.cam, p, self.guides.data_ptr(), stream())
 
+        def surface_guides(self):
+            """The same guides read off the frame's hits (rtw_world_surface_device)."""
+            self.dw.surface(self.hits.data_ptr(), self.n, None, self.guides.data_ptr(), self.b.background, stream())
+
         def prev_points(self, a_prev, xv_prev):
             self.dw.prev_points_device(self.hits.data_ptr(), self.n, 0.5, self.pp.data_ptr(), a_prev.data_ptr(),
                                        xv_prev.data_ptr() if xv_prev is not None else None, stream())
@@ -175,17 +182,24 @@ def main():
             sc.pixel_rays(), sc.trace(), sc.make_guides(p), sc.prev_points(a_prev, xv_prev)
             temporal(None, hist[0].data_ptr(), None)  # a first frame: every record holds history from here on
             torch.cuda.synchronize()
+            kernel_guides = sc.guides.clone()  # both ways to the guides give the same bytes: checked before either is timed
+            sc.guides.fill_(0xA5)
+            sc.surface_guides()
+            torch.cuda.synchronize()
+            if not torch.equal(kernel_guides, sc.guides):
+                raise SystemExit(f"scene {sid}: rtw_world_surface_device's guides differ from rtw_world_guides_device's")
             steps = {
                 "render (20 spp, all kernels)": lambda: sc.render(p),
                 "rtw_pixel_rays_device": sc.pixel_rays,
                 "rtw_world_trace_device": sc.trace,
                 "rtw_world_guides_device": lambda: sc.make_guides(p),
+                "rtw_world_surface_device (guides)": sc.surface_guides,
                 "rtw_world_prev_points_device": lambda: sc.prev_points(a_prev, xv_prev),
                 "rtw_temporal_device, static": lambda: temporal(hist[0].data_ptr(), hist[1].data_ptr(), None),
                 "rtw_temporal_device, motion": lambda: temporal(hist[0].data_ptr(), hist[1].data_ptr(), sc.pp.data_ptr()),
                 "rtw_denoise_device (+ spatial)": lambda: sc.denoise(acc, var),
             }
-            floors = {"rtw_pixel_rays_device": 72, "rtw_world_prev_points_device": 80 + 24,
+            floors = {"rtw_pixel_rays_device": 72, "rtw_world_prev_points_device": 80 + 24, "rtw_world_surface_device (guides)": 80 + 32,
                       "rtw_temporal_device, static": 12 + 32 + 32 + 48, "rtw_temporal_device, motion": 12 + 32 + 24 + 4 * 32 + 48}
             t = {k: [] for k in steps}
             trace_ms = []
@@ -221,6 +235,14 @@ def main():
                 f"guides {med['rtw_world_guides_device']:.3f} ms = {med['rtw_world_guides_device'] / (rend + extra) * 100:.1f} % of the frame; "
                 f"without the guides the steps are {extra - med['rtw_world_guides_device']:.3f} ms (+ {(extra - med['rtw_world_guides_device']) / rend * 100:.1f} %); "
                 f"the denoiser adds {med['rtw_denoise_device (+ spatial)']:.3f} ms")
+            # the guides read off the hits the frame already has (pixel rays and trace are in `extra` either way)
+            g_old, g_new = med["rtw_world_guides_device"], med["rtw_world_surface_device (guides)"]
+            new_extra = extra - g_old + g_new
+            say(f"  guides off the frame's hits (rtw_world_surface_device) {g_new:.4f} ms against rtw_world_guides_device {g_old:.4f} ms "
+                f"in this run (x{g_old / g_new:.1f}); per animated frame {rend + extra:.3f} ms -> {rend + new_extra:.3f} ms "
+                f"(temporal steps {extra:.3f} -> {new_extra:.3f} ms, + {new_extra / rend * 100:.1f} % of the render); a caller with no hits "
+                f"yet pays pixel rays + trace + surface = "
+                f"{med['rtw_pixel_rays_device'] + med['rtw_world_trace_device'] + g_new:.4f} ms for a frame's guides")
             sc.close()
 
     CLASSES = ("miss (the sky)", "ground (r >= 100)", "diffuse", "metal", "glass", "light")
