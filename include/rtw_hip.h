@@ -821,8 +821,17 @@ int rtw_accum_denoise_device(rtw_accum a, const rtw_guide *d_guides, const rtw_d
  * Input domain.  Components finite, dir != 0, time finite, t_min <= t_max,
  * t_max may be +inf; direction components that are exactly 0 are in the
  * domain, and a NaN root sends the ray through the reference's sequential loop
- * as in a render.  (A ray whose time lies outside [0, 1] on a world whose BVH
- * holds moving spheres takes that loop too: the boxes cover those times only.)
+ * as in a render, over a world and over a scene alike.  Finite components can
+ * produce one: where |dir|^2, (origin - centre) . dir or |origin - centre|^2
+ * overflows (a direction longer than 2^512) the discriminant is inf - inf,
+ * which the reference does not reject; it then accepts every later sphere
+ * whose discriminant is not negative, so the record is the last such sphere of
+ * the list with t = NaN (p, normal, u, v follow from that t) and the ray is
+ * occluded.  A direction so short that |dir|^2 underflows to 0 has roots of
+ * +-inf; +inf is accepted like any root.  (A ray whose time lies outside [0, 1]
+ * on a world whose BVH holds moving spheres takes the sequential loop too: the
+ * boxes cover those times only.  A scene extrapolates a moving sphere's centre
+ * linearly outside its own [t0, t1], as the reference does.)
  * The BVH's box tests (not the primitive tests) give a direction component that
  * is 0, or smaller than 2^-60 of the largest, that magnitude: the slab
  * arithmetic divides by it, and the shift stays far inside the boxes' margin.

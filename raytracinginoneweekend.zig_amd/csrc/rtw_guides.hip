@@ -1,15 +1,18 @@
 // rtw_guides.hip — the scene's feature buffers (rtw_hip.h
 // rtw_scene_guides_device): the first hit of each pixel's
 // feature ray over the packed sphere table, in f64.  One lane per pixel, a
-// wave-uniform loop over the table (scalar record loads); the winner is the
-// reference's — minimal effective root, ties to the later sphere of the list
-//  — and its hit record and checker value are computed as the
-// megakernel computes them (rtw_device.hpp scatter_hit).  Runs once per frame.
+// wave-uniform loop over the table (scalar record loads; scene_closest,
+// rtw_scene_hit.hpp, shared with the scene's ray queries); the winner is the
+// reference's — minimal effective root, ties to the later sphere of the list,
+// the sequential loop after a NaN root — and its hit record
+// and checker value are computed as the megakernel computes them
+// (rtw_device.hpp scatter_hit).  Runs once per frame.
 #include <hip/hip_runtime.h>
 
 #include "rtw_capi_shared.hpp"
 #include "rtw_guides.hpp"
 #include "rtw_math.hpp"
+#include "rtw_scene_hit.hpp"
 
 namespace rtwk {
 
@@ -25,41 +28,16 @@ __global__ void __launch_bounds__(kGuideTileW* kGuideTileH) scene_guides_kernel(
   V o, d;
   guide_ray(A.r, x, q, o, d);
   const D time = A.r.time, tmin = 0.001;
-  const D a = norm2(d);
-  int hit = -1, hit_orig = -1;
-  D hit_t = (D)__builtin_huge_val();
-  for (uint32_t k = 0; k < S.n; ++k) {  // (wave-uniform) Sphere.hit / MovingSphere.hit (hittable.zig:96-116, :166-187)
-    const D* sp = S.sph + 8 * k;
-    const uint32_t meta = S.meta[k];
-    V c = ld3(sp);
-    if (meta & kMoving) {
-      const D* tg = S.tg + 4 * ((meta >> 2) & 63u);
-      c = add(c, mul(ld3(sp + 3), (time - tg[0]) / (tg[1] - tg[0])));
-    }
-    const V oc = sub(o, c);
-    const D hb = dot(oc, d);
-    const D cc = norm2(oc) - sp[6];
-    const D disc = hb * hb - a * cc;
-    if (disc < 0.0) continue;
-    const D sq = sqrt(disc);
-    D root = (-hb - sq) / a;
-    if (root < tmin) root = (-hb + sq) / a;
-    if (root < tmin) continue;
-    const int orig = (int)(meta >> 20);
-    if ((root < hit_t) | ((root == hit_t) & (orig > hit_orig))) hit_t = root, hit = (int)k, hit_orig = orig;
-  }
+  const SceneHit sh = scene_closest<false>(S, o, d, time, tmin, (D)__builtin_huge_val());
+  const int hit = sh.pos, hit_orig = sh.orig;
+  const D hit_t = sh.t;
   if (hit < 0) {
     guide_store(A.r, x, q, mk(0.0, 0.0, 0.0), 0.0, ld3(A.r.bg), 0u);
     return;
   }
-  const D* sp = S.sph + 8 * hit;
   const uint32_t meta = S.meta[hit];
   const V p = add(o, mul(d, hit_t));
-  V c = ld3(sp);
-  if (meta & kMoving) {
-    const D* tg = S.tg + 4 * ((meta >> 2) & 63u);
-    c = add(c, mul(ld3(sp + 3), (time - tg[0]) / (tg[1] - tg[0])));
-  }
+  const V c = scene_center(S, (uint32_t)hit, meta, time);
   const V outward = divs(sub(p, c), S.rad[hit]);
   const V normal = dot(outward, d) < 0.0 ? outward : mul(outward, -1.0);
   const uint32_t mi = (meta >> 8) & 0xFFFu;

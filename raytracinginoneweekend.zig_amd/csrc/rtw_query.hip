@@ -11,6 +11,7 @@
 
 #include "rtw_device.hpp"
 #include "rtw_libm.hpp"
+#include "rtw_scene_hit.hpp"
 #include "rtw_world_walk.hpp"
 
 namespace rtwk {
@@ -157,7 +158,7 @@ __global__ void __launch_bounds__(kQueryBlock, 4) world_query_lane_kernel(WorldQ
   }
 }
 
-// Scenes: the wave-uniform loop of scene_guides_kernel (rtw_guides.hip) over
+// Scenes: scene_closest (rtw_scene_hit.hpp, shared with scene_guides_kernel) over
 // the packed sphere table, with the ray's own time, t_min and t_max.
 template <bool OCCL>
 __global__ void __launch_bounds__(kQueryBlock) scene_query_kernel(SceneQueryArgs A) {
@@ -170,32 +171,9 @@ __global__ void __launch_bounds__(kQueryBlock) scene_query_kernel(SceneQueryArgs
     if (i >= A.n) continue;
     const QRay q = load_ray(A.rays, i);
     const V &o = q.o, &d = q.d;
-    const D a = norm2(d);
-    int hit = -1, hit_orig = -1;
-    D hit_t = q.tmax;
-    for (uint32_t k = 0; k < S.n; ++k) {  // Sphere.hit / MovingSphere.hit (hittable.zig:96-116, :166-187)
-      const D* sp = S.sph + 8 * k;
-      const uint32_t meta = S.meta[k];
-      V c = ld3(sp);
-      if (meta & kMoving) {
-        const D* tg = S.tg + 4 * ((meta >> 2) & 63u);
-        c = add(c, mul(ld3(sp + 3), (q.time - tg[0]) / (tg[1] - tg[0])));
-      }
-      const V oc = sub(o, c);
-      const D hb = dot(oc, d);
-      const D cc = norm2(oc) - sp[6];
-      const D disc = hb * hb - a * cc;
-      if (disc < 0.0) continue;
-      const D sq = sqrt(disc);
-      D root = (-hb - sq) / a;
-      if (root < q.tmin) root = (-hb + sq) / a;
-      if (root < q.tmin) continue;
-      const int orig = (int)(meta >> 20);
-      if ((root < hit_t) | ((root == hit_t) & (orig > hit_orig))) hit_t = root, hit = (int)k, hit_orig = orig;
-      if constexpr (OCCL) {
-        if (!wany(hit < 0)) break;
-      }
-    }
+    const SceneHit sh = scene_closest<OCCL>(S, o, d, q.time, q.tmin, q.tmax);
+    const int hit = sh.pos, hit_orig = sh.orig;
+    const D hit_t = sh.t;
     if constexpr (OCCL) {
       static_cast<uint8_t*>(A.out)[i] = hit >= 0 ? (uint8_t)1 : (uint8_t)0;
     } else {
@@ -203,15 +181,10 @@ __global__ void __launch_bounds__(kQueryBlock) scene_query_kernel(SceneQueryArgs
         store_miss(A.out, i);
         continue;
       }
-      const D* sp = S.sph + 8 * hit;
       const uint32_t meta = S.meta[hit];
       HitRec R;
       R.p = add(o, mul(d, hit_t));
-      V c = ld3(sp);
-      if (meta & kMoving) {
-        const D* tg = S.tg + 4 * ((meta >> 2) & 63u);
-        c = add(c, mul(ld3(sp + 3), (q.time - tg[0]) / (tg[1] - tg[0])));
-      }
+      const V c = scene_center(S, (uint32_t)hit, meta, q.time);
       const V outward = divs(sub(R.p, c), S.rad[hit]);
       R.front = dot(outward, d) < 0.0;
       R.nrm = R.front ? outward : mul(outward, -1.0);

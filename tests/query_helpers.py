@@ -52,15 +52,15 @@ def _unit(rng):
     return v / np.sqrt((v * v).sum())
 
 
-def ray_set(rtw, ow, cam, look_from, seed):
-    """(rays, kinds): (a) the QW x QH feature rays of `cam` with random times in [0, 1); from every hit
+def ray_set(rtw, ow, cam, look_from, seed, w=QW, h=QH):
+    """(rays, kinds): (a) the w x h (QW x QH) feature rays of `cam` with random times in [0, 1); from every hit
     of (a): (b) a bounce normal + 0.999 unit, (c) an inward ray -normal + 0.5 unit, (d) a shadow ray
     towards 0.5 look_from + (0, 3, 0) with t_max = 1.  kinds[i] in "abcd"."""
     rng = np.random.default_rng(seed)
     rows = []
-    for y in range(QH):
-        for x in range(QW):
-            o, d, _ = feature_ray(cam, QW, QH, x, y)
+    for y in range(h):
+        for x in range(w):
+            o, d, _ = feature_ray(cam, w, h, x, y)
             rows.append((o, d, float(rng.random()), 0.001, np.inf))
     prim = make_rays(rtw, rows)
     hits = oracle_hits(rtw, ow, prim)

@@ -2,7 +2,7 @@
 """Throughput of the ray queries (rtw_world_trace_device / rtw_world_occluded_device,
 DESIGN.md §15) in Mrays/s, and the numbers behind the AUTO traversal rule.
 
-  python tools/query_bench.py [--rounds 3] [--window-ms 300] [--out FILE]
+  python tools/query_bench.py [--rounds 3] [--window-ms 300] [--out FILE] [--scene-api]
 
 Worlds: scene 7 (the globe with the real map, as bench.py uses it; 1200x675),
 scene 6 (the Cornell box, the linear loop; 600x600) and scene 1 as a world
@@ -18,7 +18,13 @@ reported.  On (P) the guides kernel (rtw_world_guides_device) of the same frame
 is timed the same way: before the queries it was the only first-hit facility,
 so its time is the baseline and the ratio is printed.  AUTO follows whichever
 of UNION / LANE is faster on (S); the verdict line says whether the two lie
-within the measured spread."""
+within the measured spread.
+
+--scene-api measures the scene entries instead (rtw_scene_trace_device / rtw_scene_occluded_device /
+rtw_scene_guides_device: scene_query_kernel and scene_guides_kernel over the packed sphere table) on
+cover_scene(42) at 1200x800 with the same (P) and (S) batches, and ends with one line
+"scene_api_ms closest_P=.. occlusion_P=.. closest_S=.. occlusion_S=.. guides=.." of the medians, for
+A/B runs of two libraries (RTW_LIB_PATH), each in a process of its own."""
 import argparse
 import math
 import os
@@ -35,6 +41,7 @@ def main():
     ap.add_argument("--window-ms", type=float, default=300.0)
     ap.add_argument("--max-launches", type=int, default=4000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--scene-api", action="store_true")
     args = ap.parse_args()
     import torch
     import rtw_amd as R
@@ -89,6 +96,43 @@ def main():
                 f"{counts[name]} launches x {len(ms)} rounds)")
 
     say(f"device: {torch.cuda.get_device_name(0)}")
+    if args.scene_api:
+        W, H = 1200, 800
+        sph, mats, _ = R.cover_scene(42)
+        sc = R.DeviceScene(sph, mats)
+        cam = R.cover_camera(W / H)
+        tr = TorchTracer(sc)
+        o, d, time = feature_rays(cam, W, H)
+        P = tr.pack(o, d, time=time)
+        hit = tr.trace(o, d, time=time)
+        torch.cuda.synchronize()
+        m = hit["prim"] >= 0
+        g = torch.Generator(device=dev)
+        g.manual_seed(1235)
+        u = torch.randn((int(m.sum()), 3), generator=g, dtype=torch.float64, device=dev)
+        u = u / u.norm(dim=1, keepdim=True)
+        S = tr.pack(hit["p"][m].contiguous(), hit["normal"][m] + u, time=time)
+        say(f"scene API, cover_scene(42) ({len(sph)} spheres), {W}x{H}: (P) {P.shape[0]} rays, {int(m.sum())} hit; (S) {S.shape[0]} rays"
+            f"; library {R.LIB_PATH}")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rec = torch.empty((P.shape[0], 10), dtype=torch.float64, device=dev)
+        occ = torch.empty((P.shape[0],), dtype=torch.uint8, device=dev)
+        guides = torch.empty((H, W, 32), dtype=torch.uint8, device=dev)
+        params = R.make_params(W, H, 1)
+        variants = {}
+        for label, rays in (("P", P), ("S", S)):
+            n = rays.shape[0]
+            variants[f"closest_{label}"] = (lambda rays=rays, n=n: sc.trace(rays.data_ptr(), n, rec.data_ptr(), stream), n)
+            variants[f"occlusion_{label}"] = (lambda rays=rays, n=n: sc.occluded(rays.data_ptr(), n, occ.data_ptr(), stream), n)
+        variants["guides"] = (lambda: sc.guides(cam, params, guides.data_ptr(), stream), P.shape[0])
+        res, counts = bench(variants)
+        report("  scene entries", variants, res, counts)
+        say("scene_api_ms " + " ".join(f"{k}={statistics.median(v):.5f}" for k, v in res.items()))
+        sc.close()
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     for sid, W, H in ((7, 1200, 675), (6, 600, 600), (1, 1200, 800)):
         img = Wd.earth_map() if sid == 7 else None
         built = Wd.BuiltScene(sid, 42, img)
