@@ -1018,6 +1018,48 @@ int rtw_temporal_host(const float *mean, const rtw_guide *guides, const double *
                       const rtw_temporal_opts *opts, rtw_history *hist_out,
                       float *mean_out, float *var_out, void *stream);
 
+/* The same accumulation with the history clamped to the current frame's
+ * neighbourhood: what a mirror or a glass shows moves although
+ * its surface point does not, and a history that no longer resembles the frame
+ * around the pixel is pulled into that frame's range before the blend.  New
+ * symbols only; rtw_temporal_device and rtw_temporal_host are untouched. */
+typedef struct {     /* every field 0 = its default */
+  double gamma;      /* finite, >= 0, < 1e30; 0 = the default, 0.5: the window's mean +- gamma sigma */
+  uint32_t radius;   /* 0 = default 1; 1..3: a (2r+1)^2 window */
+  uint32_t reserved; /* 0 */
+} rtw_temporal_clamp; /* 16 bytes */
+
+/* Steps 1 and 2 above unchanged.  Where the pixel has history, between "hist =
+ * the weight-normalised taps" and the blend (csrc/rtw_temporal_clamp.hpp; the
+ * same arithmetic rules, and sqrt):
+ *  a. Over the pixels (x + dx, y + dy), |dx|, |dy| <= radius, of d_mean in
+ *     row-major order, leaving out those outside the image and those with a
+ *     non-finite channel, n pixels: per channel mu = s / n, var = max(0, s2 / n -
+ *     mu mu), lo = mu - gamma sqrt(var), hi = mu + gamma sqrt(var).
+ *  b. n < 4: the history is left alone.  Else each channel of hist becomes
+ *     min(max(h, lo), hi).
+ *  c. If no channel changed nothing else does: the bytes are rtw_temporal_device's.
+ *     Else with d = luminance(h') - luminance(h): m2 = (m2 + (2 m1) d) + d d, then
+ *     m1 = m1 + d (the accumulated luminances move with the mean and keep their
+ *     variance); len is untouched.
+ * Steps 3 and 4 run on the result; a value that comes out NaN (a bad pixel in the
+ * frame or in the history) is stored as the quiet NaN 0x7FC00000, whatever NaN
+ * the instruction set produced.  clamp == NULL: exactly rtw_temporal_device /
+ * rtw_temporal_host.  Every argument check of rtw_temporal_device applies, and
+ * RTW_EINVAL also for a non-finite or negative gamma, gamma >= 1e30, radius > 3 or
+ * reserved != 0.  Asynchronous on `stream`, graph-capturable, no workspace, no
+ * state, no atomics; the device's bytes are the host's. */
+int rtw_temporal_clamped_device(const float *d_mean, const rtw_guide *d_guides, const double *d_prev_p,
+                                const rtw_camera *cam_prev, const rtw_camera *cam,
+                                const rtw_history *d_hist_in, uint32_t width, uint32_t height,
+                                const rtw_temporal_opts *opts, const rtw_temporal_clamp *clamp,
+                                rtw_history *d_hist_out, float *d_mean_out, float *d_var_out, void *stream);
+int rtw_temporal_clamped_host(const float *mean, const rtw_guide *guides, const double *prev_p,
+                              const rtw_camera *cam_prev, const rtw_camera *cam,
+                              const rtw_history *hist_in, uint32_t width, uint32_t height,
+                              const rtw_temporal_opts *opts, const rtw_temporal_clamp *clamp,
+                              rtw_history *hist_out, float *mean_out, float *var_out, void *stream);
+
 /* The width*height feature rays of a frame in row-major order, each record
  * byte-equal to rtw_pixel_ray's.  Asynchronous on `stream`.  RTW_EINVAL for null
  * pointers, width or height < 2, more than 2^31 pixels, d_rays not 8-byte aligned. */

@@ -10,7 +10,8 @@
 //              [--denoise [--denoise-levels N] [--denoise-spatial]]
 //              [--pick X,Y] [--focus-at X,Y]
 //              [--frames N [--orbit DEG] [--rebuild-above R]
-//                          [--temporal [--temporal-history M] [--denoise ...]]]
+//                          [--temporal [--temporal-history M] [--denoise ...]
+//                                      [--temporal-clamp G [--temporal-clamp-radius R]]]]
 //              [--aov-dir DIR]
 // --aov-dir DIR writes the frame's feature buffers as two more images, DIR/albedo.ppm
 // and DIR/normal.ppm (with --frames one pair per frame, albedo_%04d.ppm and
@@ -58,7 +59,12 @@
 // frames, default 32); each frame_%04d.ppm is the accumulated image, and with
 // --denoise the denoiser's image of it, steered by the temporal variance
 // (--denoise-spatial still fills the pixels whose history is too short for one).
-// Without --temporal every run and every refusal is unchanged.
+// --temporal-clamp G clamps the history to the frame's neighbourhood before the
+// blend: each channel to the mean +- G sigma of the current
+// frame's (2R+1)^2 window around the pixel (G = 0: the default gamma;
+// --temporal-clamp-radius R, 1-3, default 1).  Frame 0 has no history and keeps
+// its bytes.  Without --temporal every run and every refusal is unchanged, and
+// without --temporal-clamp every frame's bytes are.
 // Defaults are the reference's: scene 6 (main.zig:313) with that scene's own
 // size, spp, camera and background (main.zig:316-362); --width/--aspect/--spp
 // override them.  Scenes 4 and 7 need --image (assets/sekaichizu.png).
@@ -194,7 +200,9 @@ int main(int argc, char** argv) {
   uint64_t seed = 42;
   std::string out = "out.ppm", image_path, preview_dir, spp_map, aov_dir;
   bool denoise = false, denoise_spatial = false, temporal = false;
-  uint32_t denoise_levels = 0, temporal_history = 0;
+  uint32_t denoise_levels = 0, temporal_history = 0, temporal_clamp_radius = 0;
+  bool temporal_clamp = false, temporal_clamp_radius_set = false;
+  double temporal_clamp_gamma = 0;
   bool pick = false, focus_at = false;
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0};
   for (int i = 1; i < argc; i += 2) {
@@ -228,6 +236,10 @@ int main(int argc, char** argv) {
     else if (k == "--orbit") orbit = std::atof(v);
     else if (k == "--rebuild-above") rebuild_above = std::atof(v);
     else if (k == "--temporal-history") temporal_history = (uint32_t)std::strtoul(v, nullptr, 10);
+    else if (k == "--temporal-clamp") temporal_clamp = true, temporal_clamp_gamma = std::atof(v);
+    else if (k == "--temporal-clamp-radius") {
+      temporal_clamp_radius_set = true, temporal_clamp_radius = (uint32_t)std::strtoul(v, nullptr, 10);
+    }
     else if (k == "--denoise-levels") denoise_levels = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--pick" || k == "--focus-at") {
       const bool is_pick = k == "--pick";
@@ -252,6 +264,19 @@ int main(int argc, char** argv) {
   }
   if (temporal_history && !temporal) {
     std::fprintf(stderr, "--temporal-history needs --temporal\n");
+    return 2;
+  }
+  if ((temporal_clamp || temporal_clamp_radius_set) && !temporal) {
+    std::fprintf(stderr, "--temporal-clamp and --temporal-clamp-radius need --temporal\n");
+    return 2;
+  }
+  if (temporal_clamp_radius_set && !temporal_clamp) {
+    std::fprintf(stderr, "--temporal-clamp-radius needs --temporal-clamp\n");
+    return 2;
+  }
+  if (temporal_clamp && (!(temporal_clamp_gamma >= 0 && temporal_clamp_gamma < 1e30) ||
+                         (temporal_clamp_radius_set && (temporal_clamp_radius < 1 || temporal_clamp_radius > 3)))) {
+    std::fprintf(stderr, "--temporal-clamp needs a finite G >= 0 (0: the default) and --temporal-clamp-radius R in 1..3\n");
     return 2;
   }
   if (temporal && (frames < 2 || pass_spp || pick || focus_at || temporal_history > 4096)) {
@@ -406,7 +431,10 @@ int main(int argc, char** argv) {
       if (temporal) {
         rtw::TemporalRun run;
         run.max_history = temporal_history, run.denoise = denoise, run.dn = dn;
-        rtw::renderOrbitTemporal(cam.to_c(), p, desc, frames, orbit, write_frame, run, rebuild_above, write_guides);
+        rtw_temporal_clamp tc{};
+        tc.gamma = temporal_clamp_gamma, tc.radius = temporal_clamp_radius;
+        rtw::renderOrbitTemporal(cam.to_c(), p, desc, frames, orbit, write_frame, run, rebuild_above, write_guides,
+                                 temporal_clamp ? &tc : nullptr);
       } else {
         rtw::renderOrbit(cam.to_c(), p, desc, frames, orbit, write_frame, rebuild_above, write_guides);
       }

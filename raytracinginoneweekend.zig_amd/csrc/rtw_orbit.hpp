@@ -46,6 +46,8 @@ struct TemporalRun {
 };
 void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames,
                          double deg, const FrameFn& on_frame, const TemporalRun& run, double rebuild_above = -1.0,
-                         const GuideFn& on_guides = GuideFn());
+                         const GuideFn& on_guides = GuideFn(), const rtw_temporal_clamp* clamp = nullptr);
+// clamp (rtw_render --temporal-clamp G): every frame goes through rtw_temporal_clamped_device with it, the
+// history clamped to the frame's neighbourhood; nullptr: rtw_temporal_device as before.
 
 }  // namespace rtw

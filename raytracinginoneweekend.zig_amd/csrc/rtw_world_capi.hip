@@ -951,7 +951,7 @@ void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_des
 // The frames of renderOrbit, each accumulated over the ones before it (rtw_hip.h "temporal accumulation").
 void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p0, const rtw_world_desc& desc, uint32_t frames,
                          double deg, const FrameFn& on_frame, const TemporalRun& run, double rebuild_above,
-                         const GuideFn& on_guides) {
+                         const GuideFn& on_guides, const rtw_temporal_clamp* clamp) {
   const char* who = "renderOrbitTemporal";
   OrbitDev d;
   if (p0.row_begin != 0 || p0.row_stride != 1 || p0.row_count != p0.height)
@@ -1012,8 +1012,13 @@ void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p0, const rtw_
     if (reproject)
       ok(rtw_world_prev_points_device(d.w, d_hits, npix, time, na ? d_a_prev : nullptr, nxv ? d_xv_prev : nullptr, d_pp,
                                       nullptr));
-    ok(rtw_temporal_device(d_mean, d_guides, reproject ? d_pp : nullptr, &cam, &cam, k ? d_hist[(k + 1) & 1] : nullptr, W,
-                           H, &to, d_hist[k & 1], d_acc, d_var, nullptr));
+    if (clamp)
+      ok(rtw_temporal_clamped_device(d_mean, d_guides, reproject ? d_pp : nullptr, &cam, &cam,
+                                     k ? d_hist[(k + 1) & 1] : nullptr, W, H, &to, clamp, d_hist[k & 1], d_acc, d_var,
+                                     nullptr));
+    else
+      ok(rtw_temporal_device(d_mean, d_guides, reproject ? d_pp : nullptr, &cam, &cam, k ? d_hist[(k + 1) & 1] : nullptr, W,
+                             H, &to, d_hist[k & 1], d_acc, d_var, nullptr));
     if (run.denoise) {
       ok(rtw_denoise_device(d_acc, d_var, d_guides, W, H, &dn, d_dn, dnb, d_rgb, nullptr, nullptr));
       if (hipMemcpy(rgb.data(), d_rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)

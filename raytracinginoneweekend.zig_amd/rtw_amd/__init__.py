@@ -120,12 +120,21 @@ class TemporalOpts(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class TemporalClamp(C.Structure):
+    """rtw_temporal_clamp: every field 0 = its default (gamma 0.5, radius 1, reserved 0); 16 bytes."""
+    _fields_ = [("gamma", C.c_double), ("radius", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 HISTORY_DTYPE = np.dtype([("mean", np.float32, 3), ("len", np.float32), ("m1", np.float32), ("m2", np.float32),
                           ("depth", np.float32), ("prim", np.uint32)])
 
 
 def temporal_opts(max_history=0, depth_tol=0.0, min_len_var=0, flags=0) -> TemporalOpts:
     return TemporalOpts(max_history, depth_tol, min_len_var, flags)
+
+
+def temporal_clamp(gamma=0.0, radius=0) -> TemporalClamp:
+    return TemporalClamp(gamma, radius, 0)
 
 
 RAY_DTYPE = np.dtype([("origin", np.float64, 3), ("dir", np.float64, 3), ("time", np.float64),
@@ -287,6 +296,10 @@ def lib() -> C.CDLL:
                                                    C.c_void_p, C.c_void_p, C.c_void_p]
         L.rtw_world_prev_points_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]
+    if hasattr(L, "rtw_temporal_clamped_device"):  # the history clamped to the frame's neighbourhood
+        for f in (L.rtw_temporal_clamped_device, L.rtw_temporal_clamped_host):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(Camera), P(Camera), C.c_void_p, C.c_uint32, C.c_uint32,
+                          P(TemporalOpts), P(TemporalClamp), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "rtw_world_surface_device"):  # surface queries
         for f in (L.rtw_world_surface_device, L.rtw_scene_surface_device):
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -381,6 +394,40 @@ def temporal_host(mean, guides, cam_prev: Camera, cam: Camera, hist_in=None, pre
                                    C.byref(cam_prev), C.byref(cam), hi.ctypes.data if hi is not None else None, W, H,
                                    C.byref(opts) if opts is not None else None, ho.ctypes.data, mo.ctypes.data,
                                    vo.ctypes.data, None))
+    return ho, mo, vo
+
+
+def temporal_clamped_device(mean_ptr: int, guides_ptr: int, prev_p_ptr: int | None, cam_prev: Camera, cam: Camera,
+                            hist_in_ptr: int | None, width: int, height: int, hist_out_ptr: int,
+                            mean_out_ptr: int | None = None, var_out_ptr: int | None = None,
+                            opts: TemporalOpts | None = None, clamp: TemporalClamp | None = None,
+                            stream: int | None = None):
+    """rtw_temporal_clamped_device on device pointers: temporal_device with the history clamped to the window of
+    the current mean around each pixel (clamp None: temporal_device's bytes)."""
+    _check(lib().rtw_temporal_clamped_device(_vp(mean_ptr), _vp(guides_ptr), _vp(prev_p_ptr), C.byref(cam_prev),
+                                             C.byref(cam), _vp(hist_in_ptr), width, height,
+                                             C.byref(opts) if opts is not None else None,
+                                             C.byref(clamp) if clamp is not None else None, _vp(hist_out_ptr),
+                                             _vp(mean_out_ptr), _vp(var_out_ptr), _vp(stream)))
+
+
+def temporal_clamped_host(mean, guides, cam_prev: Camera, cam: Camera, hist_in=None, prev_p=None,
+                          opts: TemporalOpts | None = None, clamp: TemporalClamp | None = None):
+    """rtw_temporal_clamped_host on numpy arrays (no GPU): temporal_host's arguments and results, `clamp` after
+    `opts` (None: temporal_host's bytes)."""
+    m = np.ascontiguousarray(mean, np.float32)
+    g = np.ascontiguousarray(guides, GUIDE_DTYPE)
+    H, W = g.shape
+    hi = np.ascontiguousarray(hist_in, HISTORY_DTYPE) if hist_in is not None else None
+    pp = np.ascontiguousarray(prev_p, np.float64) if prev_p is not None else None
+    if m.shape != (H, W, 3) or (hi is not None and hi.shape != (H, W)) or (pp is not None and pp.shape != (H, W, 3)):
+        raise ValueError("mean (H, W, 3), guides (H, W), hist_in (H, W), prev_p (H, W, 3)")
+    ho, mo, vo = np.zeros((H, W), HISTORY_DTYPE), np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.float32)
+    _check(lib().rtw_temporal_clamped_host(m.ctypes.data, g.ctypes.data, pp.ctypes.data if pp is not None else None,
+                                           C.byref(cam_prev), C.byref(cam), hi.ctypes.data if hi is not None else None,
+                                           W, H, C.byref(opts) if opts is not None else None,
+                                           C.byref(clamp) if clamp is not None else None, ho.ctypes.data,
+                                           mo.ctypes.data, vo.ctypes.data, None))
     return ho, mo, vo
 
 

@@ -6,8 +6,8 @@ from __future__ import annotations
 
 import torch
 
-from . import (Accumulator, Camera, DeviceScene, Params, QueryOpts, TemporalOpts, Timer, pixel_rays_device,
-               temporal_device, workspace_bytes)
+from . import (Accumulator, Camera, DeviceScene, Params, QueryOpts, TemporalClamp, TemporalOpts, Timer,
+               pixel_rays_device, temporal_clamped_device, temporal_device, workspace_bytes)
 
 
 class TorchRenderer:
@@ -320,16 +320,19 @@ class TemporalAccumulator:
 
         ta = TemporalAccumulator(W, H)
         mean_out, var_out = ta.step(mean, guides, cam, prev_p)   # feed both to the denoiser
+
+    clamp (rtw_amd.temporal_clamp(...)): each step clamps the history to the frame's neighbourhood
+    (rtw_temporal_clamped_device); None: rtw_temporal_device as before.
     """
 
     def __init__(self, width: int, height: int, opts: TemporalOpts | None = None,
-                 device: int | torch.device | None = None):
+                 device: int | torch.device | None = None, clamp: TemporalClamp | None = None):
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the rtw temporal path has no CPU fallback")
         if device is None:
             device = torch.cuda.current_device()
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        self.width, self.height, self.opts = int(width), int(height), opts
+        self.width, self.height, self.opts, self.clamp = int(width), int(height), opts, clamp
         self.hist = [torch.zeros((self.height, self.width, 32), dtype=torch.uint8, device=self.device) for _ in range(2)]
         self.reset()
 
@@ -356,11 +359,15 @@ class TemporalAccumulator:
         mean_out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
         var_out = torch.empty((H, W), dtype=torch.float32, device=self.device)
         cam_now = Camera.from_buffer_copy(cam)
+        args = (mean.data_ptr(), guides.data_ptr(), prev_p.data_ptr() if prev_p is not None else None,
+                self.cam_prev if self.frames else cam_now, cam_now, src.data_ptr() if self.frames else None,
+                W, H, dst.data_ptr(), mean_out.data_ptr(), var_out.data_ptr(), self.opts)
         with torch.cuda.device(self.device):
-            temporal_device(mean.data_ptr(), guides.data_ptr(), prev_p.data_ptr() if prev_p is not None else None,
-                            self.cam_prev if self.frames else cam_now, cam_now, src.data_ptr() if self.frames else None,
-                            W, H, dst.data_ptr(), mean_out.data_ptr(), var_out.data_ptr(), self.opts,
-                            torch.cuda.current_stream(self.device).cuda_stream)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            if self.clamp is None:
+                temporal_device(*args, stream)
+            else:
+                temporal_clamped_device(*args, self.clamp, stream)
         self.frames += 1
         self.cam_prev = cam_now
         return mean_out, var_out

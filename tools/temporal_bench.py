@@ -6,6 +6,7 @@ the globe + 10k spheres (scene 7, the real map).
   python tools/temporal_bench.py --mode time    [--repeats 7] [--out FILE]
   python tools/temporal_bench.py --mode quality [--frames 16] [--spp 20] [--ref-spp 500] [--width W] [--out FILE]
                                                 [--degrees 1,5,0] [--max-history M]
+  either mode: [--clamp-gamma G[,G...]] [--clamp-radius R[,R...]]   
 
 time: at the scene's own size (1200x675), HIP events around each call, the calls
 alternating in one process after a warm-up round, median (min .. max), each
@@ -20,7 +21,17 @@ same positions, for the input, the spatial denoiser alone, temporal alone and
 temporal + denoise; the mean history length and the share of pixels without
 history per frame; the averaged frames' error split by what the pixel's feature
 ray hits first (the sky, the ground, a diffuse, metal or glass primitive); and
-the static case (0 degrees) frame by frame."""
+the static case (0 degrees) frame by frame.
+--clamp-gamma / --clamp-radius add the clamped call (rtw_temporal_clamped_device,
+DESIGN.md §20) for every (gamma, radius) of the two lists (radius alone: the
+default gamma, 0; gamma alone: radius 1).  time: one row per radius, static and
+motion, in the same alternating rounds as rtw_temporal_device, each beside its
+own floor (the unclamped floor with the 12 B/pixel of the mean read (4 + 2r) / 4
+times, the tile's halo rows).  quality: every setting accumulates the same
+renders beside the unclamped call in one pass, so all of them share their
+inputs and references; the unclamped tables come first, unchanged, then each
+setting's summary line and by-class split (with --max-history: the sweep with
+the clamp on)."""
 import argparse
 import os
 import statistics
@@ -43,6 +54,8 @@ def main():
     ap.add_argument("--scenes", default="1,7")
     ap.add_argument("--degrees", default="1,5,0", help="quality: degrees per frame, one turntable each (0: the static case)")
     ap.add_argument("--max-history", type=int, default=0, help="quality: rtw_temporal_opts.max_history (0 = the default)")
+    ap.add_argument("--clamp-gamma", default="", help="rtw_temporal_clamp.gamma, a list (0 = the default)")
+    ap.add_argument("--clamp-radius", default="", help="rtw_temporal_clamp.radius, a list (1..3)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -55,6 +68,10 @@ def main():
         raise SystemExit("temporal_bench needs a GPU (there is no CPU path)")
     dev = "cuda:0"
     lines = []
+    gammas = [float(x) for x in args.clamp_gamma.split(",") if x]
+    radii = [int(x) for x in args.clamp_radius.split(",") if x]
+    if gammas or radii:
+        gammas, radii = gammas or [0.0], radii or [1]
 
     def say(s=""):
         print(s, flush=True)
@@ -178,6 +195,10 @@ def main():
             def temporal(src, dst, pp):
                 R.temporal_device(sc.mean.data_ptr(), sc.guides.data_ptr(), pp, sc.cam, sc.cam, src, W, H, dst, acc.data_ptr(),
                                   var.data_ptr(), None, stream())
+
+            def clamped(src, dst, pp, r):
+                R.temporal_clamped_device(sc.mean.data_ptr(), sc.guides.data_ptr(), pp, sc.cam, sc.cam, src, W, H, dst,
+                                          acc.data_ptr(), var.data_ptr(), None, R.temporal_clamp(gammas[0], r), stream())
             sc.render(p)
             sc.pixel_rays(), sc.trace(), sc.make_guides(p), sc.prev_points(a_prev, xv_prev)
             temporal(None, hist[0].data_ptr(), None)  # a first frame: every record holds history from here on
@@ -201,6 +222,12 @@ def main():
             }
             floors = {"rtw_pixel_rays_device": 72, "rtw_world_prev_points_device": 80 + 24, "rtw_world_surface_device (guides)": 80 + 32,
                       "rtw_temporal_device, static": 12 + 32 + 32 + 48, "rtw_temporal_device, motion": 12 + 32 + 24 + 4 * 32 + 48}
+            for r in radii:  # the clamped call beside the unclamped one, in the same rounds
+                steps[f"clamped r={r}, static"] = lambda r=r: clamped(hist[0].data_ptr(), hist[1].data_ptr(), None, r)
+                steps[f"clamped r={r}, motion"] = lambda r=r: clamped(hist[0].data_ptr(), hist[1].data_ptr(), sc.pp.data_ptr(), r)
+                halo = 12 * (4 + 2 * r) // 4 - 12
+                floors[f"clamped r={r}, static"] = floors["rtw_temporal_device, static"] + halo
+                floors[f"clamped r={r}, motion"] = floors["rtw_temporal_device, motion"] + halo
             t = {k: [] for k in steps}
             trace_ms = []
             est = timed(lambda: sc.render(p))
@@ -227,6 +254,10 @@ def main():
                 fl = f"   floor {floors[k] * n / COPY_RATE * 1e3:.4f} ms ({floors[k]} B/pixel at 6.29 TB/s): x{statistics.median(v) / (floors[k] * n / COPY_RATE * 1e3):.1f}" if k in floors else ""
                 say(f"  {k:32s} {fmt(v)}{fl}")
             say(f"  {'  of which the trace kernel':32s} {fmt(trace_ms)}")
+            for r in radii:
+                for what in ("static", "motion"):
+                    c, u = statistics.median(t[f"clamped r={r}, {what}"]), statistics.median(t[f"rtw_temporal_device, {what}"])
+                    say(f"  rtw_temporal_clamped_device r={r} (gamma {gammas[0]:g}), {what}: {c:.4f} ms = x{c / u:.2f} of rtw_temporal_device's {u:.4f} ms")
             med = {k: statistics.median(v) for k, v in t.items()}
             extra = sum(med[k] for k in ("rtw_pixel_rays_device", "rtw_world_trace_device", "rtw_world_guides_device",
                                          "rtw_world_prev_points_device", "rtw_temporal_device, motion"))
@@ -256,12 +287,14 @@ def main():
             W, H = sc.W, sc.H
             say(f"# scene {sid}: {W}x{H}, {args.spp} spp per frame (seed 42 + k), reference {args.ref_spp} spp (seed 1000 + k), "
                 f"RMSE of the linear mean over all pixels and channels; max_history {args.max_history or 32}, depth_tol 0.02, min_len_var 4")
+            variants = [("unclamped", None)] + [(f"clamp gamma {g:g} radius {r}", R.temporal_clamp(g, r)) for r in radii for g in gammas]
             for deg in [float(x) for x in args.degrees.split(",")]:
                 frames = args.frames if deg else 2 * args.frames
-                ta = TemporalAccumulator(W, H, R.temporal_opts(max_history=args.max_history), device=0)
+                tas = [TemporalAccumulator(W, H, R.temporal_opts(max_history=args.max_history), device=0, clamp=c) for _, c in variants]
                 prev = None
-                rows = []
-                by_class = np.zeros((len(CLASSES), 4))  # pixels, squared error of the input, of temporal, sum of len
+                rows = [[] for _ in variants]
+                # per variant and class: pixels, squared error of the input, of temporal, sum of len
+                by_class = np.zeros((len(variants), len(CLASSES), 4))
                 ref0 = None
                 for k in range(frames):
                     a, xv = sc.numbers(k * deg)
@@ -281,41 +314,46 @@ def main():
                     if k and deg:
                         sc.prev_points(*prev)
                         pp = sc.pp
-                    acc, var = ta.step(cur, sc.guides, sc.cam, pp)
                     spatial = sc.denoise(cur, None)
-                    both = sc.denoise(acc, var)
-                    torch.cuda.synchronize()
-                    if k >= frames // 2:  # the frames the summary line averages, split by what the pixel shows
-                        cls = sc.cls[sc.guides.view(torch.int32)[..., 7].long()]
-                        for c in range(len(CLASSES)):
-                            m = cls == c
-                            by_class[c] += np.array([float(m.sum()), float(((cur.double() - ref.double()) ** 2)[m].sum()),
-                                                     float(((acc.double() - ref.double()) ** 2)[m].sum()),
-                                                     float(ta.history().view(torch.float32)[..., 3][m].sum())])
-                    hist = ta.history().cpu().numpy().reshape(-1).view(R.HISTORY_DTYPE)
-                    rows.append((k, rmse(cur, ref), rmse(spatial, ref), rmse(acc, ref), rmse(both, ref), float(hist["len"].mean()),
-                                 float((hist["len"] == 1).mean()), float((var.cpu().numpy() < 0).mean())))
+                    cls = sc.cls[sc.guides.view(torch.int32)[..., 7].long()]
+                    for v, ta in enumerate(tas):  # every variant accumulates the same renders
+                        acc, var = ta.step(cur, sc.guides, sc.cam, pp)
+                        both = sc.denoise(acc, var)
+                        torch.cuda.synchronize()
+                        if k >= frames // 2:  # the frames the summary line averages, split by what the pixel shows
+                            for c in range(len(CLASSES)):
+                                m = cls == c
+                                by_class[v, c] += np.array([float(m.sum()), float(((cur.double() - ref.double()) ** 2)[m].sum()),
+                                                            float(((acc.double() - ref.double()) ** 2)[m].sum()),
+                                                            float(ta.history().view(torch.float32)[..., 3][m].sum())])
+                        hist = ta.history().cpu().numpy().reshape(-1).view(R.HISTORY_DTYPE)
+                        rows[v].append((k, rmse(cur, ref), rmse(spatial, ref), rmse(acc, ref), rmse(both, ref), float(hist["len"].mean()),
+                                        float((hist["len"] == 1).mean()), float((var.cpu().numpy() < 0).mean())))
                     prev = (a, xv)
                 say(f"## {deg:g} degrees per frame, {frames} frames")
-                say("  frame   input   denoise+spatial   temporal   temporal+denoise   mean len   no history   var unknown")
-                for r in rows:
-                    say(f"  {r[0]:5d}  {r[1]:.5f}       {r[2]:.5f}       {r[3]:.5f}       {r[4]:.5f}       {r[5]:7.3f}    {r[6] * 100:6.2f} %    {r[7] * 100:6.2f} %")
-                tail = rows[len(rows) // 2:]
-                m = [statistics.mean(r[i] for r in tail) for i in range(1, 5)]
-                say(f"  mean over the last {len(tail)} frames: input {m[0]:.5f}  denoise+spatial {m[1]:.5f} ({m[1] / m[0]:.3f}x)  "
-                    f"temporal {m[2]:.5f} ({m[2] / m[0]:.3f}x)  temporal+denoise {m[3]:.5f} ({m[3] / m[0]:.3f}x)")
-                say("  the same frames by what the pixel's feature ray hits first (RMSE over the class's pixels; share of the temporal "
-                    "image's squared error):")
-                for c, name in enumerate(CLASSES):
-                    n, se_in, se_t, ln = by_class[c]
-                    if n:
-                        say(f"    {name:22s} {n / by_class[:, 0].sum() * 100:6.2f} % of the pixels   input {np.sqrt(se_in / n / 3):.5f}   "
-                            f"temporal {np.sqrt(se_t / n / 3):.5f} ({np.sqrt(se_t / se_in):.3f}x)   {se_t / by_class[:, 2].sum() * 100:6.2f} % "
-                            f"of the error   mean len {ln / n:6.2f}")
-                if not deg:
-                    for frac in (0.5, 0.25):
-                        hit = next((r[0] + 1 for r in rows if r[3] <= frac * rows[0][1]), None)
-                        say(f"  static: temporal alone reaches {frac:g} x the input's RMSE after {hit} frames (1 / sqrt(n) says {round(1 / frac ** 2)})")
+                for v, (label, _) in enumerate(variants):
+                    if v == 0:
+                        say("  frame   input   denoise+spatial   temporal   temporal+denoise   mean len   no history   var unknown")
+                        for r in rows[0]:
+                            say(f"  {r[0]:5d}  {r[1]:.5f}       {r[2]:.5f}       {r[3]:.5f}       {r[4]:.5f}       {r[5]:7.3f}    {r[6] * 100:6.2f} %    {r[7] * 100:6.2f} %")
+                    else:
+                        say(f"### {label} ({deg:g} degrees per frame)")
+                    tail = rows[v][len(rows[v]) // 2:]
+                    m = [statistics.mean(r[i] for r in tail) for i in range(1, 5)]
+                    say(f"  mean over the last {len(tail)} frames: input {m[0]:.5f}  denoise+spatial {m[1]:.5f} ({m[1] / m[0]:.3f}x)  "
+                        f"temporal {m[2]:.5f} ({m[2] / m[0]:.3f}x)  temporal+denoise {m[3]:.5f} ({m[3] / m[0]:.3f}x)")
+                    say("  the same frames by what the pixel's feature ray hits first (RMSE over the class's pixels; share of the temporal "
+                        "image's squared error):")
+                    for c, name in enumerate(CLASSES):
+                        n, se_in, se_t, ln = by_class[v, c]
+                        if n:
+                            say(f"    {name:22s} {n / by_class[v, :, 0].sum() * 100:6.2f} % of the pixels   input {np.sqrt(se_in / n / 3):.5f}   "
+                                f"temporal {np.sqrt(se_t / n / 3):.5f} ({np.sqrt(se_t / se_in):.3f}x)   {se_t / by_class[v, :, 2].sum() * 100:6.2f} % "
+                                f"of the error   mean len {ln / n:6.2f}")
+                    if not deg:
+                        for frac in (0.5, 0.25):
+                            hit = next((r[0] + 1 for r in rows[v] if r[3] <= frac * rows[v][0][1]), None)
+                            say(f"  static: temporal alone reaches {frac:g} x the input's RMSE after {hit} frames (1 / sqrt(n) says {round(1 / frac ** 2)})")
             sc.close()
 
     (mode_time if args.mode == "time" else mode_quality)()
