@@ -1086,6 +1086,71 @@ int rtw_world_prev_points_device(rtw_world w, const rtw_hit *d_hits, uint64_t n,
 int rtw_world_prev_points_host(const rtw_world_desc *desc, const rtw_hit *hits, uint64_t n, double time,
                                const double *a_prev, const double *xv_prev, double *prev_p);
 
+/* ---- mirror points ----
+ * rtw_world_prev_points_device gives a mirror's own surface point, which stays
+ * put (or moves with the mirror) while what the mirror reflects slides across
+ * it.  These entries answer instead, for a record that counts as a mirror, WHICH
+ * POINT OF THE MIRROR showed the same reflected thing in the previous frame: a
+ * point M' on the mirror, with the mirror's own prim and its real depth under
+ * cam_prev, so rtw_temporal_device and rtw_temporal_clamped_device take the
+ * result as their d_prev_p and nothing else changes.
+ *
+ * A record counts as a mirror iff its prim is of the world's list, front == 1 and
+ * the primitive's material is RTW_WMAT_METAL (any fuzz).  Its reflected ray has
+ * origin p, direction d - 2 dot(d, n) n (the ray's unnormalised d, the record's
+ * normal), the ray's time, t_min 0.001, t_max +inf.  With Mg = the record's
+ * previous point (rtw_world_prev_points_*, at the ray's time), ng = its normal
+ * under the previous numbers, O' = cam_prev's origin and the target S' = the
+ * previous point of the reflected ray's hit (or, if it missed, the reflected unit
+ * direction: the sky does not move):
+ *   rect:   M' is where the line from O' to the target's mirror image across the
+ *           plane (Mg, ng) meets that plane (exact);
+ *   sphere: a thin-lens predictor (curvature (1 / cos + cos) / r') picks a start,
+ *           then `steps` guarded Newton steps minimise |M - O'| + |M - S'| over the
+ *           sphere of the previous numbers; a step is taken only if it is finite,
+ *           the Hessian's determinant is > 0, the new normal faces the camera and
+ *           the target, and the tangential residual shrank.
+ * The result is Mg's bytes (rtw_world_prev_points_*'s) whenever the camera is not
+ * in front of the tangent plane, an input or the result is not finite, the radius
+ * is not > 0, the predictor's denominator is not > 0, a rect's target is not in
+ * front of its plane or the plane's denominator is 0.  The exact expressions:
+ * csrc/rtw_specular.hpp.  One specular bounce: a mirror seen in a mirror is
+ * followed to the second mirror's surface; no occlusion test between M' and S'.
+ *
+ * Non-mirror records and misses get rtw_world_prev_points_device's bytes with
+ * the record's ray's time.  Both previous arrays NULL: "the world stood still,
+ * the camera may not have" — non-mirror records get p, M' is computed against
+ * the current numbers.
+ *
+ * Device form: one launch on `stream`, no workspace, no readback, no atomics,
+ * graph-capturable; equal inputs give equal bytes.  The reflected rays are walked
+ * by the ray queries' own walks, chosen as rtw_world_trace_device chooses them
+ * for this world (linear loop, union walk, per-lane walk with lane regeneration).
+ * d_hits2 (optional, n x rtw_hit): the reflected ray's hit record, 80 zero bytes
+ * for a non-mirror record or a reflected miss.  RTW_EINVAL for a NULL world,
+ * cam_prev, d_rays, d_hits or d_prev_p, a world of another device, buffers not
+ * 8-byte aligned, n > 2^31, steps > 8, unknown flags, an output that overlaps an
+ * input or the other output (byte ranges).  n == 0 launches nothing.
+ *
+ * Host forms (the library has no host tracer): rtw_world_mirror_rays_host gives
+ * the reflected rays and a byte per record (non-mirror records: 72 zero bytes);
+ * the caller traces them (rtw_world_trace) and rtw_world_mirror_points_host takes
+ * their hit records as hits2.  The device's bytes are this pipeline's. */
+#define RTW_MIRROR_PREDICT_ONLY 1u /* flags bit 0: the predictor alone, no Newton step */
+typedef struct {     /* every field 0 = its default */
+  uint32_t steps;    /* Newton steps: 0 = 2; 1..8 */
+  uint32_t flags;    /* RTW_MIRROR_PREDICT_ONLY */
+} rtw_mirror_opts;   /* 8 bytes */
+int rtw_world_mirror_points_device(rtw_world w, const rtw_ray *d_rays, const rtw_hit *d_hits, uint64_t n,
+                                   const rtw_camera *cam_prev, const double *d_a_prev, const double *d_xv_prev,
+                                   const rtw_mirror_opts *opts, double *d_prev_p, rtw_hit *d_hits2, void *stream);
+int rtw_world_mirror_rays_host(const rtw_world_desc *desc, const rtw_ray *rays, const rtw_hit *hits, uint64_t n,
+                               rtw_ray *rays2, uint8_t *is_mirror);
+int rtw_world_mirror_points_host(const rtw_world_desc *desc, const rtw_ray *rays, const rtw_hit *hits,
+                                 const rtw_hit *hits2, uint64_t n, const rtw_camera *cam_prev,
+                                 const double *a_prev, const double *xv_prev, const rtw_mirror_opts *opts,
+                                 double *prev_p);
+
 #ifdef __cplusplus
 }
 #endif

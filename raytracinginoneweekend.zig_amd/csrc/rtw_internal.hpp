@@ -399,4 +399,21 @@ hipError_t launch_scene_query(const SceneQueryArgs& a, uint32_t grid, bool occlu
 size_t query_lds_bytes(int fs);
 int query_blocks_per_cu(int fs, bool occlusion);
 
+// ---------------------------------------------------------- mirror points --
+// rtw_specular.hip (rtw_hip.h "mirror points"): the previous
+// point of n hit records, a mirror record's through the walk of its reflected
+// ray.  q.rays: the rays the records came from; q.out: n x rtw_hit for the
+// reflected rays' records, or null.  fs and the grid: the query kernels' rules.
+struct WorldMirrorArgs {
+  WorldQueryArgs q;
+  const double* hits;     // n x rtw_hit
+  const double* a_prev;   // n_prims x 9, list order, or null
+  const double* xv_prev;  // n_xforms x kMaxXfOps x 3, or null
+  double* prev_p;         // n x 3
+  double cam_o[3];        // the previous camera's origin
+  uint32_t steps;         // Newton steps (0: the predictor alone)
+};
+hipError_t launch_world_mirror(const WorldMirrorArgs& a, uint32_t grid, int fs, hipStream_t s);
+int mirror_blocks_per_cu(int fs);
+
 }  // namespace rtwk

@@ -11,7 +11,8 @@
 //              [--pick X,Y] [--focus-at X,Y]
 //              [--frames N [--orbit DEG] [--rebuild-above R]
 //                          [--temporal [--temporal-history M] [--denoise ...]
-//                                      [--temporal-clamp G [--temporal-clamp-radius R]]]]
+//                                      [--temporal-clamp G [--temporal-clamp-radius R]]
+//                                      [--temporal-mirror [--temporal-mirror-steps K]]]]
 //              [--aov-dir DIR]
 // --aov-dir DIR writes the frame's feature buffers as two more images, DIR/albedo.ppm
 // and DIR/normal.ppm (with --frames one pair per frame, albedo_%04d.ppm and
@@ -65,6 +66,11 @@
 // --temporal-clamp-radius R, 1-3, default 1).  Frame 0 has no history and keeps
 // its bytes.  Without --temporal every run and every refusal is unchanged, and
 // without --temporal-clamp every frame's bytes are.
+// --temporal-mirror reprojects a metal surface from where it showed the same
+// reflected thing in the last frame, not from its own surface point (DESIGN.md
+// §21: rtw_world_mirror_points_device in place of rtw_world_prev_points_device;
+// --temporal-mirror-steps K, 1-8 Newton steps, default 2).  Without the flag
+// every frame's bytes are as before.
 // Defaults are the reference's: scene 6 (main.zig:313) with that scene's own
 // size, spp, camera and background (main.zig:316-362); --width/--aspect/--spp
 // override them.  Scenes 4 and 7 need --image (assets/sekaichizu.png).
@@ -203,12 +209,14 @@ int main(int argc, char** argv) {
   uint32_t denoise_levels = 0, temporal_history = 0, temporal_clamp_radius = 0;
   bool temporal_clamp = false, temporal_clamp_radius_set = false;
   double temporal_clamp_gamma = 0;
+  bool temporal_mirror = false, temporal_mirror_steps_set = false;
+  uint32_t temporal_mirror_steps = 0;
   bool pick = false, focus_at = false;
   uint32_t pick_xy[2] = {0, 0}, focus_xy[2] = {0, 0};
   for (int i = 1; i < argc; i += 2) {
     const std::string k = argv[i];
-    if (k == "--denoise" || k == "--denoise-spatial" || k == "--temporal") {  // (the options without a value)
-      (k == "--denoise" ? denoise : k == "--temporal" ? temporal : denoise_spatial) = true;
+    if (k == "--denoise" || k == "--denoise-spatial" || k == "--temporal" || k == "--temporal-mirror") {  // (the options without a value)
+      (k == "--denoise" ? denoise : k == "--temporal" ? temporal : k == "--temporal-mirror" ? temporal_mirror : denoise_spatial) = true;
       --i;
       continue;
     }
@@ -237,7 +245,9 @@ int main(int argc, char** argv) {
     else if (k == "--rebuild-above") rebuild_above = std::atof(v);
     else if (k == "--temporal-history") temporal_history = (uint32_t)std::strtoul(v, nullptr, 10);
     else if (k == "--temporal-clamp") temporal_clamp = true, temporal_clamp_gamma = std::atof(v);
-    else if (k == "--temporal-clamp-radius") {
+    else if (k == "--temporal-mirror-steps") {
+      temporal_mirror_steps_set = true, temporal_mirror_steps = (uint32_t)std::strtoul(v, nullptr, 10);
+    } else if (k == "--temporal-clamp-radius") {
       temporal_clamp_radius_set = true, temporal_clamp_radius = (uint32_t)std::strtoul(v, nullptr, 10);
     }
     else if (k == "--denoise-levels") denoise_levels = (uint32_t)std::strtoul(v, nullptr, 10);
@@ -268,6 +278,14 @@ int main(int argc, char** argv) {
   }
   if ((temporal_clamp || temporal_clamp_radius_set) && !temporal) {
     std::fprintf(stderr, "--temporal-clamp and --temporal-clamp-radius need --temporal\n");
+    return 2;
+  }
+  if ((temporal_mirror || temporal_mirror_steps_set) && !temporal) {
+    std::fprintf(stderr, "--temporal-mirror and --temporal-mirror-steps need --temporal\n");
+    return 2;
+  }
+  if (temporal_mirror_steps_set && (!temporal_mirror || temporal_mirror_steps < 1 || temporal_mirror_steps > 8)) {
+    std::fprintf(stderr, "--temporal-mirror-steps needs --temporal-mirror and K in 1..8\n");
     return 2;
   }
   if (temporal_clamp_radius_set && !temporal_clamp) {
@@ -433,8 +451,10 @@ int main(int argc, char** argv) {
         run.max_history = temporal_history, run.denoise = denoise, run.dn = dn;
         rtw_temporal_clamp tc{};
         tc.gamma = temporal_clamp_gamma, tc.radius = temporal_clamp_radius;
+        rtw_mirror_opts mo{};
+        mo.steps = temporal_mirror_steps;
         rtw::renderOrbitTemporal(cam.to_c(), p, desc, frames, orbit, write_frame, run, rebuild_above, write_guides,
-                                 temporal_clamp ? &tc : nullptr);
+                                 temporal_clamp ? &tc : nullptr, temporal_mirror ? &mo : nullptr);
       } else {
         rtw::renderOrbit(cam.to_c(), p, desc, frames, orbit, write_frame, rebuild_above, write_guides);
       }

@@ -46,8 +46,12 @@ struct TemporalRun {
 };
 void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p, const rtw_world_desc& desc, uint32_t frames,
                          double deg, const FrameFn& on_frame, const TemporalRun& run, double rebuild_above = -1.0,
-                         const GuideFn& on_guides = GuideFn(), const rtw_temporal_clamp* clamp = nullptr);
+                         const GuideFn& on_guides = GuideFn(), const rtw_temporal_clamp* clamp = nullptr,
+                         const rtw_mirror_opts* mirror = nullptr);
 // clamp (rtw_render --temporal-clamp G): every frame goes through rtw_temporal_clamped_device with it, the
 // history clamped to the frame's neighbourhood; nullptr: rtw_temporal_device as before.
+// mirror (rtw_render --temporal-mirror): the previous points come from rtw_world_mirror_points_device with
+// it, a mirror's from where it showed the same reflected thing; nullptr:
+// rtw_world_prev_points_device as before.
 
 }  // namespace rtw

@@ -21,6 +21,7 @@
 #include "rtw_host.hpp"
 #include "rtw_libm.hpp"
 #include "rtw_orbit.hpp"
+#include "rtw_specular.hpp"
 #include "rtw_world_pack.hpp"
 #include "rtw_world_rebuild.hpp"
 #include "rtw_world_update.hpp"
@@ -35,6 +36,7 @@ struct rtw_world_s {
   uint32_t info[4] = {0, 0, 0, 0};
   bool packed = false;  // the BVH carries the refs in its bounds' low bits (rtw_world_pack.cpp pack_refs)
   size_t table_bytes = 0;  // of buf
+  uint32_t n_xforms = 0;   // transform chains of the description
   // RTW_WORLD_DYNAMIC (rtw_hip.h "dynamic worlds"): the refit's tables, the validation's partials and
   // the host entry's staging arrays in a second allocation; nullptr for a frozen world
   rtwp::RefitPack* refit = nullptr;
@@ -139,6 +141,7 @@ int rtw_world_create(const rtw_world_desc* d, uint32_t flags, rtw_world* out) {
   std::memcpy(w->info, k.info, sizeof(w->info));
   w->packed = k.packed;
   w->table_bytes = total;
+  w->n_xforms = d->n_xforms;
   if (flags & RTW_WORLD_DYNAMIC) {
     const int sd = make_dynamic(w, d, k);
     if (sd != RTW_OK) {
@@ -723,6 +726,26 @@ int query_bpc(int fs, bool occlusion) {  // resident workgroups per CU, asked on
   return e;
 }
 
+int mirror_bpc(int fs) {  // the mirror-point kernels' (rtw_specular.hip)
+  static std::mutex mu;
+  static int cache[64] = {};
+  std::lock_guard<std::mutex> lk(mu);
+  int& e = cache[fs & 63];
+  if (e == 0) e = rtwk::mirror_blocks_per_cu(fs);
+  return e;
+}
+
+// What a query kernel reads of the world (a: zeroed).
+void query_args(const rtw_world_s* w, rtwk::WorldQueryArgs& a) {
+  a.w = w->view;
+  a.lane_yield = kLaneYield;
+  a.seq_times = (w->has_moving && w->view.n_nodes) ? 1u : 0u;
+  for (int k = 0; k < 3; ++k) {
+    if (std::isfinite(w->bounds_lo[k])) a.reach = std::max(a.reach, std::fabs(w->bounds_lo[k]));
+    if (std::isfinite(w->bounds_hi[k])) a.reach = std::max(a.reach, std::fabs(w->bounds_hi[k]));
+  }
+}
+
 int world_query(const char* who, rtw_world w, const rtw_ray* d_rays, uint64_t n, const rtw_query_opts* opts,
                 void* d_out, bool occlusion, hipStream_t stream) {
   std::string msg;
@@ -735,16 +758,10 @@ int world_query(const char* who, rtw_world w, const rtw_ray* d_rays, uint64_t n,
   const QueryCfg c = query_cfg(w, opts);
   rtwk::WorldQueryArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.w = w->view;
+  query_args(w, a);
   a.rays = reinterpret_cast<const double*>(d_rays);
   a.out = d_out;
   a.n = (uint32_t)n;
-  a.lane_yield = kLaneYield;
-  a.seq_times = (w->has_moving && w->view.n_nodes) ? 1u : 0u;
-  for (int k = 0; k < 3; ++k) {
-    if (std::isfinite(w->bounds_lo[k])) a.reach = std::max(a.reach, std::fabs(w->bounds_lo[k]));
-    if (std::isfinite(w->bounds_hi[k])) a.reach = std::max(a.reach, std::fabs(w->bounds_hi[k]));
-  }
   const uint32_t grid = rtwq::grid(n, (uint32_t)rtw_device_cus(dev), (uint32_t)query_bpc(c.fs, occlusion));
   const hipError_t e = rtwk::launch_world_query(a, grid, c.fs, occlusion, stream);
   if (e != hipSuccess) return rtw_fail(RTW_EHIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
@@ -790,6 +807,44 @@ int rtw_world_query_info(rtw_world w, const rtw_query_opts* opts, uint32_t info_
   info_out[1] = (uint32_t)c.fs;
   info_out[2] = rtwq::grid(RTW_QUERY_MAX_RAYS, (uint32_t)rtw_device_cus(dev), (uint32_t)query_bpc(c.fs, false));
   info_out[3] = (uint32_t)rtwk::query_lds_bytes(c.fs);
+  return RTW_OK;
+}
+
+// (rtw_hip.h "mirror points"; kernels: rtw_specular.hip; the shared checks: rtw_specular_host.cpp)
+int rtw_world_mirror_points_device(rtw_world w, const rtw_ray* d_rays, const rtw_hit* d_hits, uint64_t n,
+                                   const rtw_camera* cam_prev, const double* d_a_prev, const double* d_xv_prev,
+                                   const rtw_mirror_opts* opts, double* d_prev_p, rtw_hit* d_hits2, void* stream) {
+  const char* who = "rtw_world_mirror_points_device";
+  if (!w) return rtw_fail(RTW_EINVAL, "%s: world is NULL", who);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
+  if (dev != w->device) return rtw_fail(RTW_EINVAL, "%s: world lives on device %d, current is %d", who, w->device, dev);
+  if (n > RTW_QUERY_MAX_RAYS) return rtw_fail(RTW_EINVAL, "%s: n > 2^31", who);
+  const rtw_mirror_opts dflt{};
+  if (!opts) opts = &dflt;
+  rtwk::WorldMirrorArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (n == 0) {
+    if (!cam_prev || !rtwsp::resolve(opts->steps, opts->flags, a.steps))
+      return rtw_fail(RTW_EINVAL, "%s: cam_prev is NULL or options out of range", who);
+    return RTW_OK;
+  }
+  const int st = rtwsp::check_call(who, d_rays, d_hits, nullptr, n, cam_prev, d_a_prev, (size_t)72 * w->view.n_prims,
+                                   d_xv_prev, (size_t)24 * RTW_MAX_XFORM_OPS * w->n_xforms, opts->steps, opts->flags,
+                                   d_prev_p, d_hits2, a.steps);
+  if (st != RTW_OK) return st;
+  const QueryCfg c = query_cfg(w, nullptr);
+  query_args(w, a.q);
+  a.q.rays = reinterpret_cast<const double*>(d_rays);
+  a.q.out = d_hits2;
+  a.q.n = (uint32_t)n;
+  a.hits = reinterpret_cast<const double*>(d_hits);
+  a.a_prev = d_a_prev, a.xv_prev = d_xv_prev;
+  a.prev_p = d_prev_p;
+  for (int k = 0; k < 3; ++k) a.cam_o[k] = cam_prev->origin[k];
+  const uint32_t grid = rtwq::grid(n, (uint32_t)rtw_device_cus(dev), (uint32_t)mirror_bpc(c.fs));
+  const hipError_t e = rtwk::launch_world_mirror(a, grid, c.fs, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return rtw_fail(RTW_EHIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
   return RTW_OK;
 }
 
@@ -951,7 +1006,7 @@ void renderOrbit(const rtw_camera& cam, const rtw_params& p, const rtw_world_des
 // The frames of renderOrbit, each accumulated over the ones before it (rtw_hip.h "temporal accumulation").
 void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p0, const rtw_world_desc& desc, uint32_t frames,
                          double deg, const FrameFn& on_frame, const TemporalRun& run, double rebuild_above,
-                         const GuideFn& on_guides, const rtw_temporal_clamp* clamp) {
+                         const GuideFn& on_guides, const rtw_temporal_clamp* clamp, const rtw_mirror_opts* mirror) {
   const char* who = "renderOrbitTemporal";
   OrbitDev d;
   if (p0.row_begin != 0 || p0.row_stride != 1 || p0.row_count != p0.height)
@@ -1009,7 +1064,10 @@ void renderOrbitTemporal(const rtw_camera& cam, const rtw_params& p0, const rtw_
     // the frame's guides from the hits it already has: rtw_world_guides_device's bytes
     ok(rtw_world_surface_device(d.w, d_hits, npix, p.background, nullptr, d_guides, nullptr));
     const bool reproject = k && moves;
-    if (reproject)
+    if (reproject && mirror)  // (the feature rays all carry `time`)
+      ok(rtw_world_mirror_points_device(d.w, d_rays, d_hits, npix, &cam, na ? d_a_prev : nullptr,
+                                        nxv ? d_xv_prev : nullptr, mirror, d_pp, nullptr, nullptr));
+    else if (reproject)
       ok(rtw_world_prev_points_device(d.w, d_hits, npix, time, na ? d_a_prev : nullptr, nxv ? d_xv_prev : nullptr, d_pp,
                                       nullptr));
     if (clamp)

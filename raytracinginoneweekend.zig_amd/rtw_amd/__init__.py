@@ -137,6 +137,18 @@ def temporal_clamp(gamma=0.0, radius=0) -> TemporalClamp:
     return TemporalClamp(gamma, radius, 0)
 
 
+class MirrorOpts(C.Structure):
+    """rtw_mirror_opts: every field 0 = its default (2 Newton steps, no flags); 8 bytes."""
+    _fields_ = [("steps", C.c_uint32), ("flags", C.c_uint32)]
+
+
+MIRROR_PREDICT_ONLY = 1  # rtw_hip.h RTW_MIRROR_PREDICT_ONLY
+
+
+def mirror_opts(steps=0, flags=0) -> MirrorOpts:
+    return MirrorOpts(steps, flags)
+
+
 RAY_DTYPE = np.dtype([("origin", np.float64, 3), ("dir", np.float64, 3), ("time", np.float64),
                       ("t_min", np.float64), ("t_max", np.float64)])
 HIT_DTYPE = np.dtype([("t", np.float64), ("p", np.float64, 3), ("normal", np.float64, 3), ("u", np.float64),
@@ -304,6 +316,12 @@ def lib() -> C.CDLL:
         for f in (L.rtw_world_surface_device, L.rtw_scene_surface_device):
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rtw_world_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    if hasattr(L, "rtw_world_mirror_points_device"):  # mirror points
+        L.rtw_world_mirror_points_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(Camera), C.c_void_p,
+                                                     C.c_void_p, P(MirrorOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rtw_world_mirror_rays_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.rtw_world_mirror_points_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(Camera),
+                                                   C.c_void_p, C.c_void_p, P(MirrorOpts), C.c_void_p]
     _lib = L
     return L
 

@@ -278,6 +278,33 @@ class TorchTracer:
         self.target.surface(self._frame_hits.data_ptr(), n, None, g.data_ptr(), background, stream)
         return g
 
+    def mirror_points(self, rays, hits, cam_prev: Camera, a_prev=None, xv_prev=None, opts=None, hits2: bool = False):
+        """The prev_p of TemporalAccumulator.step with the mirrors followed (rtw_hip.h "mirror points"): rays is
+        the (N, 9) float64 ray tensor the hits came from (pack()'s), hits trace()'s dict or its (N, 10) record
+        tensor.  (N, 3) float64: each hit's surface point under the previous numbers (a_prev (n_prims, 9),
+        xv_prev (n_xforms, 4, 3) float64 device tensors; None: the current ones), and for a front hit of a
+        metal primitive the point of the mirror that showed the same reflected thing from cam_prev.  One
+        launch on torch's current stream.  hits2=True: (prev_p, the reflected rays' (N, 10) records)."""
+        if not self.is_world:
+            raise ValueError("mirror_points needs a world.DeviceWorld")
+        rec_in = hits["records"] if isinstance(hits, dict) else hits
+        n = rec_in.shape[0]
+        for name, t, cols in (("rays", rays, 9), ("hits", rec_in, 10)):
+            if t.dtype != torch.float64 or t.dim() != 2 or t.shape != (n, cols) or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"{name} must be a contiguous (N, {cols}) float64 tensor on the world's device")
+        for name, t, shape in (("a_prev", a_prev, (self.target.n_prims, 9)), ("xv_prev", xv_prev, (self.target.n_xforms, 4, 3))):
+            if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError(f"{name} must be a contiguous float64 device tensor of shape {shape}")
+        out = torch.empty((n, 3), dtype=torch.float64, device=self.device)
+        rec2 = torch.empty((n, 10), dtype=torch.float64, device=self.device) if hits2 else None
+        if n:
+            self.target.mirror_points_device(rays.data_ptr(), rec_in.data_ptr(), n, cam_prev, out.data_ptr(),
+                                             a_prev.data_ptr() if a_prev is not None and a_prev.numel() else None,
+                                             xv_prev.data_ptr() if xv_prev is not None and xv_prev.numel() else None, opts,
+                                             rec2.data_ptr() if hits2 else None,
+                                             torch.cuda.current_stream(self.device).cuda_stream)
+        return (out, rec2) if hits2 else out
+
 
 def update_world(dw, a: torch.Tensor, xv: torch.Tensor | None = None):
     """New numbers for a dynamic world.DeviceWorld from torch tensors of its device

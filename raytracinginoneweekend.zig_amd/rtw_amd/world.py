@@ -351,6 +351,41 @@ def prev_points_host(desc: WorldDesc, hits, time: float, a_prev=None, xv_prev=No
     return out
 
 
+def mirror_rays_host(desc: WorldDesc, rays, hits):
+    """rtw_world_mirror_rays_host (no GPU): rays (n,) RAY_DTYPE and their hits (n,) HIT_DTYPE of the world `desc`
+    describes -> (rays2 (n,) RAY_DTYPE, is_mirror (n,) uint8): the reflected ray of every record that counts as a
+    mirror (a front hit of a metal primitive), zero bytes for the others."""
+    r = np.ascontiguousarray(rays, RAY_DTYPE).reshape(-1)
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    if r.size != h.size:
+        raise ValueError("rays and hits must have the same length")
+    r2, m = np.zeros(r.size, RAY_DTYPE), np.zeros(r.size, np.uint8)
+    _check(_wlib().rtw_world_mirror_rays_host(C.byref(desc), r.ctypes.data, h.ctypes.data, r.size, r2.ctypes.data,
+                                              m.ctypes.data))
+    return r2, m
+
+
+def mirror_points_host(desc: WorldDesc, rays, hits, hits2, cam_prev, a_prev=None, xv_prev=None, opts=None) -> np.ndarray:
+    """rtw_world_mirror_points_host (no GPU): prev_points_host's result with each ray's own time, except that a
+    mirror record gets the point of the mirror that showed the same reflected thing from cam_prev under the
+    previous numbers; hits2 (n,) HIT_DTYPE are the hits of mirror_rays_host's rays.  -> (n, 3) float64."""
+    r = np.ascontiguousarray(rays, RAY_DTYPE).reshape(-1)
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    h2 = np.ascontiguousarray(hits2, HIT_DTYPE).reshape(-1)
+    if r.size != h.size or h2.size != h.size:
+        raise ValueError("rays, hits and hits2 must have the same length")
+    a = np.ascontiguousarray(a_prev, np.float64) if a_prev is not None else None
+    xv = np.ascontiguousarray(xv_prev, np.float64) if xv_prev is not None else None
+    if (a is not None and a.shape != (desc.n_prims, 9)) or (xv is not None and xv.shape != (desc.n_xforms, 4, 3)):
+        raise ValueError("a_prev must be (n_prims, 9) and xv_prev (n_xforms, 4, 3)")
+    out = np.zeros((h.size, 3), np.float64)
+    _check(_wlib().rtw_world_mirror_points_host(C.byref(desc), r.ctypes.data, h.ctypes.data, h2.ctypes.data, h.size,
+                                                C.byref(cam_prev), a.ctypes.data if a is not None else None,
+                                                xv.ctypes.data if xv is not None and xv.size else None,
+                                                C.byref(opts) if opts is not None else None, out.ctypes.data))
+    return out
+
+
 TRAVERSAL_NAMES = {1: "union", 2: "lane", 3: "linear"}  # rtw_world_traversal (rtw_hip.h)
 
 
@@ -508,6 +543,23 @@ class DeviceWorld:
                                                     C.c_void_p(out_ptr) if out_ptr else None,
                                                     C.c_void_p(stream) if stream else None))
 
+    def mirror_points_device(self, rays_ptr: int, hits_ptr: int, n: int, cam_prev, out_ptr: int,
+                             a_prev_ptr: int | None = None, xv_prev_ptr: int | None = None, opts=None,
+                             hits2_ptr: int | None = None, stream: int | None = None):
+        """rtw_world_mirror_points_device: prev_points_device with each ray's own time, except that a mirror
+        record (a front hit of a metal primitive) gets the point of the mirror that showed the same reflected
+        thing from cam_prev under the previous numbers; one launch that walks the reflected rays itself.
+        hits2_ptr (optional): n rtw_hit records of the reflected rays.  Asynchronous on `stream`."""
+        _check(_wlib().rtw_world_mirror_points_device(self.h, C.c_void_p(rays_ptr) if rays_ptr else None,
+                                                      C.c_void_p(hits_ptr) if hits_ptr else None, n,
+                                                      C.byref(cam_prev) if cam_prev is not None else None,
+                                                      C.c_void_p(a_prev_ptr) if a_prev_ptr else None,
+                                                      C.c_void_p(xv_prev_ptr) if xv_prev_ptr else None,
+                                                      C.byref(opts) if opts is not None else None,
+                                                      C.c_void_p(out_ptr) if out_ptr else None,
+                                                      C.c_void_p(hits2_ptr) if hits2_ptr else None,
+                                                      C.c_void_p(stream) if stream else None))
+
     def query_info(self, opts: QueryOpts | None = None) -> dict:
         """rtw_world_query_info: the walk a query runs (after AUTO and the world's limits),
         its kernel feature set, the workgroups of a device-filling batch, LDS per workgroup."""
@@ -541,4 +593,4 @@ class DeviceWorld:
             pass
 
 
-__all__ = ["BuiltScene", "DeviceWorld", "refit_tables_host", "rebuild_tables_host", "prev_points_host", "desc_numbers", "render_world", "load_png", "earth_map", "synthetic_world_map", "RtwError", "SCENES"]
+__all__ = ["BuiltScene", "DeviceWorld", "refit_tables_host", "rebuild_tables_host", "prev_points_host", "mirror_rays_host", "mirror_points_host", "desc_numbers", "render_world", "load_png", "earth_map", "synthetic_world_map", "RtwError", "SCENES"]

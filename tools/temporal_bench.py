@@ -7,6 +7,7 @@ the globe + 10k spheres (scene 7, the real map).
   python tools/temporal_bench.py --mode quality [--frames 16] [--spp 20] [--ref-spp 500] [--width W] [--out FILE]
                                                 [--degrees 1,5,0] [--max-history M]
   either mode: [--clamp-gamma G[,G...]] [--clamp-radius R[,R...]]   
+               [--mirror]                                           
 
 time: at the scene's own size (1200x675), HIP events around each call, the calls
 alternating in one process after a warm-up round, median (min .. max), each
@@ -31,7 +32,15 @@ times, the tile's halo rows).  quality: every setting accumulates the same
 renders beside the unclamped call in one pass, so all of them share their
 inputs and references; the unclamped tables come first, unchanged, then each
 setting's summary line and by-class split (with --max-history: the sweep with
-the clamp on)."""
+the clamp on).
+--mirror adds the mirror points (rtw_world_mirror_points_device).
+time: the launch beside rtw_world_prev_points_device and beside what a caller
+would run without it (rtw_world_prev_points_device + rtw_world_trace_device on
+the compacted reflected rays), in the same alternating rounds.  quality: after
+the tables above, unchanged, every setting once more with the mirror points as
+its prev_p and once with the predictor alone, over the same renders; the metal
+class split by the material's fuzz, and the share of the metal pixels whose
+taps were all refused (no history)."""
 import argparse
 import os
 import statistics
@@ -56,6 +65,7 @@ def main():
     ap.add_argument("--max-history", type=int, default=0, help="quality: rtw_temporal_opts.max_history (0 = the default)")
     ap.add_argument("--clamp-gamma", default="", help="rtw_temporal_clamp.gamma, a list (0 = the default)")
     ap.add_argument("--clamp-radius", default="", help="rtw_temporal_clamp.radius, a list (1..3)")
+    ap.add_argument("--mirror", action="store_true", help="add the mirror points (DESIGN.md §21)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -118,6 +128,10 @@ def main():
             big = (self.kinds <= 1) & (self.a0[:, 6] >= 100.0)
             mk = np.array([d.mats[d.prims[i].mat].kind for i in range(d.n_prims)])
             self.cls = torch.from_numpy(np.concatenate([[0], np.where(big, 1, 2 + mk)]).astype(np.int64)).to(dev)
+            # a metal primitive's fuzz bin (index = guide prim): 1: < 0.05, 2: < 0.25, 3: the rest; 0: no metal
+            fz = np.array([d.mats[d.prims[i].mat].fuzz for i in range(d.n_prims)])
+            self.fuzz_bin = torch.from_numpy(np.concatenate([[0], np.where(mk == 1, 1 + (fz >= 0.05) + (fz >= 0.25), 0)])
+                                             .astype(np.int64)).to(dev)
             self.dw = Wd.DeviceWorld(d, dynamic=True)
             self.n = self.W * self.H
             W, H = self.W, self.H
@@ -163,6 +177,11 @@ def main():
         def prev_points(self, a_prev, xv_prev):
             self.dw.prev_points_device(self.hits.data_ptr(), self.n, 0.5, self.pp.data_ptr(), a_prev.data_ptr(),
                                        xv_prev.data_ptr() if xv_prev is not None else None, stream())
+
+        def mirror_points(self, a_prev, xv_prev, out, opts=None):
+            self.dw.mirror_points_device(self.rays.data_ptr(), self.hits.data_ptr(), self.n, self.cam, out.data_ptr(),
+                                         a_prev.data_ptr(), xv_prev.data_ptr() if xv_prev is not None else None, opts, None,
+                                         stream())
 
         def denoise(self, mean, var):
             out = torch.empty_like(mean)
@@ -222,6 +241,23 @@ def main():
             }
             floors = {"rtw_pixel_rays_device": 72, "rtw_world_prev_points_device": 80 + 24, "rtw_world_surface_device (guides)": 80 + 32,
                       "rtw_temporal_device, static": 12 + 32 + 32 + 48, "rtw_temporal_device, motion": 12 + 32 + 24 + 4 * 32 + 48}
+            if args.mirror:  # the fused launch, and what a caller would run without it
+                torch.cuda.synchronize()
+                h_rays = sc.rays.cpu().numpy().reshape(-1).view(R.RAY_DTYPE)
+                h_hits = sc.hits.cpu().numpy().reshape(-1).view(R.HIT_DTYPE)
+                rays2, flag = Wd.mirror_rays_host(sc.b.desc, h_rays, h_hits)
+                n_mirror = int(flag.sum())
+                d_r2 = torch.from_numpy(np.ascontiguousarray(rays2[flag != 0]).view(np.float64).reshape(-1, 9)).to(dev)
+                d_h2 = torch.empty((max(1, n_mirror), 10), dtype=torch.float64, device=dev)
+                pp_m = torch.empty_like(sc.pp)
+
+                def unfused():
+                    sc.prev_points(a_prev, xv_prev)
+                    if n_mirror:
+                        sc.dw.trace(d_r2.data_ptr(), n_mirror, d_h2.data_ptr(), None, stream())
+                steps["rtw_world_mirror_points_device"] = lambda: sc.mirror_points(a_prev, xv_prev, pp_m)
+                steps["prev_points + trace (compacted)"] = unfused
+                floors["rtw_world_mirror_points_device"] = 72 + 80 + 24
             for r in radii:  # the clamped call beside the unclamped one, in the same rounds
                 steps[f"clamped r={r}, static"] = lambda r=r: clamped(hist[0].data_ptr(), hist[1].data_ptr(), None, r)
                 steps[f"clamped r={r}, motion"] = lambda r=r: clamped(hist[0].data_ptr(), hist[1].data_ptr(), sc.pp.data_ptr(), r)
@@ -274,6 +310,14 @@ def main():
                 f"(temporal steps {extra:.3f} -> {new_extra:.3f} ms, + {new_extra / rend * 100:.1f} % of the render); a caller with no hits "
                 f"yet pays pixel rays + trace + surface = "
                 f"{med['rtw_pixel_rays_device'] + med['rtw_world_trace_device'] + g_new:.4f} ms for a frame's guides")
+            if args.mirror:
+                m_new, m_pp, m_un = (med[k] for k in ("rtw_world_mirror_points_device", "rtw_world_prev_points_device",
+                                                       "prev_points + trace (compacted)"))
+                say(f"  mirror points: {n_mirror} of {n} records are mirrors ({n_mirror / n * 100:.2f} %); the launch {m_new:.4f} ms = "
+                    f"x{m_new / m_pp:.1f} of rtw_world_prev_points_device's {m_pp:.4f} ms, x{m_new / m_un:.2f} of prev_points + "
+                    f"rtw_world_trace_device on the {n_mirror} compacted reflected rays ({m_un:.4f} ms; the compaction and "
+                    f"rtw_world_mirror_points_host's arithmetic are not in that figure); per animated frame "
+                    f"{rend + new_extra:.3f} ms -> {rend + new_extra - m_pp + m_new:.3f} ms")
             sc.close()
 
     CLASSES = ("miss (the sky)", "ground (r >= 100)", "diffuse", "metal", "glass", "light")
@@ -288,6 +332,13 @@ def main():
             say(f"# scene {sid}: {W}x{H}, {args.spp} spp per frame (seed 42 + k), reference {args.ref_spp} spp (seed 1000 + k), "
                 f"RMSE of the linear mean over all pixels and channels; max_history {args.max_history or 32}, depth_tol 0.02, min_len_var 4")
             variants = [("unclamped", None)] + [(f"clamp gamma {g:g} radius {r}", R.temporal_clamp(g, r)) for r in radii for g in gammas]
+            source = ["surface"] * len(variants)  # what each variant takes as prev_p
+            if args.mirror:
+                base = list(variants)
+                for how, word in (("mirror", "mirror points"), ("predict", "mirror points, predictor only")):
+                    variants += [(f"{label} + {word}", c) for label, c in base]
+                    source += [how] * len(base)
+            FUZZ = ("metal, fuzz < 0.05", "metal, fuzz < 0.25", "metal, fuzz <= 0.5")
             for deg in [float(x) for x in args.degrees.split(",")]:
                 frames = args.frames if deg else 2 * args.frames
                 tas = [TemporalAccumulator(W, H, R.temporal_opts(max_history=args.max_history), device=0, clamp=c) for _, c in variants]
@@ -295,6 +346,8 @@ def main():
                 rows = [[] for _ in variants]
                 # per variant and class: pixels, squared error of the input, of temporal, sum of len
                 by_class = np.zeros((len(variants), len(CLASSES), 4))
+                by_fuzz = np.zeros((len(variants), 3, 4))  # pixels, squared error of the input, of temporal, pixels without history
+                pps = {"surface": None}
                 ref0 = None
                 for k in range(frames):
                     a, xv = sc.numbers(k * deg)
@@ -314,10 +367,15 @@ def main():
                     if k and deg:
                         sc.prev_points(*prev)
                         pp = sc.pp
+                        if args.mirror:
+                            for how, o in (("mirror", None), ("predict", R.mirror_opts(flags=R.MIRROR_PREDICT_ONLY))):
+                                if pps.get(how) is None:
+                                    pps[how] = torch.empty_like(sc.pp)
+                                sc.mirror_points(*prev, pps[how], o)
                     spatial = sc.denoise(cur, None)
                     cls = sc.cls[sc.guides.view(torch.int32)[..., 7].long()]
                     for v, ta in enumerate(tas):  # every variant accumulates the same renders
-                        acc, var = ta.step(cur, sc.guides, sc.cam, pp)
+                        acc, var = ta.step(cur, sc.guides, sc.cam, pp if pp is None or source[v] == "surface" else pps[source[v]])
                         both = sc.denoise(acc, var)
                         torch.cuda.synchronize()
                         if k >= frames // 2:  # the frames the summary line averages, split by what the pixel shows
@@ -326,6 +384,14 @@ def main():
                                 by_class[v, c] += np.array([float(m.sum()), float(((cur.double() - ref.double()) ** 2)[m].sum()),
                                                             float(((acc.double() - ref.double()) ** 2)[m].sum()),
                                                             float(ta.history().view(torch.float32)[..., 3][m].sum())])
+                            if args.mirror:
+                                fb = sc.fuzz_bin[sc.guides.view(torch.int32)[..., 7].long()]
+                                lens = ta.history().view(torch.float32)[..., 3]
+                                for b in range(3):
+                                    m = fb == b + 1
+                                    by_fuzz[v, b] += np.array([float(m.sum()), float(((cur.double() - ref.double()) ** 2)[m].sum()),
+                                                               float(((acc.double() - ref.double()) ** 2)[m].sum()),
+                                                               float((lens[m] == 1).sum())])
                         hist = ta.history().cpu().numpy().reshape(-1).view(R.HISTORY_DTYPE)
                         rows[v].append((k, rmse(cur, ref), rmse(spatial, ref), rmse(acc, ref), rmse(both, ref), float(hist["len"].mean()),
                                         float((hist["len"] == 1).mean()), float((var.cpu().numpy() < 0).mean())))
@@ -350,6 +416,12 @@ def main():
                             say(f"    {name:22s} {n / by_class[v, :, 0].sum() * 100:6.2f} % of the pixels   input {np.sqrt(se_in / n / 3):.5f}   "
                                 f"temporal {np.sqrt(se_t / n / 3):.5f} ({np.sqrt(se_t / se_in):.3f}x)   {se_t / by_class[v, :, 2].sum() * 100:6.2f} % "
                                 f"of the error   mean len {ln / n:6.2f}")
+                    if args.mirror:
+                        for b, name in enumerate(FUZZ):
+                            n, se_in, se_t, lost = by_fuzz[v, b]
+                            if n:
+                                say(f"    {name:22s} {n / by_class[v, :, 0].sum() * 100:6.2f} % of the pixels   input {np.sqrt(se_in / n / 3):.5f}   "
+                                    f"temporal {np.sqrt(se_t / n / 3):.5f} ({np.sqrt(se_t / se_in):.3f}x)   {lost / n * 100:6.2f} % without history")
                     if not deg:
                         for frac in (0.5, 0.25):
                             hit = next((r[0] + 1 for r in rows[v] if r[3] <= frac * rows[v][0][1]), None)
