@@ -12,6 +12,7 @@
 #include "rtw_cull.hpp"
 #include "rtw_internal.hpp"
 #include "rtw_math.hpp"
+#include "rtw_selfskip.hpp"
 
 namespace rtwk {
 
@@ -807,7 +808,11 @@ struct KStats {
 // PRIMARY (the primary-first loop; f64, clusters on, one 64-slot block): a camera
 // ray — the wide spheres exactly, then the per-lane exact tests of the slots
 // in (pm0, pm1), the mask of the lane's tile, in place of the pretest.
-template <typename R, bool F32, int MODE, bool PRIMARY = false, bool FLAT = false, typename SV>
+// LEAVEPRE (the f64 megakernel of a full frame; rtw_selfskip.hpp): the "both roots behind"
+// prefilter of every exact test is rtws::leaves — cc > -tmin * hb in place of cc > 0 — so that the sphere a
+// secondary ray has just left, whose cc is a rounding error of either sign, ends its test at that compare
+// instead of solving for two roots that are both below tmin.
+template <typename R, bool F32, int MODE, bool PRIMARY = false, bool FLAT = false, bool LEAVEPRE = false, typename SV>
 __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, const Lane<R>& L, R tmin,
                                             R pre_k, uint32_t lid, KStats& st, int& hit, R& tmax, uint32_t pm0 = 0u,
                                             uint32_t pm1 = 0u) {
@@ -815,7 +820,9 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
   constexpr bool STATS = MODE == 1;
   const R a = norm2(L.d);
   const R inv_a = (R)1 / a;          // RN(1/a): roots via div_rn
-  const R pre_lim = pre_k * a;     // "both roots behind" prefilter bound
+  static_assert(!LEAVEPRE || !F32, "rtws::leaves is proven for the f64 test");
+  R pre_lim = pre_k * a;     // "both roots behind" prefilter bound
+  if constexpr (LEAVEPRE) pre_lim = rtws::hb_limit(a, tmin);  // (its own bound on hb: 0 outside the rule's ranges)
   int tg_cur = -1;
   R frac = (R)0;
   const RTW_CONST uint32_t* c_meta = cptr(S.meta);
@@ -851,7 +858,8 @@ __device__ __forceinline__ void closest_hit(const SV& S, const LdsTables<R>& T, 
     // also enters (reference: `disc < 0` is false for NaN).
     if (!(disc < (R)0)) {
       // (bitwise &: no short-circuit branches)
-      const bool pre = (hb > (R)0) & (cc > (R)0) & (hb < pre_lim);
+      bool pre = (hb > (R)0) & (cc > (R)0) & (hb < pre_lim);
+      if constexpr (LEAVEPRE) pre = rtws::leaves_lim(hb, cc, tmin, pre_lim);
       bool cand = !pre;
       if (F32) cand = cand & ((int)k != L.skip);
       if constexpr (STATS) {

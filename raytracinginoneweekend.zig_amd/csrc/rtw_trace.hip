@@ -78,6 +78,14 @@ struct TraceCfg {
   // Bytes per wave after those, in a launch with TraceArgs::tail_on: the tail block of the primary-first loop
   // (profiles/r15/README.md).
   static constexpr size_t kTailBytes = kPrimaryFirst ? kTailLdsBytesPerWave : 0;
+  // The exact tests' "both roots behind" prefilter is rtw_selfskip.hpp's rule (closest_hit LEAVEPRE): the sphere a
+  // secondary ray has just left ends its test there.  f64 frames: -1.26 % per configs[1] frame
+  // (profiles/r25/README.md).  -DRTW_NO_SELFSKIP: the parent's prefilter, the measurement build of that A/B.
+#ifdef RTW_NO_SELFSKIP
+  static constexpr bool kLeavePre = false;
+#else
+  static constexpr bool kLeavePre = !F32 && !MASKED;
+#endif
 };
 
 template <typename R, bool F32, int MODE, bool MASKED>
@@ -398,8 +406,8 @@ __global__ void __launch_bounds__(kTraceBlock, (TraceCfg<F32, MASKED>::kWavesPer
     uint32_t pm0 = 0u, pm1 = 0u;
     if constexpr (PRIM) pm0 = h_me[kPm], pm1 = h_me[kPm + 64];
     // (scene fields re-read from the kernel argument: SGPR budget)
-    closest_hit<R, F32, MODE, PRIM>(opaque(kargs<R>())->sc, T, L, RTW_KA(tmin), RTW_KA(pre_k), lid, st, hit, tmax,
-                                    pm0, pm1);
+    closest_hit<R, F32, MODE, PRIM, false, Cfg::kLeavePre>(opaque(kargs<R>())->sc, T, L, RTW_KA(tmin), RTW_KA(pre_k), lid,
+                                                           st, hit, tmax, pm0, pm1);
     if (hit < 0) {  // miss: background (main.zig:109-112)
       const V3<R> col = mulv(L.T, ld3(opaque(kargs<R>())->bg));
       h_sum[lid] += (double)col.x;
