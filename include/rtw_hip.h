@@ -287,7 +287,13 @@ typedef enum {
   RTW_PRIM_MOVING_SPHERE = 1, /* MovingSphere  hittable.zig:157-226 a = c0[3], c1[3], r, t0, t1 */
   RTW_PRIM_XY_RECT = 2,       /* XyRect        hittable.zig:270-323 a = x0, x1, y0, y1, k */
   RTW_PRIM_XZ_RECT = 3,       /* XzRect        hittable.zig:325-378 a = x0, x1, z0, z1, k */
-  RTW_PRIM_YZ_RECT = 4        /* YzRect        hittable.zig:380-427 a = y0, y1, z0, z1, k */
+  RTW_PRIM_YZ_RECT = 4,       /* YzRect        hittable.zig:380-427 a = y0, y1, z0, z1, k */
+  /* Not in the reference (arithmetic: csrc/rtw_tri.hpp).  rtw_hit.u, v = the barycentric
+   * weights of v1 and v2; front when n . d < 0 with n = unit((v1 - v0) x (v2 - v0)); the normal faces the
+   * ray.  A non-finite vertex or zero area: RTW_EINVAL at creation, update and rebuild (the world is left
+   * untouched).  rtw_world_prev_points_* and rtw_world_mirror_points_* return RTW_UNSUPPORTED for a world
+   * or description that holds one. */
+  RTW_PRIM_TRIANGLE = 5       /* a = v0[3], v1[3], v2[3] */
 } rtw_prim_kind;
 
 typedef struct {
@@ -887,6 +893,17 @@ int rtw_scene_trace(rtw_scene s, const rtw_ray *rays, uint64_t n, rtw_hit *hits_
  * device (a smaller batch launches ceil(n / 256)), dynamic LDS bytes per
  * workgroup}. */
 int rtw_world_query_info(rtw_world w, const rtw_query_opts *opts, uint32_t info_out[4]);
+/* Host reference of the triangle primitive (no device involved): the closest hit
+ * of each ray over the description's TRIANGLE primitives only — every other
+ * kind is skipped — by the reference's sequential list loop, chains included,
+ * through the arithmetic the kernels run (csrc/rtw_tri.hpp).  Records as
+ * rtw_world_trace's (prim = list index + 1, a miss all zero).  For tests and
+ * for integrators that want a CPU twin; merged with the oracle's record of the
+ * other kinds (the smaller t, the later list index on a tie) it is the record
+ * rtw_world_trace_device returns.  RTW_EINVAL for null pointers, or a triangle
+ * with a chain out of range, a non-finite vertex or zero area. */
+int rtw_world_trace_tri_host(const rtw_world_desc *desc, const rtw_ray *rays, size_t n, const rtw_query_opts *opts,
+                             rtw_hit *hits_out);
 
 /* ======================================================== surface queries ===
  *   What the surface under a hit record IS: its material's

@@ -109,8 +109,8 @@ struct Material {
 };
 
 struct Hittable {
-  enum class Kind { sphere, movingSphere, list, xyRect, xzRect, yzRect, box, translate, rotateY } kind = Kind::list;
-  Point3 center0, center1;
+  enum class Kind { sphere, movingSphere, list, xyRect, xzRect, yzRect, box, translate, rotateY, triangle } kind = Kind::list;
+  Point3 center0, center1, v2;
   double time0 = 0, time1 = 1, radius = 0;
   double a0 = 0, a1 = 0, b0 = 0, b1 = 0, k = 0;  // rects (first, second in-plane axis; plane offset)
   Point3 box_min, box_max;                       // box (sides in `objects`)
@@ -127,6 +127,8 @@ struct Hittable {
   static Hittable makeXzRect(double x0, double x1, double z0, double z1, double k, std::shared_ptr<Material> m);
   static Hittable makeYzRect(double y0, double y1, double z0, double z1, double k, std::shared_ptr<Material> m);
   static Hittable makeBox(Point3 p0, Point3 p1, std::shared_ptr<Material> m);             // hittable.zig:34-36
+  // Not in the reference: a triangle (rtw_hip.h RTW_PRIM_TRIANGLE); its vertices in center0, center1, v2.
+  static Hittable makeTriangle(Point3 v0, Point3 v1, Point3 v2, std::shared_ptr<Material> m);
   static Hittable makeTranslate(std::shared_ptr<Hittable> obj, Vec3 offset);            // hittable.zig:38-40
   static Hittable makeRotateY(std::shared_ptr<Hittable> obj, double angle_rad);         // hittable.zig:42-44
 };

@@ -368,7 +368,7 @@ struct WorldGuideArgs {
   GuideRay r;
 };
 hipError_t launch_scene_guides(const SceneGuideArgs& a, hipStream_t s);
-hipError_t launch_world_guides(const WorldGuideArgs& a, hipStream_t s);
+hipError_t launch_world_guides(const WorldGuideArgs& a, bool tri, hipStream_t s);  // tri: the world holds triangles
 
 // ------------------------------------------------------------ ray queries --
 // rtw_query.hip (rtw_hip.h "ray queries"): closest hit or

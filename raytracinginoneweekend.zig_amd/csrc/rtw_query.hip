@@ -165,6 +165,7 @@ __global__ void __launch_bounds__(kQueryBlock) scene_query_kernel(SceneQueryArgs
 }
 
 constexpr int kLanePacked = kFeatImage | kFeatLane | kFeatPacked, kLanePlain = kFeatImage | kFeatLane;
+constexpr int kTriLanePacked = kLanePacked | kFeatTri, kTriLanePlain = kLanePlain | kFeatTri, kTriAll = kFeatAll | kFeatTri;
 
 template <typename K>
 int blocks_per_cu(K kernel, size_t lds) {
@@ -193,6 +194,21 @@ hipError_t launch_world_query(const WorldQueryArgs& a, uint32_t grid, int fs, bo
       hipLaunchKernelGGL((world_query_lane_kernel<kLanePlain, true>), g, b, lds, s, a);
     else
       hipLaunchKernelGGL((world_query_lane_kernel<kLanePlain, false>), g, b, lds, s, a);
+  } else if (fs == kTriLanePacked) {
+    if (occlusion)
+      hipLaunchKernelGGL((world_query_lane_kernel<kTriLanePacked, true>), g, b, lds, s, a);
+    else
+      hipLaunchKernelGGL((world_query_lane_kernel<kTriLanePacked, false>), g, b, lds, s, a);
+  } else if (fs == kTriLanePlain) {
+    if (occlusion)
+      hipLaunchKernelGGL((world_query_lane_kernel<kTriLanePlain, true>), g, b, lds, s, a);
+    else
+      hipLaunchKernelGGL((world_query_lane_kernel<kTriLanePlain, false>), g, b, lds, s, a);
+  } else if (fs == kTriAll) {
+    if (occlusion)
+      hipLaunchKernelGGL((world_query_kernel<kTriAll, true>), g, b, lds, s, a);
+    else
+      hipLaunchKernelGGL((world_query_kernel<kTriAll, false>), g, b, lds, s, a);
   } else {
     if (occlusion)
       hipLaunchKernelGGL((world_query_kernel<kFeatAll, true>), g, b, lds, s, a);
@@ -218,6 +234,15 @@ int query_blocks_per_cu(int fs, bool occlusion) {
   if (fs == kLanePlain)
     return occlusion ? blocks_per_cu(world_query_lane_kernel<kLanePlain, true>, lds)
                      : blocks_per_cu(world_query_lane_kernel<kLanePlain, false>, lds);
+  if (fs == kTriLanePacked)
+    return occlusion ? blocks_per_cu(world_query_lane_kernel<kTriLanePacked, true>, lds)
+                     : blocks_per_cu(world_query_lane_kernel<kTriLanePacked, false>, lds);
+  if (fs == kTriLanePlain)
+    return occlusion ? blocks_per_cu(world_query_lane_kernel<kTriLanePlain, true>, lds)
+                     : blocks_per_cu(world_query_lane_kernel<kTriLanePlain, false>, lds);
+  if (fs == kTriAll)
+    return occlusion ? blocks_per_cu(world_query_kernel<kTriAll, true>, lds)
+                     : blocks_per_cu(world_query_kernel<kTriAll, false>, lds);
   return occlusion ? blocks_per_cu(world_query_kernel<kFeatAll, true>, lds)
                    : blocks_per_cu(world_query_kernel<kFeatAll, false>, lds);
 }

@@ -52,6 +52,9 @@ int check_desc(const char* who, const rtw_world_desc* d) {
   if ((d->n_prims && !d->prims) || (d->n_xforms && !d->xforms) || (d->n_mats && !d->mats))
     return rtw_fail(RTW_EINVAL, "%s: NULL array with a non-zero count", who);
   for (uint32_t i = 0; i < d->n_prims; ++i)
+    if (d->prims[i].kind == RTW_PRIM_TRIANGLE)
+      return rtw_fail(RTW_UNSUPPORTED, "%s: primitive %u is a triangle: mirror points are not built for triangles", who, i);
+  for (uint32_t i = 0; i < d->n_prims; ++i)
     if (d->prims[i].kind > RTW_PRIM_YZ_RECT || d->prims[i].xform < -1 || d->prims[i].xform >= (int32_t)d->n_xforms ||
         d->prims[i].mat >= d->n_mats)
       return rtw_fail(RTW_EINVAL, "%s: primitive %u: kind %u, transform %d, material %u", who, i, d->prims[i].kind,

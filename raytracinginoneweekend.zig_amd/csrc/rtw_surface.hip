@@ -193,7 +193,11 @@ int rtw_world_surface_device(rtw_world w, const rtw_hit* d_hits, uint64_t n, con
   fill_common(a, d_hits, n, background, d_surf, d_guides);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int fs = world_feature_set(feat, false, false);
-  if (fs == kFeatImage)
+  if (fs == (kFeatImage | kFeatTri))
+    launch_world_surface_feat<kFeatImage | kFeatTri>(a, s);
+  else if (fs == (kFeatAll | kFeatTri))
+    launch_world_surface_feat<kFeatAll | kFeatTri>(a, s);
+  else if (fs == kFeatImage)
     launch_world_surface_feat<kFeatImage>(a, s);
   else if (fs == (kFeatXform | kFeatRect))
     launch_world_surface_feat<kFeatXform | kFeatRect>(a, s);

@@ -191,8 +191,11 @@ int rtw_world_prev_points_device(rtw_world w, const rtw_hit* d_hits, uint64_t n,
   using namespace rtwk;
   const char* who = "rtw_world_prev_points_device";
   WorldView view;
-  const int st = rtw_world_view(w, who, &view);  // (the world's device must be current)
+  uint32_t feat = 0;
+  const int st = rtw_world_view(w, who, &view, &feat);  // (the world's device must be current)
   if (st != RTW_OK) return st;
+  if (feat & 64u)  // rtw_world_walk.hpp kFeatTri
+    return rtw_fail(RTW_UNSUPPORTED, "%s: the world holds triangles: previous points are not built for them", who);
   if (n > RTW_QUERY_MAX_RAYS || !std::isfinite(time)) return rtw_fail(RTW_EINVAL, "%s: n > 2^31 or a non-finite time", who);
   if (n == 0) return RTW_OK;
   if (!d_hits || !d_prev_p) return rtw_fail(RTW_EINVAL, "%s: d_hits or d_prev_p is NULL", who);

@@ -97,6 +97,9 @@ int rtw_world_prev_points_host(const rtw_world_desc* d, const rtw_hit* hits, uin
   if ((((uintptr_t)hits | (uintptr_t)prev_p | (uintptr_t)a_prev | (uintptr_t)xv_prev) & 7u) != 0)
     return rtw_fail(RTW_EINVAL, "%s: a buffer is not 8-byte aligned", who);
   for (uint32_t i = 0; i < d->n_prims; ++i)
+    if (d->prims[i].kind == RTW_PRIM_TRIANGLE)
+      return rtw_fail(RTW_UNSUPPORTED, "%s: primitive %u is a triangle: previous points are not built for triangles", who, i);
+  for (uint32_t i = 0; i < d->n_prims; ++i)
     if (d->prims[i].kind > RTW_PRIM_YZ_RECT || d->prims[i].xform < -1 || d->prims[i].xform >= (int32_t)d->n_xforms)
       return rtw_fail(RTW_EINVAL, "%s: primitive %u: kind %u, transform %d", who, i, d->prims[i].kind, d->prims[i].xform);
   for (uint32_t i = 0; i < d->n_xforms; ++i)

@@ -48,7 +48,9 @@ namespace rtwk {
 // literal sequential loop (seq_hit: no BVH, no LDS — the kernel runs once per
 // frame, and the loop is the one traversal with nothing to get wrong), then the
 // winner's hit record and texture value as world_kernel's shade computes them.
-// The general feature set: every primitive, texture and transform.
+// The general feature set: every primitive, texture and transform (FEAT: kFeatAll, with kFeatTri for a
+// world that holds triangles).
+template <int FEAT>
 __global__ void __launch_bounds__(kGuideTileW* kGuideTileH) world_guides_kernel(WorldGuideArgs A) {
   uint32_t x, q;
   if (!guide_pixel(A.r, x, q)) return;
@@ -58,7 +60,7 @@ __global__ void __launch_bounds__(kGuideTileW* kGuideTileH) world_guides_kernel(
   const D time = A.r.time;
   WHit h;
   h.nan = 0u;
-  seq_hit<kFeatAll>(W, W.order, o0, d0, time, (D)0.001, h);
+  seq_hit<FEAT>(W, W.order, o0, d0, time, (D)0.001, h);
   if (h.pos < 0) {
     guide_store(A.r, x, q, mk(0.0, 0.0, 0.0), 0.0, ld3(A.r.bg), 0u);
     return;
@@ -70,7 +72,7 @@ __global__ void __launch_bounds__(kGuideTileW* kGuideTileH) world_guides_kernel(
   const bool image_tex =
       (mkind == 0u || mkind == 3u) && *reinterpret_cast<const uint32_t*>(W.tex + kWorldRec * mtex) == 3u;
   // (getSphereUv only where an image texture reads it)
-  const HitRec R = hit_record<kFeatAll>(W, h.pos, h.t, o0, d0, time, image_tex);
+  const HitRec R = hit_record<FEAT>(W, h.pos, h.t, o0, d0, time, image_tex);
   const V& p = R.p;
   const V& nrm = R.nrm;
   const D tu = R.u, tv = R.v;
@@ -80,13 +82,16 @@ __global__ void __launch_bounds__(kGuideTileW* kGuideTileH) world_guides_kernel(
   else if (mkind == 2u)
     albedo = mk(1.0, 1.0, 1.0);
   else
-    albedo = tex_value<kFeatAll>(W, mtex, tu, tv, p);
+    albedo = tex_value<FEAT>(W, mtex, tu, tv, p);
   guide_store(A.r, x, q, nrm, h.t, albedo, (uint32_t)h.orig + 1u);
 }
 
-hipError_t launch_world_guides(const WorldGuideArgs& a, hipStream_t s) {
+hipError_t launch_world_guides(const WorldGuideArgs& a, bool tri, hipStream_t s) {
   const dim3 grid((a.r.W + kGuideTileW - 1) / kGuideTileW, (a.r.row_count + kGuideTileH - 1) / kGuideTileH);
-  hipLaunchKernelGGL(world_guides_kernel, grid, dim3(kGuideTileW * kGuideTileH), 0, s, a);
+  if (tri)
+    hipLaunchKernelGGL(world_guides_kernel<kFeatAll | kFeatTri>, grid, dim3(kGuideTileW * kGuideTileH), 0, s, a);
+  else
+    hipLaunchKernelGGL(world_guides_kernel<kFeatAll>, grid, dim3(kGuideTileW * kGuideTileH), 0, s, a);
   return hipGetLastError();
 }
 
@@ -337,7 +342,12 @@ __global__ void __launch_bounds__(kWorldBlock, OCC) world_kernel(WorldArgs A) {
         const uint32_t mkind = mh[0], mtex = mh[1];
         const bool image_tex = (FEAT & kFeatImage) &&
             (mkind == 0u || mkind == 3u) && *reinterpret_cast<const uint32_t*>(W.tex + kWorldRec * mtex) == 3u;
-        if (!(FEAT & kFeatRect) || kind <= 1u) {
+        if ((FEAT & kFeatTri) && kind == 5u) {  // rtw_tri.hpp (as hit_record)
+          const V n0 = mk(r[rtwtri::kNx], r[rtwtri::kNy], r[rtwtri::kNz]);
+          if (image_tex) rtwtri::bary(r, o.x, o.y, o.z, d.x, d.y, d.z, tu, tv);  // (only an image texture reads u, v)
+          front = dot(n0, d) < 0.0;
+          nrm = front ? n0 : mul(n0, -1.0);
+        } else if (!(FEAT & kFeatRect) || kind <= 1u) {
           V c = ld3(r);
           if (kind == 1u) c = add(c, mul(ld3(r + 3), (L.time - r[7]) / r[8]));
           const V outward = divs(sub(p, c), r[6]);
@@ -594,6 +604,11 @@ static void launch_feat(const WorldArgs& a, uint32_t grid, size_t lds, hipStream
 // (scenes 1, 2, 4 and configs[4]'s globe), rects + transforms + lights without
 // noise / image (the Cornell box, scene 5's light), and everything.
 int world_feature_set(uint32_t feat, bool lane, bool packed) {
+  if (feat & (uint32_t)kFeatTri) {  // triangles: spheres + triangles without chains (meshes; per lane too), or everything
+    if ((feat & ~(uint32_t)(kFeatImage | kFeatTri)) == 0u)
+      return kFeatTri | (lane ? (packed ? (kFeatImage | kFeatLane | kFeatPacked) : (kFeatImage | kFeatLane)) : kFeatImage);
+    return kFeatAll | kFeatTri;
+  }
   if ((feat & ~(uint32_t)kFeatImage) == 0u)
     return lane ? (packed ? (kFeatImage | kFeatLane | kFeatPacked) : (kFeatImage | kFeatLane)) : kFeatImage;
   if ((feat & ~(uint32_t)(kFeatXform | kFeatRect)) == 0u) return kFeatXform | kFeatRect;
@@ -608,6 +623,14 @@ hipError_t launch_world(const WorldArgs& a, uint32_t grid, size_t lds, hipStream
     launch_feat<kFeatImage>(a, grid, lds, s, mode, occ);
   else if (fs == (kFeatXform | kFeatRect))
     launch_feat<kFeatXform | kFeatRect>(a, grid, lds, s, mode, occ);
+  else if (fs == (kFeatTri | kFeatImage | kFeatLane | kFeatPacked))
+    launch_feat<kFeatTri | kFeatImage | kFeatLane | kFeatPacked>(a, grid, lds, s, mode, occ);
+  else if (fs == (kFeatTri | kFeatImage | kFeatLane))
+    launch_feat<kFeatTri | kFeatImage | kFeatLane>(a, grid, lds, s, mode, occ);
+  else if (fs == (kFeatTri | kFeatImage))
+    launch_feat<kFeatTri | kFeatImage>(a, grid, lds, s, mode, occ);
+  else if (fs == (kFeatTri | kFeatAll))
+    launch_feat<kFeatTri | kFeatAll>(a, grid, lds, s, mode, occ);
   else
     launch_feat<kFeatAll>(a, grid, lds, s, mode, occ);
   return hipGetLastError();
@@ -634,6 +657,10 @@ int world_blocks_per_cu(size_t lds, int occ, int fs) {
   if (fs == (kFeatImage | kFeatLane)) return bpc_feat<kFeatImage | kFeatLane>(lds, occ);
   if (fs == kFeatImage) return bpc_feat<kFeatImage>(lds, occ);
   if (fs == (kFeatXform | kFeatRect)) return bpc_feat<kFeatXform | kFeatRect>(lds, occ);
+  if (fs == (kFeatTri | kFeatImage | kFeatLane | kFeatPacked)) return bpc_feat<kFeatTri | kFeatImage | kFeatLane | kFeatPacked>(lds, occ);
+  if (fs == (kFeatTri | kFeatImage | kFeatLane)) return bpc_feat<kFeatTri | kFeatImage | kFeatLane>(lds, occ);
+  if (fs == (kFeatTri | kFeatImage)) return bpc_feat<kFeatTri | kFeatImage>(lds, occ);
+  if (fs == (kFeatTri | kFeatAll)) return bpc_feat<kFeatTri | kFeatAll>(lds, occ);
   return bpc_feat<kFeatAll>(lds, occ);
 }
 

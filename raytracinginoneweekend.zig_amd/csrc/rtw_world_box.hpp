@@ -43,6 +43,11 @@ Box prim_box(const rtw_prim& p, const rtw_xform* xf) {
       for (int k = 0; k < 3; ++k) cb.lo[k] = c[k] - r, cb.hi[k] = c[k] + r;
       b.grow(cb);
     }
+  } else if (p.kind == RTW_PRIM_TRIANGLE) {  // its vertices' box, padded by 1e-4 on every axis
+    for (int k = 0; k < 3; ++k) {
+      b.lo[k] = std::min(std::min(p.a[k], p.a[3 + k]), p.a[6 + k]) - 0.0001;
+      b.hi[k] = std::max(std::max(p.a[k], p.a[3 + k]), p.a[6 + k]) + 0.0001;
+    }
   } else {
     const int ax_k = p.kind == RTW_PRIM_XY_RECT ? 2 : (p.kind == RTW_PRIM_XZ_RECT ? 1 : 0);
     const int ax_a = p.kind == RTW_PRIM_YZ_RECT ? 1 : 0, ax_b = p.kind == RTW_PRIM_XY_RECT ? 1 : 2;

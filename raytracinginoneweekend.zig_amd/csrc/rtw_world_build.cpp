@@ -12,6 +12,7 @@
 #include "rtw_layout.hpp"
 #include "rtw_world_build.hpp"
 #include "rtw_world_pack.hpp"
+#include "rtw_tri.hpp"
 #include "rtw_world_refit.hpp"
 
 namespace rtwp {

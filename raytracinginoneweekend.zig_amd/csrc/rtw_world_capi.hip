@@ -83,6 +83,7 @@ int make_dynamic(rtw_world_s* w, const rtw_world_desc* d, const rtwp::WorldPack&
   V.mate = reinterpret_cast<const uint32_t*>(rb + r->o_mate);
   V.n_prims = k.n_prims, V.n_xforms = d->n_xforms, V.n_nodes = k.n_nodes;
   V.packed = k.packed ? 1u : 0u, V.has_table = k.has_cull ? 1u : 0u;
+  V.has_tri = (k.feat & 64u) ? 1u : 0u;
   w->upd.partials = reinterpret_cast<double*>(rb + o_part);
   w->upd.result = reinterpret_cast<double*>(rb + o_res);
   w->upd.n_wg = n_wg;
@@ -444,7 +445,10 @@ namespace {
 static_assert(rtwk::kMaxXfOps == RTW_MAX_XFORM_OPS, "transform chain length");
 int world_occ_default(const rtw_world_s* w) {
   if (w->view.n_perlins) return 1;
-  return (w->feat & (4u | 8u)) ? 3 : 4;  // rtw_world.hip kFeatXform | kFeatRect
+  // rtw_world.hip kFeatXform | kFeatRect; kFeatTri: at the 4-wave budget (128 VGPRs) every triangle set
+  // spills (64-128 B per lane; per lane too, the record is 13 doubles), at 3 waves none does, and the mesh
+  // world of tools/mesh_bench.py renders 10 % faster there (profiles/r26/mesh.txt)
+  return (w->feat & (4u | 8u | 64u)) ? 3 : 4;
 }
 
 // Widening of every BVH box test.  A computed sphere root deviates from the
@@ -490,12 +494,12 @@ WorldLaunchCfg world_cfg(const rtw_world_s* w, const rtw_params* p, int dev) {
   // RTW_WORLD_FEATURES_ALL: the general kernel; every set gives the same bits)
   // and its BVH traversal (params.world_traversal): per lane for sphere worlds
   // whose BVH fits the per-lane stack, else the wave's union walk.
-  const uint32_t feat = p->world_features == RTW_WORLD_FEATURES_ALL ? 15u : w->feat;
+  const uint32_t feat = p->world_features == RTW_WORLD_FEATURES_ALL ? (15u | (w->feat & 64u)) : w->feat;  // (64: kFeatTri)
   // AUTO: per lane on BVHs of >= kLaneNodes nodes (configs[4]'s globe: 5,802
   // nodes, +30 %); the union walk on small trees, where the lanes' paths
   // mostly coincide (scene 1's 23 nodes: the union 17 % faster).
   const bool lane_ok = w->view.n_nodes > 0 && w->info[2] <= rtwk::kLaneStack && w->info[3] <= rtwk::kMaxLeafPrims &&
-                       w->view.n_prims + 1u < (1u << rtwk::kTravPosBits);
+                       w->view.n_prims + 1u < (1u << rtwk::kTravPosBits) && (feat & ~(2u | 64u)) == 0u;
   const bool lane = lane_ok && (p->world_traversal == RTW_WORLD_TRAVERSAL_LANE ||
                                 (p->world_traversal == RTW_WORLD_TRAVERSAL_AUTO && w->view.n_nodes >= kLaneNodes));
   const char* up = rtw_dev_knob("RTW_WORLD_UNPACKED");  // development knob (A/B): the per-lane walk loads the refs
@@ -507,8 +511,8 @@ WorldLaunchCfg world_cfg(const rtw_world_s* w, const rtw_params* p, int dev) {
   const int occ = p->world_waves ? (int)p->world_waves : world_occ_default(w);
   c.oi = occ >= 4 ? 4 : (occ == 3 ? 3 : 1);
   static std::mutex mu;
-  static int bpc_cache[64][5] = {};
-  static size_t bpc_lds[64][5] = {};
+  static int bpc_cache[128][5] = {};
+  static size_t bpc_lds[128][5] = {};
   int bpc;
   {
     std::lock_guard<std::mutex> lk(mu);
@@ -630,7 +634,7 @@ int rtw_world_guides_device(rtw_world w, const rtw_camera* cam, const rtw_params
   if (dev != w->device)
     return rtw_fail(RTW_EINVAL, "rtw_world_guides_device: world lives on device %d, current is %d", w->device, dev);
   a.w = w->view;
-  const hipError_t e = rtwk::launch_world_guides(a, static_cast<hipStream_t>(stream));
+  const hipError_t e = rtwk::launch_world_guides(a, (w->feat & 64u) != 0u, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return rtw_fail(RTW_EHIP, "guide kernel launch: %s", hipGetErrorString(e));
   return RTW_OK;
 }
@@ -710,18 +714,18 @@ struct QueryCfg {
 };
 QueryCfg query_cfg(const rtw_world_s* w, const rtw_query_opts* o) {
   // per lane: sphere worlds (image textures allowed) whose BVH fits the per-lane stack, as world_cfg
-  const bool lane_ok = (w->feat & ~2u) == 0u && w->view.n_nodes > 0 && w->info[2] <= rtwk::kLaneStack &&
+  const bool lane_ok = (w->feat & ~(2u | 64u)) == 0u && w->view.n_nodes > 0 && w->info[2] <= rtwk::kLaneStack &&
                        w->info[3] <= rtwk::kMaxLeafPrims && w->view.n_prims + 1u < (1u << rtwk::kTravPosBits);
   QueryCfg c;
   c.traversal = rtwq::traversal(o ? o->traversal : 0u, w->view.n_nodes, lane_ok);
-  c.fs = c.traversal == RTW_WORLD_TRAVERSAL_LANE ? rtwk::world_feature_set(w->feat, true, w->packed) : 15;
+  c.fs = c.traversal == RTW_WORLD_TRAVERSAL_LANE ? rtwk::world_feature_set(w->feat, true, w->packed) : (15 | (int)(w->feat & 64u));
   return c;
 }
 int query_bpc(int fs, bool occlusion) {  // resident workgroups per CU, asked once per kernel
   static std::mutex mu;
-  static int cache[64][2] = {};
+  static int cache[128][2] = {};
   std::lock_guard<std::mutex> lk(mu);
-  int& e = cache[fs & 63][occlusion ? 1 : 0];
+  int& e = cache[fs & 127][occlusion ? 1 : 0];
   if (e == 0) e = rtwk::query_blocks_per_cu(fs, occlusion);
   return e;
 }
@@ -819,6 +823,8 @@ int rtw_world_mirror_points_device(rtw_world w, const rtw_ray* d_rays, const rtw
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return rtw_fail(RTW_ENODEV, "no HIP device");
   if (dev != w->device) return rtw_fail(RTW_EINVAL, "%s: world lives on device %d, current is %d", who, w->device, dev);
+  if (w->feat & 64u)  // rtw_world_walk.hpp kFeatTri
+    return rtw_fail(RTW_UNSUPPORTED, "%s: the world holds triangles: mirror points are not built for them", who);
   if (n > RTW_QUERY_MAX_RAYS) return rtw_fail(RTW_EINVAL, "%s: n > 2^31", who);
   const rtw_mirror_opts dflt{};
   if (!opts) opts = &dflt;

@@ -96,6 +96,13 @@ Hittable Hittable::makeXzRect(double x0, double x1, double z0, double z1, double
 Hittable Hittable::makeYzRect(double y0, double y1, double z0, double z1, double k, std::shared_ptr<Material> m) {
   return rect(Kind::yzRect, y0, y1, z0, z1, k, std::move(m));
 }
+Hittable Hittable::makeTriangle(Point3 v0, Point3 v1, Point3 v2, std::shared_ptr<Material> m) {
+  Hittable h;
+  h.kind = Kind::triangle;
+  h.center0 = v0, h.center1 = v1, h.v2 = v2;
+  h.material = std::move(m);
+  return h;
+}
 Hittable Hittable::makeBox(Point3 p0, Point3 p1, std::shared_ptr<Material> m) {  // Box.init, hittable.zig:434-452
   Hittable h;
   h.kind = Kind::box;
@@ -310,6 +317,12 @@ struct Flattener {
         p.a[8] = mv ? h.time1 : 0.0;
         break;
       }
+      case Hittable::Kind::triangle:
+        p.kind = RTW_PRIM_TRIANGLE;
+        put3(p.a, h.center0);
+        put3(p.a + 3, h.center1);
+        put3(p.a + 6, h.v2);
+        break;
       default:
         p.kind = h.kind == Hittable::Kind::xyRect ? RTW_PRIM_XY_RECT
                  : h.kind == Hittable::Kind::xzRect ? RTW_PRIM_XZ_RECT : RTW_PRIM_YZ_RECT;

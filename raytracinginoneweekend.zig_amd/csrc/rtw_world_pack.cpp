@@ -12,6 +12,7 @@
 
 #include "rtw_cull.hpp"
 #include "rtw_layout.hpp"
+#include "rtw_tri.hpp"
 #include "rtw_world_box.hpp"
 #include "rtw_world_refit.hpp"
 
@@ -324,7 +325,7 @@ int pack_world(const rtw_world_desc* d, uint32_t flags, bool no_leaf_pretest, Wo
   std::vector<Box> boxes(d->n_prims);
   for (uint32_t i = 0; i < d->n_prims; ++i) {
     const rtw_prim& p = d->prims[i];
-    if (p.kind > RTW_PRIM_YZ_RECT || p.mat >= d->n_mats || p.xform >= (int32_t)d->n_xforms || p.xform < -1) {
+    if (p.kind > RTW_PRIM_TRIANGLE || p.mat >= d->n_mats || p.xform >= (int32_t)d->n_xforms || p.xform < -1) {
       return fail(msg, RTW_EINVAL, "prim %u: kind %u / material %u / xform %d out of range", i, p.kind, p.mat, p.xform);
     }
     // MovingSphere.center divides by time1 - time0 (hittable.zig:219-221): an
@@ -333,11 +334,21 @@ int pack_world(const rtw_world_desc* d, uint32_t flags, bool no_leaf_pretest, Wo
     if (p.kind == RTW_PRIM_MOVING_SPHERE && !(p.a[8] > p.a[7])) {
       return fail(msg, RTW_EINVAL, "prim %u: moving sphere needs time1 > time0 (got %g, %g)", i, p.a[7], p.a[8]);
     }
+    // A triangle needs finite vertices and a non-zero, finite area (rtw_tri.hpp derive): its
+    // normal divides by the area.
+    if (p.kind == RTW_PRIM_TRIANGLE) {
+      double nn[3], hh;
+      bool fin = true;
+      for (int k = 0; k < 9; ++k) fin = fin && rtwr::finite(p.a[k]);
+      if (!fin || !rtwtri::derive(p.a, nn, hh))
+        return fail(msg, RTW_EINVAL, "prim %u: triangle with a non-finite vertex or zero area", i);
+      wp.feat |= 64u;
+    }
     boxes[i] = prim_box(p, p.xform >= 0 ? &d->xforms[p.xform] : nullptr);
     bounds.grow(boxes[i]);
     wp.has_moving |= p.kind == RTW_PRIM_MOVING_SPHERE;
     if (p.xform >= 0) wp.feat |= 4u;
-    if (p.kind >= RTW_PRIM_XY_RECT) wp.feat |= 8u;
+    if (p.kind >= RTW_PRIM_XY_RECT && p.kind <= RTW_PRIM_YZ_RECT) wp.feat |= 8u;
   }
   Bvh bvh;
   // Small worlds (<= kLinearMax primitives: the Cornell box, the Perlin and
@@ -387,7 +398,10 @@ int pack_world(const rtw_world_desc* d, uint32_t flags, bool no_leaf_pretest, Wo
     list_to_pos[li] = pos;
     const rtw_prim& p = d->prims[li];
     double* r = prim.data() + (size_t)rtwk::kWorldRec * pos;
-    rtwr::fill_record(p.kind, p.a, r);  // doubles 0-10 (shared with the refit)
+    if (p.kind == RTW_PRIM_TRIANGLE)
+      (void)rtwr::fill_record_tri(p.a, r);  // doubles 0-10, 12, 13
+    else
+      rtwr::fill_record(p.kind, p.a, r);  // doubles 0-10 (shared with the refit)
     const uint32_t meta[4] = {p.kind | ((uint32_t)(p.xform + 1) << 8), p.mat, li, 0u};
     std::memcpy(r + 14, meta, sizeof(meta));
     // the kind and list index again in double 11, so the per-lane walk's root

@@ -24,7 +24,7 @@ struct WorldPack {
   uint32_t n_prims = 0, n_nodes = 0, n_perlins = 0;
   uint32_t view_flags = 0;  // WorldView.flags (kWorldHasSpheres)
   float cull_cmax = 0.0f, cull_rho = 0.0f;  // rtw_cull.hpp Cmax and rho_max over the pretested spheres
-  uint32_t feat = 0;        // features used (rtw_world.hip kFeat*): 1 noise, 2 image, 4 transform chains, 8 rects
+  uint32_t feat = 0;        // features used (rtw_world.hip kFeat*): 1 noise, 2 image, 4 transform chains, 8 rects, 64 triangles
   bool has_moving = false;
   double bounds_lo[3] = {0, 0, 0}, bounds_hi[3] = {0, 0, 0};  // box of every primitive (+-inf when empty)
   uint32_t info[4] = {0, 0, 0, 0};  // rtw_world_bvh_info: nodes, leaves, depth, largest leaf

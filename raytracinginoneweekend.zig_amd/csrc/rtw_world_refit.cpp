@@ -12,6 +12,7 @@
 #include "rtw_cull.hpp"
 #include "rtw_layout.hpp"
 #include "rtw_world_pack.hpp"
+#include "rtw_tri.hpp"
 #include "rtw_world_refit.hpp"
 
 namespace rtwp {
@@ -33,6 +34,7 @@ rtwr::View refit_view(WorldPack& k, RefitPack& r, const double* a, const double*
   V.a = a, V.xv = xv;
   V.n_prims = k.n_prims, V.n_xforms = r.n_xforms, V.n_nodes = k.n_nodes;
   V.packed = k.packed ? 1u : 0u, V.has_table = k.has_cull ? 1u : 0u, V.cull_on = 0u;
+  V.has_tri = (k.feat & 64u) ? 1u : 0u;
   return V;
 }
 

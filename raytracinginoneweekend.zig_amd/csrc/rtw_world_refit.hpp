@@ -22,6 +22,13 @@
 #define RTWR_HD inline
 #endif
 
+// The triangle's derived fields (rtw_tri.hpp, which defines it): declared here
+// so that this header keeps standing on rtw_layout.hpp alone; a translation
+// unit that packs, validates or commits primitives includes rtw_tri.hpp too.
+namespace rtwtri {
+RTWR_HD bool derive(const double* a, double n[3], double& h);
+}
+
 namespace rtwr {
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;
@@ -126,6 +133,17 @@ RTWR_HD void fill_record(uint32_t kind, const double* a, double r[11]) {
   }
 }
 
+// A triangle's record (kind 5, rtw_tri.hpp): its vertices and the derived n, h
+// in doubles 0-10, 12, 13 of r (r[11], the per-lane walk's kind copy, is not
+// touched).  false: degenerate or not finite.
+RTWR_HD bool fill_record_tri(const double* a, double r[14]) {
+  for (int k = 0; k < 9; ++k) r[k] = a[k];
+  double n[3], h;
+  const bool ok = rtwtri::derive(a, n, h);
+  r[9] = n[0], r[10] = n[1], r[12] = n[2], r[13] = h;  // rtwtri::kNx, kNy, kNz, kH
+  return ok;
+}
+
 // Header word of a transform record: n | op[k] << (8 + 4 k).
 RTWR_HD uint32_t xform_ops(uint32_t h) { return h & 0xFFu; }
 RTWR_HD uint32_t xform_op(uint32_t h, int k) { return (h >> (8 + 4 * k)) & 0xFu; }
@@ -153,6 +171,10 @@ RTWR_HD void prim_box(uint32_t kind, const double* a, uint32_t xf_h, const doubl
       lo[1] = dmin(lo[1], c1 - r), hi[1] = dmax(hi[1], c1 + r);
       lo[2] = dmin(lo[2], c2 - r), hi[2] = dmax(hi[2], c2 + r);
     }
+  } else if (kind == 5u) {  // triangle: its vertices' box, padded by 1e-4 on every axis as a rect's plane is
+    lo[0] = dmin(dmin(a[0], a[3]), a[6]) - 0.0001, hi[0] = dmax(dmax(a[0], a[3]), a[6]) + 0.0001;
+    lo[1] = dmin(dmin(a[1], a[4]), a[7]) - 0.0001, hi[1] = dmax(dmax(a[1], a[4]), a[7]) + 0.0001;
+    lo[2] = dmin(dmin(a[2], a[5]), a[8]) - 0.0001, hi[2] = dmax(dmax(a[2], a[5]), a[8]) + 0.0001;
   } else {
     const double k0 = a[4] - 0.0001, k1 = a[4] + 0.0001;
     if (kind == 2u) {  // XY: x, y, k on z
@@ -228,6 +250,7 @@ struct View {
   uint32_t packed;     // the tree carries its refs in the lower bounds
   uint32_t has_table;  // the world was created with a pretest table
   uint32_t cull_on;    // this update's Cmax is within rtwc::kCmaxLimit
+  uint32_t has_tri;    // the world holds triangles (feature bit 64): records carry doubles 12-13
 };
 
 RTWR_HD const double* xform_vals(const View& V, uint32_t xi) {
@@ -278,6 +301,10 @@ RTWR_HD void validate_prim(const View& V, uint32_t i, Partial& p) {
     ok = ok && finite(a[6]);
     if (kind == 1u)
       ok = ok && finite(a[3]) && finite(a[4]) && finite(a[5]) && finite(a[7]) && finite(a[8]) && a[8] > a[7];
+  } else if (kind == 5u) {  // finite vertices and a non-zero, finite area (rtw_tri.hpp)
+    double n[3], h;
+    ok = ok && finite(a[3]) && finite(a[4]) && finite(a[5]) && finite(a[6]) && finite(a[7]) && finite(a[8]) &&
+         rtwtri::derive(a, n, h);
   } else {
     ok = ok && finite(a[3]) && finite(a[4]);
   }
@@ -311,10 +338,20 @@ RTWR_HD void validate_xform(const View& V, uint32_t xi, Partial& p) {
 // Commit, list index i: doubles 0-10 of its record (the meta doubles stay).
 RTWR_HD void commit_prim(const View& V, uint32_t i) {
   const uint32_t pos = V.order[i];
+  double* d = V.prim + (size_t)rtwk::kWorldRec * pos;
+  if ((prim_meta0(V, pos) & 0xFFu) == 5u) {  // a triangle: doubles 0-10, 12, 13
+    double t[14];
+    (void)fill_record_tri(V.a + (size_t)9 * i, t);
+    for (int k = 0; k < 11; ++k) d[k] = t[k];
+    d[12] = t[12], d[13] = t[13];
+    return;
+  }
   double r[11];
   fill_record(prim_meta0(V, pos) & 0xFFu, V.a + (size_t)9 * i, r);
-  double* d = V.prim + (size_t)rtwk::kWorldRec * pos;
   for (int k = 0; k < 11; ++k) d[k] = r[k];
+  // (a rebuild can move a triangle's record out of this position: no stale n.z, h behind it.  Worlds without
+  // triangles hold zeros there and write nothing more than before.)
+  if (V.has_tri) d[12] = 0.0, d[13] = 0.0;
 }
 RTWR_HD void commit_xform(const View& V, uint32_t xi) {
   if (!V.xv) return;

@@ -7,6 +7,7 @@
 // Visibility between tree heights comes from kernel boundaries, and inside the
 // last launch from the workgroup barrier: no workgroup reads what another
 // wrote in the same launch, there are no counters and nothing spins.
+#include "rtw_tri.hpp"
 #include "rtw_world_update.hpp"
 
 namespace rtwk {

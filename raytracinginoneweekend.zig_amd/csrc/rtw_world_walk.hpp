@@ -9,6 +9,7 @@
 
 #include "rtw_device.hpp"
 #include "rtw_libm.hpp"
+#include "rtw_tri.hpp"
 
 namespace rtwk {
 
@@ -38,6 +39,9 @@ constexpr int kFeatAll = kFeatNoise | kFeatImage | kFeatXform | kFeatRect;
 constexpr int kFeatLane = 16;
 // ... reading each child's ref from its lower bounds' low bits (rtw_world_pack.cpp pack_refs).
 constexpr int kFeatPacked = 32;
+// A world feature outside kFeatAll (the reference's vocabulary): triangles (rtw_tri.hpp).
+// Sets with it carry the longer primitive record (doubles 12-13) and the triangle's root and hit record.
+constexpr int kFeatTri = 64;
 
 __device__ __forceinline__ const uint32_t* meta_of(const D* r) { return reinterpret_cast<const uint32_t*>(r + 14); }
 
@@ -86,15 +90,19 @@ __device__ __forceinline__ void to_world(const D* xf, V& p, V& nrm) {
 // and the meta words), loaded in one place so the linear loop can prefetch
 // the next record (scalar loads through the constant address space) while
 // the current one is tested.
-struct PrimRec {
-  D v[11];
+// (kFeatTri sets: doubles 12-13 too, a triangle's n.z and h, as v[11], v[12].)
+template <bool TRI>
+struct PrimRecT {
+  D v[TRI ? 13 : 11];
   uint32_t meta0, orig;
 };
-template <typename P>
-__device__ __forceinline__ PrimRec load_rec(P r) {
-  PrimRec q;
+using PrimRec = PrimRecT<false>;
+template <int FEAT = 0, typename P>
+__device__ __forceinline__ PrimRecT<(FEAT & kFeatTri) != 0> load_rec(P r) {
+  PrimRecT<(FEAT & kFeatTri) != 0> q;
 #pragma unroll
   for (int i = 0; i < 11; ++i) q.v[i] = r[i];
+  if constexpr ((FEAT & kFeatTri) != 0) q.v[11] = r[12], q.v[12] = r[13];
   // meta u32 {kind | xform+1 << 8, mat, orig, 0} occupies doubles 14-15
   q.meta0 = (uint32_t)__builtin_bit_cast(uint64_t, (D)r[14]);
   q.orig = (uint32_t)__builtin_bit_cast(uint64_t, (D)r[15]);
@@ -102,12 +110,14 @@ __device__ __forceinline__ PrimRec load_rec(P r) {
 }
 
 // The per-lane walk's record load: doubles 0-10 and the {kind, list index}
-// copy in double 11 (rtw_world_pack.cpp), one 96-B span = six 16-B loads.
-template <typename P>
-__device__ __forceinline__ PrimRec load_rec_lane(P r) {
-  PrimRec q;
+// copy in double 11 (rtw_world_pack.cpp), one 96-B span = six 16-B loads
+// (kFeatTri sets: doubles 0-13, seven).
+template <int FEAT = 0, typename P>
+__device__ __forceinline__ PrimRecT<(FEAT & kFeatTri) != 0> load_rec_lane(P r) {
+  PrimRecT<(FEAT & kFeatTri) != 0> q;
 #pragma unroll
   for (int i = 0; i < 11; ++i) q.v[i] = r[i];
+  if constexpr ((FEAT & kFeatTri) != 0) q.v[11] = r[12], q.v[12] = r[13];
   const uint64_t m = __builtin_bit_cast(uint64_t, (D)r[11]);
   q.meta0 = (uint32_t)m;
   q.orig = (uint32_t)(m >> 32);
@@ -150,11 +160,15 @@ __device__ __forceinline__ bool rect_root(const D* r, D ok, D oa, D ob, D dk, D 
 // root_obj: the ray already in the primitive's object space; RCP: use the
 // ray space's a and RN(1/a) (else plain IEEE divisions; same results).
 template <bool RCP, int FEAT>
-__device__ __forceinline__ bool root_obj(const PrimRec& q, const RaySp& s, D time, D tmin, D& t) {
+__device__ __forceinline__ bool root_obj(const PrimRecT<(FEAT & kFeatTri) != 0>& q, const RaySp& s, D time, D tmin,
+                                         D& t) {
   const D* r = q.v;
   const V& o = s.o;
   const V& d = s.d;
   const uint32_t kind = q.meta0 & 0xFFu;
+  if constexpr ((FEAT & kFeatTri) != 0) {  // the plane root, then the edge functions (rtw_tri.hpp)
+    if (kind == 5u) return rtwtri::root(r, r[9], r[10], r[11], r[12], o.x, o.y, o.z, d.x, d.y, d.z, tmin, t);
+  }
   if (!(FEAT & kFeatRect) || kind <= 1u) {
     V c = mk(r[0], r[1], r[2]);
     if (kind == 1u)  // hittable.zig:219-221; r[10] = RN(1 / (time1 - time0))
@@ -178,7 +192,8 @@ __device__ __forceinline__ bool root_obj(const PrimRec& q, const RaySp& s, D tim
   return rect_root(r, o.x, o.y, o.z, d.x, d.y, d.z, tmin, t);
 }
 template <int FEAT, typename WV>
-__device__ __forceinline__ bool prim_root(const WV& W, const PrimRec& q, V o, V d, D time, D tmin, D& t) {
+__device__ __forceinline__ bool prim_root(const WV& W, const PrimRecT<(FEAT & kFeatTri) != 0>& q, V o, V d, D time,
+                                          D tmin, D& t) {
   const int xf = (int)(q.meta0 >> 8) - 1;
   if ((FEAT & kFeatXform) && xf >= 0) to_object(W.xform + kWorldRec * xf, o, d);
   RaySp s;
@@ -265,7 +280,7 @@ __device__ __forceinline__ void seq_hit(const WV& W, const uint32_t* order, V o,
   for (uint32_t i = 0; i < W.n_prims; ++i) {
     const uint32_t k = order[i];
     D t;
-    if (!prim_root<FEAT>(W, load_rec(W.prim + kWorldRec * k), o, d, time, tmin, t)) continue;
+    if (!prim_root<FEAT>(W, load_rec<FEAT>(W.prim + kWorldRec * k), o, d, time, tmin, t)) continue;
     if (h.t < t) continue;  // `t_max < root` rejects; NaN roots are accepted (as in the reference)
     h.t = t;
     h.pos = (int)k;
@@ -299,11 +314,11 @@ __device__ __forceinline__ void closest(const WV& W, D m, uint32_t* stack, const
   h.nan = 0u;
   if (W.n_nodes == 0) {  // linear: wave-uniform loop, scalar-loaded records, one-ahead prefetch
     const RTW_CONST D* pr = cptr(W.prim);
-    PrimRec cur = load_rec(pr);  // (a padding record follows the last primitive)
+    auto cur = load_rec<FEAT>(pr);  // (a padding record follows the last primitive)
     int xf_cur = -1;             // wave-uniform: the transform the cached object-space ray is for
     RaySp s = ray_space(o, d, W.flags);
     for (uint32_t k = 0; k < W.n_prims; ++k) {
-      const PrimRec nxt = load_rec(pr + kWorldRec * (k + 1));
+      const auto nxt = load_rec<FEAT>(pr + kWorldRec * (k + 1));
       const int xf = (int)(cur.meta0 >> 8) - 1;
       if ((FEAT & kFeatXform) && xf != xf_cur) {  // consecutive primitives share a chain (a Box's six rects)
         xf_cur = xf;
@@ -366,7 +381,7 @@ __device__ __forceinline__ void closest(const WV& W, D m, uint32_t* stack, const
   auto leaf = [&](uint32_t ref) {
     WSTAMP(2)  // (MODE 2: node visits up to here)
     const uint32_t first = ref & 0x7FFFFFu, cnt = (ref >> 23) & kLeafCountMask;
-    auto test_prim = [&](uint32_t k, const PrimRec& q) {
+    auto test_prim = [&](uint32_t k, const PrimRecT<(FEAT & kFeatTri) != 0>& q) {
       const int xf = (int)(q.meta0 >> 8) - 1;
       D t;
       if (MODE == 1) ++nt;
@@ -382,7 +397,7 @@ __device__ __forceinline__ void closest(const WV& W, D m, uint32_t* stack, const
       if (ok) accept(h, t, (int)k, (int)q.orig, tmin);
     };
     bool need0 = true, need1 = true;
-    if ((FEAT & ~(kFeatImage | kFeatLane)) == 0 && (ref & kCullBit)) {  // sphere worlds (the others ignore the bit)
+    if ((FEAT & ~(kFeatImage | kFeatLane | kFeatTri)) == 0 && (ref & kCullBit)) {  // sphere worlds (the others ignore the bit)
       const f2 x = cull_pair<1>(ld_pair(ct, first), bc((float)o.x), bc((float)o.y), bc((float)o.z), bc((float)d.x),
                                 bc((float)d.y), bc((float)d.z), bc(lk.na), bc(lk.k), bc((float)time));
       need0 = (act & ~(cull_ok & wballot(x.x < 0.0f))) != 0;  // some lane not proven to miss
@@ -393,7 +408,7 @@ __device__ __forceinline__ void closest(const WV& W, D m, uint32_t* stack, const
     // profiles/r03/world_leaf_prefetch_ab.txt.)
     for (uint32_t k = first; k < first + cnt; ++k) {
       if (!(k == first ? need0 : (k == first + 1 ? need1 : true))) continue;  // wave-uniform
-      test_prim(k, load_rec(pr + kWorldRec * k));
+      test_prim(k, load_rec<FEAT>(pr + kWorldRec * k));
     }
     tmaxf = round_up(h.t);
     if constexpr (ANY) {  // a lane with a hit needs no further box: its interval is empty from here on
@@ -692,7 +707,7 @@ __device__ __forceinline__ bool trav_phase(const WV& W, D m, uint32_t* lstack, L
       for (uint32_t k = first; k < first + cnt; ++k) {
         if (MODE == 1) ++nt;
         D t;
-        const PrimRec q = load_rec_lane(reinterpret_cast<GD*>(
+        const auto q = load_rec_lane<FEAT>(reinterpret_cast<GD*>(
             reinterpret_cast<const __attribute__((address_space(1))) char*>(pr) + (k << 7)));  // (kWorldRec doubles = 128 B)
         if (root_obj<true, FEAT>(q, ws, time, tmin, t)) accept(h, t, (int)k, (int)q.orig, tmin);
       }
@@ -740,7 +755,12 @@ __device__ __forceinline__ HitRec hit_record(const WV& W, int pos, D t, const V&
   if ((FEAT & kFeatXform) && xf >= 0) to_object(W.xform + kWorldRec * xf, o, d);
   R.p = add(o, mul(d, t));
   R.u = 0.0, R.v = 0.0;
-  if (!(FEAT & kFeatRect) || kind <= 1u) {
+  if ((FEAT & kFeatTri) && kind == 5u) {  // rtw_tri.hpp: the stored unit normal, the barycentric weights of v1, v2
+    const V n0 = mk(r[rtwtri::kNx], r[rtwtri::kNy], r[rtwtri::kNz]);
+    rtwtri::bary(r, o.x, o.y, o.z, d.x, d.y, d.z, R.u, R.v);
+    R.front = dot(n0, d) < 0.0;
+    R.nrm = R.front ? n0 : mul(n0, -1.0);
+  } else if (!(FEAT & kFeatRect) || kind <= 1u) {
     V c = ld3(r);
     if (kind == 1u) c = add(c, mul(ld3(r + 3), (time - r[7]) / r[8]));
     const V outward = divs(sub(R.p, c), r[6]);

@@ -309,7 +309,7 @@ class TorchTracer:
 def update_world(dw, a: torch.Tensor, xv: torch.Tensor | None = None):
     """New numbers for a dynamic world.DeviceWorld from torch tensors of its device
     (rtw_world_update_device on torch's current stream, no host round trip): a is
-    (n_prims, 9) float64 in list order, xv (n_xforms, 4, 3) float64 or None (the transforms
+    (n_prims, 9) float64 in list order (a triangle's row is its three vertices v0, v1, v2), xv (n_xforms, 4, 3) float64 or None (the transforms
     keep their values).  Renders and queries enqueued afterwards on that stream see the new
     world; torch's caching allocator keeps the tensors' memory valid for work of that stream."""
     _numbers_to_world(dw.update_device, dw, a, xv)

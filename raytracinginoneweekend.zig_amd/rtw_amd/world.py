@@ -23,6 +23,7 @@ from . import (HIT_DTYPE, RAY_DTYPE, RTW_EINVAL, SURFACE_DTYPE, Camera, Params, 
                _surface, camera_init, lib)
 
 PRIM_SPHERE, PRIM_MOVING_SPHERE, PRIM_XY_RECT, PRIM_XZ_RECT, PRIM_YZ_RECT = 0, 1, 2, 3, 4
+PRIM_TRIANGLE = 5  # rtw_hip.h RTW_PRIM_TRIANGLE: a = v0[3], v1[3], v2[3] (not in the reference; csrc/rtw_tri.hpp)
 XF_TRANSLATE, XF_ROTATE_Y = 0, 1
 TEX_SOLID, TEX_CHECKER, TEX_NOISE, TEX_IMAGE = 0, 1, 2, 3
 WMAT_LAMBERT, WMAT_METAL, WMAT_DIELECTRIC, WMAT_LIGHT = 0, 1, 2, 3
@@ -98,6 +99,8 @@ def _wlib():
                                              C.c_uint64 * 8]
     if hasattr(L, "rtw_world_launch_info"):  # (A/B timing may load an older build without it)
         L.rtw_world_launch_info.argtypes = [C.c_void_p, P(Params), C.c_uint32 * 6]
+    if hasattr(L, "rtw_world_trace_tri_host"):
+        L.rtw_world_trace_tri_host.argtypes = [P(WorldDesc), C.c_void_p, C.c_size_t, P(QueryOpts), C.c_void_p]
     L._world_ready = True
     return L
 
@@ -383,6 +386,65 @@ def mirror_points_host(desc: WorldDesc, rays, hits, hits2, cam_prev, a_prev=None
                                                 C.byref(cam_prev), a.ctypes.data if a is not None else None,
                                                 xv.ctypes.data if xv is not None and xv.size else None,
                                                 C.byref(opts) if opts is not None else None, out.ctypes.data))
+    return out
+
+
+def mesh_prims(vertices, faces, mat: int, xform: int = -1) -> list:
+    """The triangles of an indexed mesh as a list of Prim (PRIM_TRIANGLE): vertices (n, 3) float, faces (m, 3) int
+    indices into them (the winding gives the normal: (v1 - v0) x (v2 - v0)), one material and transform chain for
+    all.  Shared vertices keep their bits, which is what makes a closed mesh watertight (csrc/rtw_tri.hpp)."""
+    v = np.ascontiguousarray(vertices, np.float64)
+    f = np.ascontiguousarray(faces, np.int64)
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError("vertices must be (n, 3) and faces (m, 3)")
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError("a face index is out of range")
+    out = []
+    for tri in v[f].reshape(-1, 9):
+        p = Prim()
+        p.kind, p.mat, p.xform = PRIM_TRIANGLE, int(mat), int(xform)
+        for k in range(9):
+            p.a[k] = float(tri[k])
+        out.append(p)
+    return out
+
+
+def load_obj(path: str):
+    """A Wavefront OBJ's geometry: (vertices (n, 3) float64, faces (m, 3) int64).  `v` and `f` lines only (every
+    other line is skipped); a polygon is fanned from its first vertex; an index may be negative (relative to the
+    vertices read so far) and may carry /vt/vn parts, which are ignored."""
+    verts, faces = [], []
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            t = line.split("#", 1)[0].split()
+            if not t:
+                continue
+            if t[0] == "v":
+                if len(t) < 4:
+                    raise ValueError(f"{path}:{ln}: a vertex needs three coordinates")
+                verts.append([float(t[1]), float(t[2]), float(t[3])])
+            elif t[0] == "f":
+                idx = []
+                for w in t[1:]:
+                    i = int(w.split("/")[0])
+                    i = i - 1 if i > 0 else len(verts) + i
+                    if i < 0 or i >= len(verts) or int(w.split("/")[0]) == 0:
+                        raise ValueError(f"{path}:{ln}: vertex index {w} out of range")
+                    idx.append(i)
+                if len(idx) < 3:
+                    raise ValueError(f"{path}:{ln}: a face needs three vertices")
+                for k in range(1, len(idx) - 1):
+                    faces.append([idx[0], idx[k], idx[k + 1]])
+    return np.array(verts, np.float64).reshape(-1, 3), np.array(faces, np.int64).reshape(-1, 3)
+
+
+def trace_tri_host(desc: WorldDesc, rays, opts: QueryOpts | None = None) -> np.ndarray:
+    """rtw_world_trace_tri_host (no GPU): rays (n,) RAY_DTYPE -> (n,) HIT_DTYPE, the closest hit of each ray over
+    the TRIANGLES of `desc` only (the reference's sequential loop through csrc/rtw_tri.hpp); a miss is all zero."""
+    r = np.ascontiguousarray(rays, RAY_DTYPE).reshape(-1)
+    out = np.zeros(r.size, HIT_DTYPE)
+    _check(_wlib().rtw_world_trace_tri_host(C.byref(desc), r.ctypes.data, r.size,
+                                            C.byref(opts) if opts is not None else None, out.ctypes.data))
     return out
 
 
