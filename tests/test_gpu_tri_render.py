@@ -9,7 +9,8 @@ triangles each (tri_helpers.rect_tris, wound so that n = +e_k):
   T3  >= kLeafOneMin untransformed spheres plus axis-aligned cards as triangle pairs: linear, union, per lane;
 General triangles have no oracle:
   T4a linear == union == lane == features ALL on jittered meshes under every material, some under chains;
-  T4b a closed mesh of lights around the camera: every pixel is the quantised emit colour.
+  T4b a closed mesh of lights around the camera: every pixel is the quantised emit colour; also with the mesh
+      under a 3-op chain, and for a 64-gon bipyramid with the camera aimed at an apex of valence 64.
 On the parent every one of these worlds is RTW_EINVAL (kind 5)."""
 import os
 import subprocess
@@ -232,6 +233,60 @@ def test_t4b_a_closed_mesh_of_lights_leaks_nothing(rtw, W, seed, linear):
                 assert counts["segments"] == counts["samples"]  # every sample ends at its first hit
     finally:
         dev.close()
+
+
+def _assert_all_emit(rtw, W, tables, cams, frame, what):
+    """Every pixel of every camera is the quantised emit colour, through the BVH (union and lane requests) and
+    the linear loop; every sample ends at its first hit."""
+    desc, keep = _to_desc(W, *tables)
+    want = np.array([int(256 * min(max(np.sqrt(c), 0.0), 0.999)) for c in T.ENCLOSURE_EMIT], np.uint8)
+    w, h, spp = frame
+    for linear in (False, True):
+        dev = Dev(W, desc, linear=linear)
+        try:
+            assert (dev.dw.bvh_info()["nodes"] == 0) == linear
+            for k, cam in enumerate(cams):
+                for trav in ("union",) if linear else ("union", "lane"):
+                    p = rtw.make_params(w, h, spp, background=(0.0, 0.0, 0.0), world_traversal=trav)
+                    rgb, mean, counts = dev.render(rtw, cam, p)
+                    bad = (rgb != want).any(axis=2)
+                    assert not bad.any(), (what, linear, k, trav, int(bad.sum()), rgb[bad][:4].tolist(), want.tolist())
+                    assert counts["segments"] == counts["samples"]
+        finally:
+            dev.close()
+
+
+def test_t4b_closed_mesh_under_a_chain_leaks_nothing(rtw, W):
+    """T4b's enclosure held in the object space of a 3-op chain (RotateY, Translate, RotateY) that puts it back
+    around the camera: the rays reach the inside test through to_object's roundings."""
+    from helpers import chain_to_object
+    prims, _, tex, mats, perl, imgs = T.enclosure_world(W, 5)
+    xf = dict(n=3, op=[W.XF_ROTATE_Y, W.XF_TRANSLATE, W.XF_ROTATE_Y],
+              v=[(float(np.sin(0.8)), float(np.cos(0.8)), 0.8), (1.5, -0.75, 2.25), (float(np.sin(-1.9)), float(np.cos(-1.9)), -1.9)])
+    for q in prims:
+        q["xform"] = 0
+        q["a"] = [float(c) for v in np.array(q["a"]).reshape(3, 3) for c in chain_to_object(xf, v)]
+    assert len(prims) == 320
+    cams = [rtw.camera_init((0.3, -0.2, 0.4), look_at, (0, 1, 0) if k < 2 else (1, 0, 0), vfov, 1.0, 0.2, 1.0, 0.0, 1.0)
+            for k, (look_at, vfov) in enumerate((((0, 0, -1), 120.0), ((1, 0.3, 0.2), 150.0), ((-0.2, 1, 0.1), 90.0)))]
+    _assert_all_emit(rtw, W, (prims, [xf], tex, mats, perl, imgs), cams, (40, 40, 8), "enclosure under a chain")
+
+
+def test_t4b_bipyramid_apex_of_valence_64_leaks_nothing(rtw, W):
+    """A 64-gon bipyramid of lights around the camera, the camera aimed at an apex where 64 triangles meet (and
+    once at the other): 64x64 at 4 spp, every sample inside the fan."""
+    from tri_exact import bipyramid
+    v, f = bipyramid(64, 6.0, 5.0)
+    rng = np.random.default_rng(6)
+    v = T.rot_y(v * (1 + 0.03 * rng.uniform(-1, 1, v.shape)), 0.37)[:, [1, 2, 0]] * np.array([1.0, 1.2, 0.9])  # (no face axis-aligned)
+    tex = [dict(kind=W.TEX_SOLID, color=T.ENCLOSURE_EMIT)]
+    mats = [dict(kind=W.WMAT_LIGHT, tex=0)]
+    tables = (T.mesh_dicts(W, v, f, 0), [], tex, mats, [], [])
+    assert len(tables[0]) == 128
+    eye = (0.2, 0.1, -0.15)
+    cams = [rtw.camera_init(eye, tuple(float(c) for c in v[64 + k]), (0, 1, 0), vfov, 1.0, 0.05, 1.0, 0.0, 1.0)
+            for k, vfov in ((0, 20.0), (0, 90.0), (1, 2.0))]
+    _assert_all_emit(rtw, W, tables, cams, (64, 64, 4), "bipyramid")
 
 
 @pytest.mark.skipif(UNPACKED, reason="this is the child")
